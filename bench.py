@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MSDeformAttn pixel decoder + PCTrans transformer decoder forward throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Started bare (`python bench.py --gpus N`, no WORLD_SIZE in the environment) this
 process never touches a GPU: it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
@@ -91,6 +91,9 @@ def parse():
                          "untrained network gives)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's predictions and mask "
+                         "features) as DIR/<name>.npy, float32 / float64; large arrays as a fixed, seeded sample")
     return ap.parse_args()
 
 
@@ -153,6 +156,54 @@ def synth_features(shapes, batch, image, device, seed):
     g = torch.Generator(device=device).manual_seed(seed)
     return {k: torch.randn(batch, s.channels, image // s.stride, image // s.stride, device=device, generator=g)
             for k, s in shapes.items()}
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6    # the arrays' data; with the .npy headers the directory stays under 64 MB
+
+
+def flatten_outputs(obj, prefix, out):
+    """The tensors of a (nested) dict / list / tuple output, keyed by their path joined with '.'.  Insertion order is
+    the structure's own, so two runs list the same names in the same order."""
+    if torch.is_tensor(obj):
+        out[prefix] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            flatten_outputs(v, "%s.%s" % (prefix, k) if prefix else str(k), out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            flatten_outputs(v, "%s.%d" % (prefix, i) if prefix else str(i), out)
+    return out
+
+
+def dump_outputs(outputs, dirname, budget=DUMP_BUDGET_BYTES):
+    """Write every tensor of `outputs` as <dirname>/<name>.npy: float64 stays float64, everything else becomes float32.
+    The budget is shared out smallest array first, each taking at most an equal part of what is left: an array that
+    does not fit its part is written as the elements at that many flat indices, drawn (sorted, without replacement) by a
+    generator seeded from the array's name and shape, so that two runs with the same arguments sample the same positions.
+    Returns {name: {"shape", "sampled"}} where "sampled" is the number of elements written, or None for the whole array."""
+    import zlib
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    tensors = flatten_outputs(outputs, "", {})
+    item = {k: 8 if t.dtype == torch.float64 else 4 for k, t in tensors.items()}
+    order = sorted(tensors, key=lambda k: (tensors[k].numel() * item[k], k))
+    take, left = {}, budget
+    for i, k in enumerate(order):
+        take[k] = min(tensors[k].numel(), left // (len(order) - i) // item[k])
+        left -= take[k] * item[k]
+    manifest = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        flat = t.reshape(-1)
+        sampled = take[name] < flat.numel()
+        if sampled:
+            seed = zlib.crc32(("%s %s" % (name, list(t.shape))).encode())
+            idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), take[name], replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float64 if item[name] == 8 else torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a if sampled else a.reshape(tuple(t.shape)))
+        manifest[name] = {"shape": list(t.shape), "sampled": take[name] if sampled else None}
+    return manifest
 
 
 def host_cpu():
@@ -379,8 +430,7 @@ def main():
 
     def step():
         with torch.no_grad(), amp:
-            pred, _ = head(feats)
-        return pred
+            return head(feats)
 
     for _ in range(2):          # untimed pre-warm: MIOpen's first-call kernel search for the 3x3 convolutions
         step()
@@ -457,9 +507,11 @@ def main():
     step_marks[0].record()
     rec_marks = [_kt.count()]
     for i_step in range(args.steps):
-        pred = step()
+        pred, mask_features = step()
         step_marks[i_step + 1].record()       # one event per step: a straggler step shows in the JSON (step_ms)
         rec_marks.append(_kt.count())         # ... and which of the hook-timed launches belong to it
+        if i_step + 1 < args.steps:
+            del mask_features                 # (only the last step's is kept, for --dump-outputs)
     fence()
     elapsed = time.perf_counter() - t0
     gc.enable()
@@ -480,6 +532,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     assert torch.isfinite(pred["pred_masks"].float()).all(), "non-finite output"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of MaskFormerHead.forward receives (predictions dict, mask features), from the last timed step
+        dumped = dump_outputs(dict(pred, mask_features=mask_features), args.dump_outputs)
 
     rc = 0
     if rank == 0:
@@ -517,6 +573,7 @@ def main():
             "step_longest_timed_kernel": ["%.2f %s" % sl for sl in step_longest],
             "ms_per_step": 1e3 * elapsed / args.steps,
             "miopen_dirs_rank0": MIOPEN_DIRS or None,
+            "dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None,
             "ms_per_step_per_rank": {"min": 1e3 * min(per_rank) / args.steps, "max": 1e3 * max(per_rank) / args.steps,
                                      "ranks": [1e3 * x / args.steps for x in per_rank]},
             "higher_is_better": True,
