@@ -684,7 +684,9 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
       const float C = __builtin_bit_cast(float, gb) * __builtin_bit_cast(float, ab);
       int e;
       (void)frexpf(C, &e);                                                    // C < 2^e
-      fixed_ok = gb < 0x7f800000u && ab < 0x7f800000u && C < 1e30f;
+      // (below C = 2^-80 the shift would pass 100 and the clamp would coarsen the quantum beyond 2^-21 of C: grad_value
+      // lost precision from C ~ 1e-27 on and vanished below ~1e-31; such items, like non-finite ones, take the float path)
+      fixed_ok = gb < 0x7f800000u && ab < 0x7f800000u && C < 1e30f && e > -80;
       // a window dword receives at most BLOCK * P = 1024 contributions w_corner * attn * grad_out, each below C < 2^e:
       // rounded to multiples of 2^(e - 21) every contribution is below 2^21 in magnitude and the int32 sums stay inside
       // (-2^31, 2^31) (a contribution also has to stay below 2^22 for the magic-constant rounding)

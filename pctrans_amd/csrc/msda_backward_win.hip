@@ -217,7 +217,8 @@ __global__ __launch_bounds__(WIN_BLOCK, 2) void msda_backward_win_kernel(
       const float C = __builtin_bit_cast(float, gb) * __builtin_bit_cast(float, ab);
       int e;
       (void)frexpf(C, &e);                                          // C < 2^e
-      fixed_ok = gb < 0x7f800000u && ab < 0x7f800000u && C < 1e30f;
+      // (e > -80: the shift stays <= 100, so the quantum is 2^-21 of C down to C = 2^-80; smaller bounds take the float path)
+      fixed_ok = gb < 0x7f800000u && ab < 0x7f800000u && C < 1e30f && e > -80;
       const int shift = min(21 - e, 100);
       scale = ldexpf(1.f, shift);
       inv_scale = ldexpf(1.f, -shift);

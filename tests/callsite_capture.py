@@ -5,9 +5,14 @@ by reference), its output, and for the MSDeformAttn entries the kernel family th
 that calls another one (a fallback) is recorded once, as the outer call.
 
 `select`: image indices to keep (None = all).  The batch axis follows the call site's layout: encoder token rows and NCHW
-maps are image-major (axis 0), the decoder's attention operands are [tokens, N, C] (axis 1), its masks [N, ...]."""
+maps are image-major (axis 0), the decoder's attention operands are [tokens, N, C] (axis 1), its masks [N, ...].
+
+`entries`: the entry points to wrap (default: the head's forward, ENTRY_POINTS).  A training step adds TRAINING_ENTRIES:
+the MSDeformAttn backward (called from autograd's device thread, so the re-entry depth is per thread; its record carries
+the backward family) and the batched assignment of the matcher."""
 import functools
 import inspect
+import threading
 
 import torch
 
@@ -34,6 +39,14 @@ LAYOUTS = {
 ENTRY_POINTS = tuple(LAYOUTS)
 MSDA_ENTRIES = ("MSDA.ms_deform_attn_fused_forward", "MSDA.ms_deform_attn_forward")
 
+# the training step's own entry points (looked up as module attributes by MSDeformAttnFunction.backward and
+# Point_HungarianMatcher._assign_padded)
+TRAINING_LAYOUTS = {
+    "MSDA.ms_deform_attn_backward": {"value": 0, "sampling_loc": 0, "attn_weight": 0, "grad_output": 0, "out": 0},
+    "fused_ops.lsap": {"cost": 0, "num_target": 0, "out": 0},
+}
+TRAINING_ENTRIES = tuple(TRAINING_LAYOUTS)
+
 
 def _module(prefix):
     import pctrans_amd.dynamic_mask_head as dmh
@@ -43,8 +56,8 @@ def _module(prefix):
 
 
 class Call:
-    """One recorded call: `args` {name: value}, `out`, `kernel` (MSDeformAttn family id or None), `images` (the original
-    indices of the images kept, None = all)."""
+    """One recorded call: `args` {name: value}, `out`, `kernel` (MSDeformAttn forward or backward family id, else None),
+    `images` (the original indices of the images kept, None = all)."""
 
     def __init__(self, entry, args, out, kernel, images):
         self.entry, self.args, self.out, self.kernel, self.images = entry, args, out, kernel, images
@@ -73,13 +86,13 @@ def _take_any(o, axis, images):
 
 
 class CallsiteCapture:
-    def __init__(self, select=None):
+    def __init__(self, select=None, entries=ENTRY_POINTS):
         self.select = None if select is None else [int(i) for i in select]
-        self.calls = {e: [] for e in ENTRY_POINTS}
-        self._depth = 0
+        self.calls = {e: [] for e in entries}
+        self._local = threading.local()                   # .depth: wrapped calls in progress on this thread
 
     def install(self, monkeypatch):
-        for entry in ENTRY_POINTS:
+        for entry in self.calls:
             prefix, name = entry.split(".")
             mod = _module(prefix)
             monkeypatch.setattr(mod, name, self._wrap(entry, getattr(mod, name)))
@@ -95,11 +108,12 @@ class CallsiteCapture:
 
     def _wrap(self, entry, fn):
         sig = inspect.signature(fn)
-        layout = LAYOUTS[entry]
+        layout = LAYOUTS[entry] if entry in LAYOUTS else TRAINING_LAYOUTS[entry]
 
         @functools.wraps(fn)
         def wrapper(*a, **kw):
-            if self._depth:                                   # a fallback inside another wrapped entry point
+            depth = getattr(self._local, "depth", 0)
+            if depth:                                         # a fallback inside another wrapped entry point
                 return fn(*a, **kw)
             bound = sig.bind(*a, **kw)
             bound.apply_defaults()
@@ -113,11 +127,11 @@ class CallsiteCapture:
                 # the kernel reads these fp32 features (the caller's copy when it hands one over)
                 ff = args["feats_f32"] if args["feats_f32"] is not None else args["mask_feats"].detach().float()
                 rec["feats_f32"] = _take(ff, 0, images)
-            self._depth += 1
+            self._local.depth = depth + 1
             try:
                 out = fn(*a, **kw)
             finally:
-                self._depth -= 1
+                self._local.depth = depth
             if entry.endswith("_into"):
                 # the slice of `out` this call wrote, read after the call; the row offset is in rec["row_offset"]
                 h, w = args["x"].shape[2], args["x"].shape[3]
@@ -130,6 +144,9 @@ class CallsiteCapture:
             if entry in MSDA_ENTRIES:
                 from pctrans_amd import _lib
                 kernel = int(_lib.lib().pct_msda_last_kernel())
+            elif entry == "MSDA.ms_deform_attn_backward":
+                from pctrans_amd import _lib
+                kernel = int(_lib.lib().pct_msda_last_bwd_kernel())
             self.calls[entry].append(Call(entry, rec, result, kernel, images))
             return out
         return wrapper

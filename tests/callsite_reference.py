@@ -66,6 +66,77 @@ def msda(value, spatial_shapes, sampling_loc, attn_weight, dtype=F64):
     return ms_deform_attn_core_pytorch(value.to(dtype), spatial_shapes, sampling_loc.to(dtype), attn_weight.to(dtype))
 
 
+def pixel_coords(sampling_loc, spatial_shapes, dtype=F64):
+    """(x, y) = loc * (W_l, H_l) - 0.5 per level: [N, Lq, M, L, P, 2].  In float64 this is exact for fp32 locations."""
+    wh = torch.stack([spatial_shapes[:, 1], spatial_shapes[:, 0]], -1).to(dtype=dtype, device=sampling_loc.device)
+    return sampling_loc.to(dtype) * wh[:, None, :] - 0.5
+
+
+def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, dtype=F64,
+                  delta=1e-4):
+    """The sampling op's backward as the reference states it (ops/src/cuda/ms_deform_im2col_cuda.cuh:92-164): a sample
+    counts when -1 < y < H and -1 < x < W, each of its four corners when it lies on the map, with the bilinear weights of
+    the cell `floor(x), floor(y)`.  -> (grad_value [N, S, M, D], grad_loc [N, Lq, M, L, P, 2, 2], grad_attn [N, Lq, M, L, P]).
+
+    grad_value and grad_attn are continuous in the locations; grad_loc is not: it jumps where a coordinate crosses an
+    integer (the cell changes) and at the gate (-1 and H).  So grad_loc[..., c, :] holds two candidates for coordinate c:
+    where that coordinate is within `delta` px of an integer k, the derivatives of the cells on either side of k (floor
+    k - 1 and floor k, each evaluated at the coordinate itself; a side beyond the gate gives 0), else the single derivative
+    twice.  The other coordinate keeps its own cell and gate.  `delta=0` gives the plain derivative (the fp32 yardstick)."""
+    N, S, M, D = value.shape
+    _, Lq, _, L, P, _ = sampling_loc.shape
+    dev = value.device
+    vflat = value.to(dtype).reshape(N * S * M, D)
+    attn = attn_weight.to(dtype)
+    go = grad_output.to(dtype).reshape(N, Lq, M, 1, D)                       # broadcast over the points
+    xy = pixel_coords(sampling_loc, spatial_shapes, dtype)
+    grad_value = torch.zeros(N * S * M, D, dtype=dtype, device=dev)
+    grad_loc = torch.zeros(N, Lq, M, L, P, 2, 2, dtype=dtype, device=dev)
+    grad_attn = torch.zeros(N, Lq, M, L, P, dtype=dtype, device=dev)
+    n_idx = torch.arange(N, device=dev).view(N, 1, 1, 1)
+    m_idx = torch.arange(M, device=dev).view(1, 1, M, 1)
+    for l, (H, W) in enumerate(spatial_shapes.tolist()):
+        start = int(level_start_index[l])
+        x, y = xy[:, :, :, l, :, 0], xy[:, :, :, l, :, 1]                    # [N, Lq, M, P]
+        a = attn[:, :, :, l, :, None]                                         # [N, Lq, M, P, 1]
+
+        def cell(fx, fy, live):
+            """-> (value, d value / dx, d value / dy) [N, Lq, M, P, D] of the cell with corner (fx, fy), zero where not
+            `live`, and the corners (index, weight, on the map) for the scatter."""
+            lx, ly = (x - fx)[..., None], (y - fy)[..., None]
+            hx, hy = 1 - lx, 1 - ly
+            v, corners = [], []
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    r, c = fy + dy, fx + dx
+                    ok = live & (r >= 0) & (r < H) & (c >= 0) & (c < W)
+                    idx = ((n_idx * S + start + r.clamp(0, H - 1) * W + c.clamp(0, W - 1)) * M + m_idx).long()
+                    v.append(torch.where(ok[..., None], vflat[idx], 0))
+                    corners.append((idx, ok, (ly if dy else hy) * (lx if dx else hx)))
+            v00, v01, v10, v11 = v
+            val = hy * hx * v00 + hy * lx * v01 + ly * hx * v10 + ly * lx * v11
+            d_dx = hy * (v01 - v00) + ly * (v11 - v10)
+            d_dy = hx * (v10 - v00) + lx * (v11 - v01)
+            return val, d_dx, d_dy, corners
+
+        gx, gy = (x > -1) & (x < W), (y > -1) & (y < H)
+        fx0, fy0 = torch.floor(x).long(), torch.floor(y).long()
+        val, d_dx, d_dy, corners = cell(fx0, fy0, gx & gy)
+        gg = go * a                                                           # d out / d sampled value
+        grad_attn[:, :, :, l] = (go * val).sum(-1)
+        for idx, ok, w in corners:
+            contrib = (w * gg).expand(*idx.shape, D)
+            grad_value.index_add_(0, idx[ok], contrib[ok])
+        for axis, (t, f0, size, gate, other) in enumerate(((x, fx0, W, gx, gy), (y, fy0, H, gy, gx))):
+            k = torch.round(t)
+            near = (t - k).abs() < delta if delta > 0 else torch.zeros_like(gate)
+            for side, f in enumerate((torch.where(near, k.long() - 1, f0), torch.where(near, k.long(), f0))):
+                live = torch.where(near, (f >= -1) & (f <= size - 1), gate) & other
+                _, ddx, ddy, _ = cell(f, fy0, live) if axis == 0 else cell(fx0, f, live)
+                grad_loc[:, :, :, l, :, axis, side] = size * (gg * (ddx if axis == 0 else ddy)).sum(-1)
+    return grad_value.reshape(N, S, M, D), grad_loc, grad_attn
+
+
 def msda_fused(value, spatial_shapes, reference_points, sampling_offsets, attention_logits, dtype=F64):
     """softmax over L*P, ref + off / (W, H), then the sampling op"""
     N, Lq, M, L, P, _ = sampling_offsets.shape

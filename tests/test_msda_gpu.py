@@ -322,14 +322,22 @@ def test_backward_windowed_kernel_vs_oracle(MSDA, cid, kw):
         np.testing.assert_allclose(g, w, rtol=0, atol=2e-5 * scale, err_msg=name)
 
 
-@pytest.mark.parametrize("go_scale", [1e-20, 1.0, 1e20])
+@pytest.mark.parametrize("go_scale", [1e-36, 1e-32, 1e-28, 1e-24, 1e-20, 1.0, 1e20])
 def test_backward_windowed_fixed_point_follows_the_gradient_scale(MSDA, go_scale):
     """The LDS accumulators are int32 fixed point with a per-tile power-of-two scale taken from max|grad_out| *
-    max|attn|: the error stays relative to the gradient's own magnitude over 40 orders of magnitude."""
+    max|attn|: the error stays relative to the gradient's own magnitude from the bottom of the fp32 normal range to
+    1e20 (a tile whose bound is below 2^-80, where the scale exponent would pass its limit of 100, takes the float path).
+    The windowed kernel is forced: `auto` takes the column kernel at this size."""
+    from pctrans_amd import _lib
     c = make_case(seed=74, N=1, M=8, D=16, Lq=5376, P=4, shapes=[(16, 16), (32, 32), (64, 64)], model_like=True)
     go = (np.random.RandomState(174).standard_normal((1, 5376, 128)) * go_scale).astype(np.float32)
     want = orc.backward(c["value"], c["shapes"], c["starts"], c["loc"], c["attn"], go)
-    got = run_bwd(MSDA, c, go)
+    _lib.lib().pct_msda_set_bwd_kernel_choice(1)
+    try:
+        got = run_bwd(MSDA, c, go)
+        assert _lib.lib().pct_msda_last_bwd_kernel() == 1
+    finally:
+        _lib.lib().pct_msda_set_bwd_kernel_choice(-1)
     for g, w, name in zip(got, want, ("grad_value", "grad_attn")):
         np.testing.assert_allclose(g / go_scale, w / go_scale, rtol=0,
                                    atol=2e-5 * max(1.0, float(np.abs(w / go_scale).max())), err_msg=name)
