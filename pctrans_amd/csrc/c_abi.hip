@@ -5,8 +5,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <stdio.h>
-
 #include "../../include/pctrans_hip.h"
 #include "msda_common.hpp"
 
@@ -33,16 +31,12 @@ int launch_linear_ln_split(const float *x, long long ldx, const float *w, unsign
 template <typename A>
 int launch_msda_backward(const void *, const int64_t *, const int64_t *, const void *, const void *, const void *,
                          int, int, int, int, int, int, int, void *, void *, void *, hipStream_t);
-void set_win_stamp_buffer(void *);
 int launch_dyn_mask_head_fused(const float *, const float *, const float *, int, int, int, int, int, int, int, int, int,
                                void *, void *, unsigned char *, hipStream_t);
 int launch_dyn_mask_head_mfma(const float *, const float *, const float *, int, int, int, int, int, int, int, int, int,
                               void *, void *, unsigned char *, hipStream_t);
 int prepare_win_queue_device();
 int prepare_msda_backward_col_device();
-const char *msda_forward_col_build_flags();
-const char *msda_backward_col_build_flags();
-const char *ffn_fused_build_flags();
 int prepare_ffn_device();
 int launch_msda_forward_planes(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int, int, int,
                                int, int, int, void *, hipStream_t, const float *, long long);
@@ -270,9 +264,6 @@ int pct_ms_deform_attn_backward_f64(const double *value, const int64_t *spatial_
                                spatial_size, num_heads, channels, num_levels, num_query, num_point, im2col_step,
                                grad_value, grad_sampling_loc, grad_attn_weight, stream);
 }
-
-/* diagnostic hook, not part of the product ABI: per-phase cycle stamps of the windowed MSDeformAttn kernel */
-__attribute__((visibility("default"))) void pct_debug_set_stamp_buffer(void *p) { pct::set_win_stamp_buffer(p); }
 
 int pct_dynamic_mask_head_forward(const float *mask_feat, const float *ref_points, const float *params, int batch,
                                   int channels, int num_query, int height, int width, int stride, int rel_coord,
@@ -503,22 +494,7 @@ int pct_prepare_device(void)
   return a ? a : (b ? b : c);
 }
 
-const char *pct_build_info(void)
-{
-  static char buf[768];
-  static const bool once = [] {
-#ifdef PCT_EXPERIMENT_BUILD
-    const char *exp = "1";
-#else
-    const char *exp = "0";
-#endif
-    snprintf(buf, sizeof(buf), "experiment=%s; target=gfx950; %s; %s; %s", exp, pct::msda_forward_col_build_flags(),
-             pct::msda_backward_col_build_flags(), pct::ffn_fused_build_flags());
-    return true;
-  }();
-  (void)once;
-  return buf;
-}
+const char *pct_build_info(void) { return "target=gfx950"; }
 
 int pct_cross_attention_bf16(const void *q_content, const void *q_pos, const void *k_content, const void *k_pos, const void *v,
                              const unsigned char *mask, const unsigned char *row_open, int batch, int heads, int num_query,

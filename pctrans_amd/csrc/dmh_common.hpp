@@ -5,10 +5,6 @@
 #pragma once
 #include "msda_common.hpp"
 
-#ifndef PCT_DMH_L2_MFMA
-#define PCT_DMH_L2_MFMA 1
-#endif
-
 namespace pct {
 
 typedef __bf16 dm_bf16x4 __attribute__((ext_vector_type(4)));
@@ -269,7 +265,6 @@ struct DmhPair {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
       c1[t] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a1, xb[t], dm_f32x4{b1v[0], b1v[1], b1v[2], b1v[3]}, 0, 0, 0);
-#if PCT_DMH_L2_MFMA
     // layer 2 on the matrix cores too (per tile: 2 conversions + 2 packed maxima + 1 MFMA instead of 4 maxima, 4 FMAs, a lane
     // swap and 2 additions -- the kernel is bound by vector issue, its matrix pipe 18 % busy); its input is rounded to bf16 as
     // the reference's autocast convolution rounds it
@@ -279,23 +274,6 @@ struct DmhPair {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
       out[t] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a2, xc[t], dm_f32x4{b2, b2, b2, b2}, 0, 0, 0)[0];
-#else
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      float part = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) part = fmaf(w2v[r], dm_relu(c1[t][r]), part);
-      // rows 4g..4g+3 (+) rows of the partner group (lane ^ 16): v_permlane16_swap hands the even 16-lane rows the odd
-      // rows' value and the reverse; the sum of the two results is the pair's total in all four rows (a + b == b + a:
-      // the same bits as the ds_bpermute form it replaces, without the trip through the LDS pipe)
-      // (inline asm, with the two wait states a vector write -> v_permlane read needs inside the string: given the same
-      // value in both operands, the builtin's two results are taken for equal by hipcc (ROCm 7.2) and their sum is
-      // folded into 2 x one of them -- also with one operand behind an empty asm)
-      float pa = part, pb = part;
-      asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(pa), "+v"(pb));
-      out[t] = (pa + pb) + b2;
-    }
-#endif
   }
 };
 

@@ -24,9 +24,7 @@
 
 namespace pct {
 
-#ifndef PCT_DMH_WGS
-#define PCT_DMH_WGS 2          /* workgroups per CU the register budget is set for (3: 168 registers, ~30 spilled: 0.36 -> 0.53 ms at batch 64) */
-#endif
+constexpr int FZ_WGS = 2;              // workgroups per CU the register budget is set for (3: 168 registers, ~30 spilled: 0.36 -> 0.53 ms at batch 64)
 constexpr int FZ_W = 128;              // feature-map width this kernel is built for (8 tiles of 16 pixels per row)
 constexpr int FZ_BAND = 8;             // rows per workgroup
 constexpr int FZ_TILES = 20;           // per wave: 2 x 8 own tiles + 4 halo tiles
@@ -48,10 +46,10 @@ __global__ __launch_bounds__(64) void dmh_prepare_kernel(const float *__restrict
 
 // up [N, Q, 2H, 256] bf16, amask [N, Q, (H/SC) * (128/SC)] bytes
 template <bool REL, int SC>
-__global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float *__restrict__ feat,
-                                                           const unsigned *__restrict__ ws, const int Q, const int H,
-                                                           const int stride, __bf16 *__restrict__ up,
-                                                           unsigned char *__restrict__ amask)
+__global__ __launch_bounds__(256, FZ_WGS) void dmh_fused_kernel(const float *__restrict__ feat,
+                                                       const unsigned *__restrict__ ws, const int Q, const int H,
+                                                       const int stride, __bf16 *__restrict__ up,
+                                                       unsigned char *__restrict__ amask)
 {
   constexpr int W = FZ_W, C = DMH_C;
   __shared__ __attribute__((aligned(16))) unsigned short xch[2][FZ_SLOTS][2][W];   // [buffer][row slot][query of the pair][x]
@@ -86,12 +84,6 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
   const int OW = 2 * W;
   const int th_w = W / SC;                                                   // attention-mask row length
 
-#ifdef FZ_STAMP
-  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tp = 0;
-#define FZ_ST(i) do { __builtin_amdgcn_sched_barrier(0); unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); __builtin_amdgcn_sched_barrier(0); if ((i) >= 0) ts[(i) < 0 ? 0 : (i)] += t_ - tp; tp = t_; } while (0)
-#else
-#define FZ_ST(i) do { } while (0)
-#endif
   const int npairs = (Q + 1) / 2;
   // the pairs' parameters in the form the MFMAs take them, written by dmh_prepare_kernel: 5 coalesced 16-byte loads per lane
   // and pair instead of ~40 scattered dword loads and ~100 vector instructions of splitting and packing in EACH of the
@@ -103,23 +95,18 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
   // the fp32 evaluation decides: evaluated once here with the very expression the two-launch path uses
   const bool edge_masked = dm_mask_byte(0.5f, 0.5f, -0.00390625f, -0.00390625f, -0.00390625f, -0.00390625f) != 0;
   for (int pr = 0; pr < npairs; ++pr) {
-    FZ_ST(-1);
     DmhPair<REL> pw;
     pw.take(prep);
     prep = DmhPair<REL>::fetch_prepared(wsn + (size_t)min(pr + 1, npairs - 1) * (DmhPair<REL>::PREP_DWORDS * 64), lane);
     const int q_acc = min(2 * pr + qsel, Q - 1);
     const int buf = pr & 1;
-    FZ_ST(0);
 
     // ---- logits of my tiles, rounded to bf16 (what the two-launch path stores and reads back) -----------------------------
     unsigned pk0[4], pk1[4], pkh[2];
     {
       float lg[FZ_TILES];
-#ifndef FZ_BATCH
-#define FZ_BATCH 4
-#endif
 #pragma unroll
-      for (int t0 = 0; t0 < FZ_TILES; t0 += FZ_BATCH) pw.template tiles<FZ_BATCH>(fb + t0, lg + t0);
+      for (int t0 = 0; t0 < FZ_TILES; t0 += 4) pw.template tiles<4>(fb + t0, lg + t0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         pk0[k] = pack_bf16x2(lg[2 * k], lg[2 * k + 1]);
@@ -129,7 +116,6 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
       pkh[1] = pack_bf16x2(lg[18], lg[19]);
     }
 
-    FZ_ST(1);
     // ---- trade rows: group parity 0 publishes the wave's first row and its halo quarter, parity 1 the second row -------
     {
       const dm_u32x4 own = par ? dm_u32x4{pk1[0], pk1[1], pk1[2], pk1[3]} : dm_u32x4{pk0[0], pk0[1], pk0[2], pk0[3]};
@@ -137,9 +123,7 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
       if (!par)
         *reinterpret_cast<dm_u32x2 *>(&xch[buf][(wave >> 1) ? FZ_SLOTS - 1 : 0][qsel][8 * col + ht0]) = dm_u32x2{pkh[0], pkh[1]};
     }
-    FZ_ST(2);
     __syncthreads();
-    FZ_ST(3);
     // the row above my pair (parity 0) or below it (parity 1)
     const dm_u32x4 hal = *reinterpret_cast<const dm_u32x4 *>(&xch[buf][par ? 2 * wave + 3 : 2 * wave][qsel][8 * col]);
 
@@ -166,7 +150,6 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
                                                                        __builtin_bit_cast(int, e[r][1]), 0x101, 0xf, 0xf, false));
     }
 
-    FZ_ST(4);
     // ---- x2 upsample: horizontal blends of the three rows once, then the two output rows ---------------------------------
     // even output column 2 (x0 + k): source columns (x0 + k - 1, x0 + k), weights (1/4, 3/4) -- at the map's left edge
     // (1, 0) on the clamped pair; odd column: (x0 + k, x0 + k + 1), weights (3/4, 1/4)
@@ -188,13 +171,6 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
       ob[k >> 2][k & 3] = pack_bf16x2(dm_blend_y(hB0, hB1, tx[1][2 * k], tx[2][2 * k]),
                                        dm_blend_y(hB0, hB1, tx[1][2 * k + 1], tx[2][2 * k + 1]));
     }
-#ifdef FZ_DEBUG_NEAREST
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      oa[k >> 2][k & 3] = pack_bf16x2(e[par ? 0 : 1][1 + k], e[par ? 0 : 1][1 + k]);
-      ob[k >> 2][k & 3] = pack_bf16x2(e[par ? 1 : 2][1 + k], e[par ? 1 : 2][1 + k]);
-    }
-#endif
     if (wr) {
       // output rows 2 y0 + par (from window rows 0, 1) and 2 y1 + par (rows 1, 2), columns 16 col .. 16 col + 15
       __bf16 *ra = uplane + (size_t)(2 * y0 + par) * OW + 16 * col;
@@ -207,7 +183,6 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
       __builtin_nontemporal_store(ob[1], reinterpret_cast<dm_u32x4 *>(rb + 8));
     }
 
-    FZ_ST(5);
     // ---- attention mask at 1 / SC of the map: target (ty, tx) reads rows SC ty + SC/2 - 1, + 1 and the same two columns,
     // all four weights 1/2.  SC = 2: my own rows (window rows 1, 2 of parity 0); SC = 4, 8: the row above + my first row
     // (window rows 0, 1), in the waves whose first row is SC/2 (mod SC).
@@ -226,12 +201,7 @@ __global__ __launch_bounds__(256, PCT_DMH_WGS) void dmh_fused_kernel(const float
       else if constexpr (SC == 4) *reinterpret_cast<unsigned short *>(mp) = (unsigned short)bytes;
       else *mp = (unsigned char)bytes;
     }
-    FZ_ST(6);
   }
-#ifdef FZ_STAMP
-  if (blockIdx.x == 7 && threadIdx.x == 64)
-    for (int i = 0; i < 8; ++i) reinterpret_cast<unsigned long long *>(amask)[i] = ts[i];
-#endif
 }
 
 // -100: geometry not covered (the caller runs the two-launch path).  `workspace`: N * ceil(Q / 2) * 5120 bytes, 16-byte aligned.

@@ -28,48 +28,7 @@
 #include <type_traits>
 #include "msda_win_common.hpp"    // func_attr_per_device
 
-// knock-outs (WRONG RESULTS, timing only): 1 = no image transport inside the chunk loop, 2 = no bias / ReLU / split arithmetic,
-// 4 = no barrier per chunk, 16 / 32 = of the transport only the LDS stores / only the loads, 8 = no residual loads, 64 = no y stores
-#ifndef PCT_FFN_KO
-#define PCT_FFN_KO 0
-#endif
-#if PCT_FFN_KO && !defined(PCT_EXPERIMENT_BUILD)
-#error "PCT_FFN_KO gives wrong results: add -DPCT_EXPERIMENT_BUILD"
-#endif
-
-// PCT_FFN_STAMPS (experiment builds): s_memtime at the phase boundaries of every chunk, sums per workgroup in pct_ffn_stamps
-#ifndef PCT_FFN_SPREAD
-#define PCT_FFN_SPREAD 1      /* fragment reads spread between the MFMAs of a group instead of issued together at its start */
-#endif
-#ifndef PCT_FFN_STORE_NT
-#define PCT_FFN_STORE_NT 0      /* y rows with the non-temporal hint: 6.79 -> 6.97 ms, off */
-#endif
-#ifndef PCT_FFN_STAMPS
-#define PCT_FFN_STAMPS 0
-#endif
-#if PCT_FFN_STAMPS && !defined(PCT_EXPERIMENT_BUILD)
-#error "PCT_FFN_STAMPS perturbs the kernel: add -DPCT_EXPERIMENT_BUILD"
-#endif
-
 namespace pct {
-
-#if PCT_FFN_STAMPS
-__device__ unsigned long long ffn_stamps[256 * 8];
-__device__ __forceinline__ unsigned long long ff_now()
-{
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define FF_STAMP(slot)                                   \
-  do {                                                   \
-    const unsigned long long now_ = ff_now();            \
-    acc_t[slot] += now_ - last_t;                        \
-    last_t = now_;                                       \
-  } while (0)
-#else
-#define FF_STAMP(slot)
-#endif
 
 typedef float ff_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ff_f32x4 __attribute__((ext_vector_type(4)));
@@ -164,9 +123,6 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
   const int r = lane & 31, h = lane >> 5;
   const long long ntiles = (M + FF_BM - 1) / FF_BM;
   const int nch = F / FF_CH;
-#if PCT_FFN_STAMPS
-  unsigned long long acc_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_t = ff_now();
-#endif
 
   const auto img_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(img), 0, (int)((long long)nch * FF_STAGE),
                                                           0x00020000);
@@ -175,18 +131,11 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
   // seven backed up into the issuing waves (stamps: ~50 cycles per load, 700 per chunk).  Window position p = 0 .. 13 is piece
   // ORD[p] (the W2 / bias part first: see the tile seam below), stored six groups after it was requested, slot p % 7.
   ff_i32x4 gst[7];
-  bool transport = true;
   auto t_piece = [](const int p) { return p < 7 ? p + 7 : p - 7; };
   auto t_load = [&](const int p, const int image) {
-    if ((PCT_FFN_KO & (1 | 16)) && !transport) return;
     gst[p % 7] = __builtin_amdgcn_raw_buffer_load_b128(img_rsrc, tid * 16, image * FF_STAGE + t_piece(p) * (FF_BLOCK * 16), 0);
   };
   auto t_store = [&](const int p, unsigned char *stage) {
-    if ((PCT_FFN_KO & 1) && !transport) return;
-    if ((PCT_FFN_KO & 32) && !transport) {
-      asm volatile("" ::"v"(gst[p % 7]));
-      return;
-    }
     *reinterpret_cast<ff_i32x4 *>(stage + t_piece(p) * (FF_BLOCK * 16) + tid * 16) = gst[p % 7];
   };
 
@@ -222,8 +171,6 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
   for (int p = 2; p < 8; ++p) t_load(p, 1 % nch);
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   int cur = 0;                                                    // stage holding the image of the chunk about to be used
-  transport = false;
-  FF_STAMP(0);
 
   // a tile's rows of x are requested one tile ahead (under GEMM 2 of the last chunk of the tile before, when the fragments of the
   // current rows are no longer needed; a row-strided load touches 32 lines: 16 of them back to back cost 3 k cycles): lane (r, h) takes k = 16 s + 8 h .. + 7 of row r, s = 0 .. 7
@@ -251,7 +198,6 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
     ff_bf16x8 xp[8][3];
 #pragma unroll
     for (int s = 0; s < 8; ++s) ff_split8(__builtin_bit_cast(ff_f32x4, xraw[2 * s]), __builtin_bit_cast(ff_f32x4, xraw[2 * s + 1]), xp[s]);
-    FF_STAMP(1);
     ff_f32x16 y_hi[4], y_lo[4];                                   // D2[col block][cols 32][rows 32]
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
@@ -301,7 +247,6 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
     };
     w1_frags(ff_smem + cur * FF_STAGE, 0);
     load_bias(ff_smem + cur * FF_STAGE);
-    FF_STAMP(2);
 
     auto chunk_body = [&](auto last_tag, const int chunk) {
       constexpr bool LAST = decltype(last_tag)::value;
@@ -325,12 +270,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
         const int sg = m >> 2, w = m & 3, q = 2 * sg + (w >> 1), t0 = 2 * (w & 1), j0 = 4 * q + t0;
         const float v0 = fmaxf((c_hi[j0] + c_lo[j0]) + bq[q][t0], 0.f);
         const float v1 = fmaxf((c_hi[j0 + 1] + c_lo[j0 + 1]) + bq[q][t0 + 1], 0.f);
-        if (PCT_FFN_KO & 2) {
-          hpw[sg][0][w] = __float_as_uint(c_hi[j0]);
-          hpw[sg][1][w] = __float_as_uint(c_lo[j0]);
-          hpw[sg][2][w] = __float_as_uint(c_hi[j0 + 1]) ^ __float_as_uint(c_lo[j0 + 1]);
-        } else
-          ff_split(v0, v1, hpw[sg][0][w], hpw[sg][1][w], hpw[sg][2][w]);
+        ff_split(v0, v1, hpw[sg][0][w], hpw[sg][1][w], hpw[sg][2][w]);
       };
       auto h_frag = [&](const int sg, const int p) {
         return __builtin_bit_cast(ff_bf16x8, ff_i32x4{(int)hpw[sg][p][0], (int)hpw[sg][p][1], (int)hpw[sg][p][2], (int)hpw[sg][p][3]});
@@ -349,19 +289,17 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
         t_store(s + 2, nst);
         if (s <= 5) t_load(s + 8, nxt);
         if constexpr (!LAST) {                                    // reads first; vector instructions, the load and the store between MFMAs
-          if (!PCT_FFN_SPREAD) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             if (s & 1) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-            if (PCT_FFN_SPREAD && !(i & 1)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            if (!(i & 1)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // fragment reads spread between the MFMAs
             if (i == 1 && s <= 5) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             if (i == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      FF_STAMP(3);
       __builtin_amdgcn_sched_barrier(0);
       // ---- phase B: GEMM 2: D2[col 32 cb + 8 q + 4 h + t][row r] += W2 . h over this chunk's 32 hidden units; group g = (s, cb),
       // the next group's fragments requested before this group's MFMAs.  Image chunk + 1 is complete behind group 3 and the last two
@@ -399,31 +337,24 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
         y_lo[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, h_frag(sg, 1), y_lo[cb], 0, 0, 0);
         y_lo[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, h_frag(sg, 1), y_lo[cb], 0, 0, 0);
         y_lo[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, h_frag(sg, 0), y_lo[cb], 0, 0, 0);
-        if (g < 5 && !PCT_FFN_SPREAD) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-        if (g == 5 && !PCT_FFN_SPREAD) __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-        if (g == 6 && !LAST && !PCT_FFN_SPREAD) __builtin_amdgcn_sched_group_barrier(0x100, 7, 0);
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           if (g < 4) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-          if (PCT_FFN_SPREAD) {                                   // fragment reads one (two, group 5 and 6) per MFMA, not in a burst
-            if (g < 5 && !(i & 1)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if (g == 5) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if (g == 6 && !LAST) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if (g == 6 && !LAST && i == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
+          // fragment reads one (two, group 5 and 6) per MFMA, not in a burst
+          if (g < 5 && !(i & 1)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          if (g == 5) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          if (g == 6 && !LAST) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          if (g == 6 && !LAST && i == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           if (i == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
           if (i == 3 && (g < 4 || g >= 6)) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (g == 5 && !(PCT_FFN_KO & 4)) {
-          FF_STAMP(4);
+        if (g == 5) {
           asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
           __builtin_amdgcn_sched_barrier(0);
-          FF_STAMP(5);
         }
       }
-      FF_STAMP(6);
       cur ^= 1;
     };
     for (int chunk = 0; chunk + 1 < nch; ++chunk) chunk_body(std::false_type{}, chunk);
@@ -438,8 +369,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c0 = 32 * cb + 8 * q + 4 * h;
-        const ff_f32x4 res = (PCT_FFN_KO & 8) ? ff_f32x4{0.f, 0.f, 0.f, 0.f}
-                                              : __builtin_bit_cast(ff_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)((r * ldx + c0) * 4), 0, 0));
+        const ff_f32x4 res = __builtin_bit_cast(ff_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)((r * ldx + c0) * 4), 0, 0));
         const ff_f32x4 bb = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + c0 * 4);
 #pragma unroll
         for (int t = 0; t < 4; ++t) v[16 * cb + 4 * q + t] = ((y_hi[cb][4 * q + t] + y_lo[cb][4 * q + t]) + bb[t]) + res[t];
@@ -467,22 +397,11 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
         ff_f32x4 o;
 #pragma unroll
         for (int t = 0; t < 4; ++t) o[t] = v[16 * cb + 4 * q + t] * rstd * gq[t] + eq[t];
-        if (PCT_FFN_KO & 64)
-          asm volatile("" ::"v"(o));
-        else
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ff_i32x4, o), yr, (int)((r * ldy + c0) * 4), 0, PCT_FFN_STORE_NT ? 2 : 0);
+        // (y rows with the non-temporal hint: 6.79 -> 6.97 ms)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ff_i32x4, o), yr, (int)((r * ldy + c0) * 4), 0, 0);
       }
-    FF_STAMP(7);
   }
-#if PCT_FFN_STAMPS
-  if (tid == 0 && blockIdx.x < 256)
-    for (int i = 0; i < 8; ++i) ffn_stamps[blockIdx.x * 8 + i] = acc_t[i];
-#endif
 }
-
-#define PCT_FF_STR2(x) #x
-#define PCT_FF_STR(x) PCT_FF_STR2(x)
-const char *ffn_fused_build_flags() { return "ffn: KO=" PCT_FF_STR(PCT_FFN_KO) " STAMPS=" PCT_FF_STR(PCT_FFN_STAMPS) " SPREAD=" PCT_FF_STR(PCT_FFN_SPREAD); }
 
 // the kernel's LDS attribute for the current device, outside any stream capture (pct_prepare_device)
 int prepare_ffn_device() { return func_attr_per_device(reinterpret_cast<const void *>(&ffn_fused_split_kernel), FF_LDS) == hipSuccess ? 0 : -4; }
@@ -506,12 +425,5 @@ int launch_ffn_fused_split(const float *x, long long ldx, const float *w1, const
                      static_cast<const unsigned short *>(img_ws), F, b2, gamma, beta, eps, rows, out, ldo);
   return (int)hipGetLastError();
 }
-
-#if PCT_FFN_STAMPS
-extern "C" __attribute__((visibility("default"))) int pct_ffn_stamps_read(unsigned long long *host_out)
-{
-  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(ffn_stamps), sizeof(unsigned long long) * 256 * 8);
-}
-#endif
 
 }  // namespace pct

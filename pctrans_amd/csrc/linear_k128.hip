@@ -241,8 +241,7 @@ int launch_linear_k128(const float *x, long long ldx, const float *x2, long long
     if (rc != -100) return rc;                                     // -100: operands not 16-byte aligned for its epilogue
   }
   const long long ntiles = (rows + 31) / 32;
-  static const int wgs = [] { const char *e = getenv("PCT_LIN_WGS"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
-  const long long cap = 256LL * wgs;                               // persistent: `wgs` workgroups per CU (LDS allows 4)
+  const long long cap = 256LL * 3;                                 // persistent: 3 workgroups per CU (LDS allows 4)
   const unsigned gx = (unsigned)(ntiles < cap ? ntiles : cap);
   const dim3 grid(gx, (unsigned)((n + 127) / 128)), block(LIN_BLOCK);
 #define PCT_LIN(EPI_, X2_)                                                                                          \

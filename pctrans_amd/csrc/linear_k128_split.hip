@@ -25,23 +25,13 @@
 // sum is 15 in-lane adds + one cross-half exchange + one LDS hop across the 4 waves.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
-#ifndef PCT_LIN_PRIO
-#define PCT_LIN_PRIO 0
-#endif
-#ifndef PCT_LIN_INTERLEAVE
-#define PCT_LIN_INTERLEAVE 1        /* 16 x 16 form: the next tile's split / LDS stores between the MFMAs (linear1 4.17 -> 3.95 ms, same-box A/B) */
-#endif
 // output rows carry the non-temporal hint (aux bit 1 of the buffer store): written once, read by the NEXT kernel, far larger
 // than the L2 -- merged projections 1.127 -> 1.102 ms at 1.39 M rows, three same-box alternations
 constexpr int SPL_STORE_NT = 2;
-#ifndef PCT_LIN_IL_DELAY
-#define PCT_LIN_IL_DELAY 1          /* merged projections 1.117 -> 1.102 ms (same-box A/B) */
-#endif
-#ifndef PCT_LIN_STAGGER
-#define PCT_LIN_STAGGER 0
-#endif
+// 16 x 16 form with a second operand x2: the first quarters of the next tile's split wait this many MFMA steps for x2
+// (merged projections 1.117 -> 1.102 ms against no delay, same-box A/B)
+constexpr int SPL_IL_DELAY = 1;
 
 namespace pct {
 
@@ -108,13 +98,10 @@ struct SplSegs {
 // M16: the tile's products on v_mfma_f32_16x16x32_bf16 (four 16 x 16 sub-tiles, K = 32 per instruction) instead of
 // v_mfma_f32_32x32x16_bf16 -- the same flops per clock and the same fragments' worth of registers, but on a chip that holds
 // its clock down under matrix load the 16 x 16 shape is granted a higher clock (MI355X_MICROARCH.md, DVFS item 7: 1.12-1.15x
-// in bare loops on random data).  Bias / ReLU epilogues only.
-#ifndef PCT_LIN_M16
-#define PCT_LIN_M16 1
-#endif
+// in bare loops on random data).  Taken by the bias / ReLU epilogues.
 typedef float spl_f32x4acc __attribute__((ext_vector_type(4)));
 
-template <int EPI, bool HAS_X2, bool M16 = false>
+template <int EPI, bool HAS_X2>
 __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
     const float *__restrict__ X, const long long ldx, const float *__restrict__ X2, const long long ldx2,
     const int x2_period, const SplSegs segs, const long long M, const float *__restrict__ R, const long long ldr,
@@ -126,16 +113,7 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // provably wave-uniform (descriptor selects below)
-#if PCT_LIN_STAGGER
-  // Two workgroups share a CU (and every SIMD's matrix pipe).  Left alone they fall into lockstep -- both in their MFMA block at
-  // half rate each, then both splitting / staging with the matrix pipe idle.  A STATIC priority for the second half of the grid
-  // (the workgroups dispatched onto already occupied CUs) lets that workgroup's MFMAs go first whenever both want the pipe, so the
-  // pair settles into opposite phases: one multiplies while the other stages.
-#ifndef PCT_LIN_STAGGER_BY
-#define PCT_LIN_STAGGER_BY 0                                       /* 0: second half of the grid; 1: every second workgroup of an XCD */
-#endif
-  if (PCT_LIN_STAGGER_BY == 0 ? blockIdx.x >= (gridDim.x >> 1) : ((blockIdx.x >> 3) & 1)) __builtin_amdgcn_s_setprio(PCT_LIN_STAGGER);
-#endif
+  constexpr bool M16 = EPI != SPL_EPI_RES_LN;
 
   const int r = lane & 31, h = lane >> 5;
   // 1-D grid of nslots x nslices workgroups (nslots a multiple of 8).  Hardware deals workgroup g to XCD g % 8: the
@@ -287,7 +265,6 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
     __builtin_amdgcn_sched_barrier(0);                            // keep the fetches ahead of the MFMAs
 
     if constexpr (M16) {
-      static_assert(EPI != SPL_EPI_RES_LN || !M16, "16 x 16 form: bias / ReLU epilogues only");
       // sub-tile (cw, rx): output columns cbase + 16 cw .., x rows 16 rx ..; acc[t] = y[row 16 rx + lane % 16][col cbase + 16 cw + 4 (lane / 16) + t]
       spl_f32x4acc ahi[2][2], alo[2][2];
 #pragma unroll
@@ -321,14 +298,13 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
             }
           }
           __builtin_amdgcn_sched_barrier(0);
-#if PCT_LIN_INTERLEAVE
           // the NEXT tile's x, quarter sk: split into bf16 planes and stored into the other LDS image BETWEEN this step's MFMAs
           // (an MFMA holds the SIMD's vector issue for 8 of its 16 cycles: one vector instruction per MFMA rides along) instead
-          // of in a block of ~100 vector instructions behind the last MFMA with the matrix pipe idle
+          // of in a block of ~100 vector instructions behind the last MFMA with the matrix pipe idle (linear1 4.17 -> 3.95 ms,
+          // same-box A/B)
           // (with a second operand x2 -- fetched for the next tile at the top of THIS tile, from L2 -- the first quarters wait
-          // PCT_LIN_IL_DELAY steps for it and the last ones follow the loop)
-          if (sk >= (HAS_X2 ? PCT_LIN_IL_DELAY : 0)) stash_q(abuf[buf ^ 1], sk - (HAS_X2 ? PCT_LIN_IL_DELAY : 0), gn, g2);
-#endif
+          // SPL_IL_DELAY steps for it and the last ones follow the loop)
+          if (sk >= (HAS_X2 ? SPL_IL_DELAY : 0)) stash_q(abuf[buf ^ 1], sk - (HAS_X2 ? SPL_IL_DELAY : 0), gn, g2);
 #pragma unroll
           for (int cw = 0; cw < 2; ++cw) {
             const spl_bf16x8 b1 = __builtin_bit_cast(spl_bf16x8, w1[4 * cw + sk]);
@@ -344,21 +320,15 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
               alo[cw][rx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, x1[rx], alo[cw][rx], 0, 0, 0);
             }
           }
-#if PCT_LIN_INTERLEAVE
 #pragma unroll
           for (int i = 0; i < 24; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
             __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);      // one vector instruction
           }
-#endif
         }
       }
-#if !PCT_LIN_INTERLEAVE
-      stash(abuf[buf ^ 1], gn, g2);
-#else
 #pragma unroll
-      for (int q = 4 - (HAS_X2 ? PCT_LIN_IL_DELAY : 0); q < 4; ++q) stash_q(abuf[buf ^ 1], q, gn, g2);
-#endif
+      for (int q = 4 - (HAS_X2 ? SPL_IL_DELAY : 0); q < 4; ++q) stash_q(abuf[buf ^ 1], q, gn, g2);
       {
         const auto ry = tile_rsrc(Y, ldy, active ? tile : ntiles);
         float *sw = oscr[wave];
@@ -391,9 +361,6 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
       spl_bf16x8 n1 = *reinterpret_cast<const spl_bf16x8 *>(ap);
       spl_bf16x8 n2 = *reinterpret_cast<const spl_bf16x8 *>(ap + SPL_PLANE);
       spl_bf16x8 n3 = *reinterpret_cast<const spl_bf16x8 *>(ap + 2 * SPL_PLANE);
-#if PCT_LIN_PRIO
-      __builtin_amdgcn_s_setprio(PCT_LIN_PRIO);                   // (the wave feeding the matrix pipe before its SIMD-mate's split / epilogue)
-#endif
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const spl_bf16x8 a1 = n1, a2 = n2, a3 = n3;
@@ -414,9 +381,6 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
         acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a1, acc_lo, 0, 0, 0);
       }
     }
-#if PCT_LIN_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     stash(abuf[buf ^ 1], gn, g2);
 
     {
@@ -500,24 +464,16 @@ static int spl_launch(const float *x, long long ldx, const float *x2, long long 
                       float eps, hipStream_t stream)
 {
   const long long ntiles = (rows + 31) / 32;
-  static const int wgs = [] { const char *e = getenv("PCT_LIN_WGS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 2 ? 2 : v); }();
   int nslices = 0;
   for (int g = 0; g < segs.nseg; ++g) nslices += (segs.n[g] + 127) / 128;
   // persistent: 2 workgroups per CU (VGPRs) when one slice covers n, else tile slots x slices (see the kernel)
-  long long nslots = 256LL * wgs / (nslices < 8 ? nslices : 8) / 8 * 8;      // all resident at once
+  long long nslots = 256LL * 2 / (nslices < 8 ? nslices : 8) / 8 * 8;        // all resident at once
   if (nslots > (ntiles + 7) / 8 * 8) nslots = (ntiles + 7) / 8 * 8;
   if (nslots < 8) nslots = 8;
   const dim3 grid((unsigned)(nslots * nslices)), block(SPL_BLOCK);
-  static const bool m16 = [] { const char *e = getenv("PCT_LIN_M16"); return e ? e[0] != '0' : (PCT_LIN_M16 != 0); }();
 #define PCT_SPL(EPI_, X2_)                                                                                           \
-  do {                                                                                                               \
-    if (m16 && EPI_ != SPL_EPI_RES_LN)                                                                               \
-      hipLaunchKernelGGL((linear_k128_split_kernel<EPI_, X2_, EPI_ != SPL_EPI_RES_LN>), grid, block, 0, stream, x, ldx, x2, ldx2, \
-                         (int)x2_period, segs, rows, residual, ldr, gamma, beta, eps);                               \
-    else                                                                                                             \
-      hipLaunchKernelGGL((linear_k128_split_kernel<EPI_, X2_, false>), grid, block, 0, stream, x, ldx, x2, ldx2,      \
-                         (int)x2_period, segs, rows, residual, ldr, gamma, beta, eps);                               \
-  } while (0)
+  hipLaunchKernelGGL((linear_k128_split_kernel<EPI_, X2_>), grid, block, 0, stream, x, ldx, x2, ldx2, (int)x2_period,   \
+                     segs, rows, residual, ldr, gamma, beta, eps)
   if (x2) {
     if (epi == SPL_EPI_BIAS) PCT_SPL(SPL_EPI_BIAS, true);
     else if (epi == SPL_EPI_BIAS_RELU) PCT_SPL(SPL_EPI_BIAS_RELU, true);

@@ -19,19 +19,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef PCT_LIN_PRIO
-#define PCT_LIN_PRIO 0
-#endif
-#ifndef PCT_LIN_STAGGER
-#define PCT_LIN_STAGGER 1          /* static priority for the second half of the grid: 4.605 -> 4.53 ms at 2.8 M rows (same-box A/B) */
-#endif
-#ifndef PCT_LLS_KO_ALIAS
-#define PCT_LLS_KO_ALIAS 0    /* knock-out (WRONG RESULTS, timing only): x and residual rows of every tile read from the first tiles (L2-resident) */
-#endif
-#if PCT_LLS_KO_ALIAS && !defined(PCT_EXPERIMENT_BUILD)
-#error "PCT_LLS_KO_ALIAS gives wrong results: add -DPCT_EXPERIMENT_BUILD"
-#endif
-
 namespace pct {
 
 typedef float lls_f32x16 __attribute__((ext_vector_type(16)));
@@ -84,16 +71,11 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
-#if PCT_LIN_STAGGER
   // Two workgroups share a CU (and every SIMD's matrix pipe).  Left alone they fall into lockstep -- both in their MFMA block at
   // half rate each, then both splitting / staging with the matrix pipe idle.  A STATIC priority for the second half of the grid
   // (the workgroups dispatched onto already occupied CUs) lets that workgroup's MFMAs go first whenever both want the pipe, so the
-  // pair settles into opposite phases: one multiplies while the other stages.
-#ifndef PCT_LIN_STAGGER_BY
-#define PCT_LIN_STAGGER_BY 0                                       /* 0: second half of the grid; 1: every second workgroup of an XCD */
-#endif
-  if (PCT_LIN_STAGGER_BY == 0 ? blockIdx.x >= (gridDim.x >> 1) : ((blockIdx.x >> 3) & 1)) __builtin_amdgcn_s_setprio(PCT_LIN_STAGGER);
-#endif
+  // pair settles into opposite phases: one multiplies while the other stages (4.605 -> 4.53 ms at 2.8 M rows, same-box A/B).
+  if (blockIdx.x >= (gridDim.x >> 1)) __builtin_amdgcn_s_setprio(1);
                   // row half / column half of the 128 x 128 tile
   const int r = lane & 31, h = lane >> 5;
 
@@ -125,7 +107,7 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
 
   lls_i32x4 gx[4], gw[6];
   auto fetch = [&](const long long tile, const int step) {
-    const auto rs = tile_rsrc(X, ldx, PCT_LLS_KO_ALIAS ? tile % 64 : tile);
+    const auto rs = tile_rsrc(X, ldx, tile);
 #pragma unroll
     for (int q = 0; q < 4; ++q) gx[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, xg_voff, step * (LLS_BK * 4) + 16 * q, 0);
 #pragma unroll
@@ -175,9 +157,6 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
       const bool last = step + 1 == ksteps;
       fetch(last ? tile + gridDim.x : tile, last ? 0 : step + 1);
       __builtin_amdgcn_sched_barrier(0);
-#if PCT_LIN_PRIO
-      __builtin_amdgcn_s_setprio(PCT_LIN_PRIO);
-#endif
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         lls_bf16x8 a[2][3], w[2][3];
@@ -202,9 +181,6 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
       }
     }
 
-#if PCT_LIN_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
     // ---- epilogue: acc[rb][cb][4q + i] = y[row 64 wr + 32 rb + r][column 64 wc + 32 cb + 8q + 4h + i] ----------------
     const auto rr = tile_rsrc(R, ldr, tile);
     const auto ry = tile_rsrc(Y, ldy, tile);

@@ -43,28 +43,6 @@
 
 namespace pct {
 
-#ifndef PCT_BCOL_KO
-#define PCT_BCOL_KO 0         /* knock-outs (WRONG RESULTS, timing only): 1 = no scatter adds, 2 = no dots reads, 4 = no flush atomics,
-                                 16 = no dots pass, 32 = no scatter pass, 64 = no count adds, 128 = no zeroing */
-#endif
-
-#ifndef PCT_BCOL_PRIO
-#define PCT_BCOL_PRIO 0         /* wave priorities (s_setprio): 1 = dots 3 / scatter 2 / rest 0, 2 = dots 2 / scatter 3, 3 = flush raised too */
-#endif
-
-#ifndef PCT_BCOL_STAMP
-#define PCT_BCOL_STAMP 0        /* diagnostic build: per-part cycle sums of wave 0 (s_memtime), tools/stamp_msda_bwd.py */
-#endif
-#if PCT_BCOL_KO && !defined(PCT_EXPERIMENT_BUILD)
-#error "PCT_BCOL_KO knock-outs give wrong results: add -DPCT_EXPERIMENT_BUILD to build one"
-#endif
-#define PCT_BSTR2(x) #x
-#define PCT_BSTR(x) PCT_BSTR2(x)
-const char *msda_backward_col_build_flags()
-{
-  return "bcol: KO=" PCT_BSTR(PCT_BCOL_KO) " PRIO=" PCT_BSTR(PCT_BCOL_PRIO) " STAMP=" PCT_BSTR(PCT_BCOL_STAMP);
-}
-
 constexpr int BCOL_BLOCK = 256;
 constexpr int BCOL_GPX = 1092;                                  // pixels per pool (= 4 mod 32: the 8 planes of one pixel start 8 banks apart)
 constexpr int BCOL_CNT_BYTES = BCOL_GPX * 4;                    // contribution counts, one dword per pixel
@@ -88,21 +66,8 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
     const float *__restrict__ grad_out, const float *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ starts, const float *__restrict__ loc, const float *__restrict__ attn, const int N,
     const int S, const int M, float *__restrict__ grad_value, float *__restrict__ grad_loc,
-    float *__restrict__ grad_attn, unsigned *__restrict__ queue, unsigned char *__restrict__ flags, const int flag_cap,
-    unsigned long long *__restrict__ stamps)
+    float *__restrict__ grad_attn, unsigned *__restrict__ queue, unsigned char *__restrict__ flags, const int flag_cap)
 {
-  unsigned long long t_prev = 0, t_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  auto stamp = [&](int part) {
-    if constexpr (PCT_BCOL_STAMP && !DIRECT) {
-      __builtin_amdgcn_sched_barrier(0);
-      unsigned long long t;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-      __builtin_amdgcn_sched_barrier(0);
-      if (part >= 0) t_sum[part] += t - t_prev;
-      t_prev = t;
-    }
-  };
-
   constexpr int P = 4, D = 16, PXB = 64, BLOCK = BCOL_BLOCK, NW = BLOCK / 64;
   static_assert(L >= 1 && L <= 5, "unsupported geometry");
   typedef unsigned col_u32x4 __attribute__((ext_vector_type(4)));
@@ -522,7 +487,6 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
     issue_loc(b, m, qv, raw);
   }
 
-  stamp(-1);
   while (have) {
     asm volatile("" : "+v"(tid), "+v"(qi), "+v"(lane_slot), "+v"(lane_c0));
     unsigned rfetch = 0u;
@@ -556,9 +520,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
       }
       next_idx[0] = fetched;
     }
-    stamp(0);
     __syncthreads();                                                          // (A) boxes visible; pool free (previous flush read)
-    stamp(1);
     int item_n, b_n = 0, m_n = 0, qv_n = 0;
     {
       const unsigned nxt = __builtin_amdgcn_readfirstlane(next_idx[0]);
@@ -666,10 +628,8 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
         mx[wave * 2 + 1] = amax;
       }
     }
-    stamp(2);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();                                                          // (B1) phase 0 staged; bounds visible
-    stamp(3);
     bool fixed_ok;
     float scale, inv_scale;
     {
@@ -717,13 +677,8 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const unsigned char *pa = pool + (a + (r ? rowb : 0u) + rot[j]);
-              if (PCT_BCOL_KO & 2) {
-                va[j] = col_f32x4{(float)a, 1.f, 2.f, 3.f};
-                vb[j] = va[j];
-              } else {
-                va[j] = *reinterpret_cast<const col_f32x4 *>(pa);
-                vb[j] = *reinterpret_cast<const col_f32x4 *>(pa + PXB);
-              }
+              va[j] = *reinterpret_cast<const col_f32x4 *>(pa);
+              vb[j] = *reinterpret_cast<const col_f32x4 *>(pa + PXB);
             }
             col_f32x2 sa = {0.f, 0.f}, sb = {0.f, 0.f};
 #pragma unroll
@@ -773,7 +728,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
           const col_f32x2 t2 = col_f32x2{1.f - lw, lw} * col_f32x2{as, as};
           const col_f32x2 g12 = t2 * col_f32x2{1.f - lh, 1.f - lh}, g34 = t2 * col_f32x2{lh, lh};
           const unsigned pidx = (unsigned)(__mul24(y0, wwid[l]) + x0 + woff[l]);
-          if (!(PCT_BCOL_KO & (1 | 64))) {
+          {
             lds_u32 *cp = (lds_u32 *)(pool + pidx * 4u);
             lds_u32 *cq = (lds_u32 *)(pool + (pidx + (unsigned)wwid[l]) * 4u);
             __hip_atomic_fetch_add(cp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -790,13 +745,9 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
             for (int t = 0; t < 8; ++t) {
               const col_f32x2 xa = __builtin_elementwise_fma(wa, gor[t], magic2);
               const col_f32x2 xb = __builtin_elementwise_fma(wb, gor[t], magic2);
-              if (!(PCT_BCOL_KO & 1)) {
-                lds_u64 *q = (lds_u64 *)(pool + (pr + poff[t]));
-                __hip_atomic_fetch_add(q, __builtin_bit_cast(unsigned long long, xa), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(q + 1, __builtin_bit_cast(unsigned long long, xb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              } else {
-                asm volatile("" ::"v"(xa), "v"(xb));
-              }
+              lds_u64 *q = (lds_u64 *)(pool + (pr + poff[t]));
+              __hip_atomic_fetch_add(q, __builtin_bit_cast(unsigned long long, xa), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              __hip_atomic_fetch_add(q + 1, __builtin_bit_cast(unsigned long long, xb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               // (without the fence the compiler forms the 64 packed products of a sample -- of several samples -- first
               // and spills them on the way to the adds)
               if (t & 1) __builtin_amdgcn_sched_barrier(0);
@@ -848,9 +799,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
               const unsigned long long U = (unsigned long long)n[u] * K + (unsigned long long)(long long)lo;
               const int hi = (int)((unsigned)(T[u] >> 32) - (unsigned)(U >> 32) - nK);
               const int mine = (ch & 1) ? hi : lo;
-              if (!(PCT_BCOL_KO & 4)) {
-                if (mine != 0) unsafeAtomicAdd(grow + (long long)xs[u] * MD, (float)mine * inv_scale);
-              }
+              if (mine != 0) unsafeAtomicAdd(grow + (long long)xs[u] * MD, (float)mine * inv_scale);
             }
           }
         }
@@ -863,21 +812,17 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
         stage_phase(ph);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        stamp(9);
       }
       if (fixed_ok) {
-        if (PCT_BCOL_PRIO) __builtin_amdgcn_s_setprio(PCT_BCOL_PRIO == 2 ? 2 : 3);
         [&]<int... Ls>(std::integer_sequence<int, Ls...>) {
-          ([&] { if (!(PCT_BCOL_KO & 16) && phase_of[Ls] == ph) dots_lds(std::integral_constant<int, Ls>{}); }(), ...);
+          ([&] { if (phase_of[Ls] == ph) dots_lds(std::integral_constant<int, Ls>{}); }(), ...);
         }(std::make_integer_sequence<int, L>{});
-        if (PCT_BCOL_PRIO) __builtin_amdgcn_s_setprio(0);
-        stamp(4);
         __syncthreads();                                                      // (B2) every wave is done with the values
         if (ph == nph - 1 && have_n) issue_loc(b_n, m_n, qv_n, raw);           // in flight until the next iteration
         int used = 0;
 #pragma unroll
         for (int l = 0; l < L; ++l) used += phase_of[l] == ph ? wsize[l] : 0;
-        if (!(PCT_BCOL_KO & 128)) {
+        {
           const col_f32x4 z = {0.f, 0.f, 0.f, 0.f};
           for (int i = tid; i * 4 < used; i += BLOCK) *reinterpret_cast<col_f32x4 *>(pool + (size_t)i * 16) = z;   // counts
 #pragma unroll
@@ -902,20 +847,13 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
           for (int u = 0; u < 8; ++u) gor[u] = (d & 4u) ? a[(u + 4) & 7] : a[u];
         }
         auto scatter_lds = [&](auto lc) { scatter_impl(lc, gor); };
-        if (PCT_BCOL_PRIO) __builtin_amdgcn_s_setprio(PCT_BCOL_PRIO == 2 ? 3 : 2);
-        stamp(5);
         [&]<int... Ls>(std::integer_sequence<int, Ls...>) {
-          ([&] { if (!(PCT_BCOL_KO & 32) && phase_of[Ls] == ph) scatter_lds(std::integral_constant<int, Ls>{}); }(), ...);
+          ([&] { if (phase_of[Ls] == ph) scatter_lds(std::integral_constant<int, Ls>{}); }(), ...);
         }(std::make_integer_sequence<int, L>{});
-        if (PCT_BCOL_PRIO) __builtin_amdgcn_s_setprio(PCT_BCOL_PRIO == 3 ? 1 : 0);
-        stamp(6);
         __syncthreads();                                                      // (B4) every add of this phase is in the pool
-        stamp(7);
 #pragma unroll
         for (int l = 0; l < L; ++l)
           if (phase_of[l] == ph) flush_window(l);
-        if (PCT_BCOL_PRIO == 3) __builtin_amdgcn_s_setprio(0);
-        stamp(8);
       }
     }
     if ((nph == 0 || !fixed_ok) && have_n) issue_loc(b_n, m_n, qv_n, raw);
@@ -933,11 +871,6 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
     b = b_n;
     m = m_n;
     qv = qv_n;
-    stamp(10);
-  }
-  if constexpr (PCT_BCOL_STAMP && !DIRECT) {
-    if (tid == 0 && stamps)
-      for (int i = 0; i < 16; ++i) stamps[(size_t)blockIdx.x * 16 + i] = t_sum[i];
   }
 }
 
@@ -1049,8 +982,6 @@ int prepare_msda_backward_col_device()
   return bcol_flag_buffer(nullptr, &slot, true) ? 0 : (int)hipErrorOutOfMemory;
 }
 
-unsigned long long *win_stamp_buffer();                                      // msda_forward_win.hip (diagnostic)
-
 // returns -100 when this geometry is not covered (caller uses another kernel)
 int launch_msda_backward_col(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
                              const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
@@ -1084,9 +1015,9 @@ int launch_msda_backward_col(const float *value, const int64_t *shapes, const in
     if (attr_rc != hipSuccess) return (int)attr_rc;                                                                        \
     if (attr_rc2 != hipSuccess) return (int)attr_rc2;                                                                      \
     hipLaunchKernelGGL((msda_backward_col_kernel<L_, false>), grid, block, lds, stream, grad_out, value, shapes, starts,   \
-                       loc, attn, N, S, M, grad_value, grad_loc, grad_attn, queue, flags, flag_cap, PCT_BCOL_STAMP ? win_stamp_buffer() : nullptr);                                 \
+                       loc, attn, N, S, M, grad_value, grad_loc, grad_attn, queue, flags, flag_cap);                          \
     hipLaunchKernelGGL((msda_backward_col_kernel<L_, true>), grid, block, lds_direct, stream, grad_out, value, shapes,     \
-                       starts, loc, attn, N, S, M, grad_value, grad_loc, grad_attn, nullptr, flags, flag_cap, nullptr);                       \
+                       starts, loc, attn, N, S, M, grad_value, grad_loc, grad_attn, nullptr, flags, flag_cap);               \
   } while (0)
   if (L == 3) PCT_BCOL(3);
   else if (L == 4) PCT_BCOL(4);

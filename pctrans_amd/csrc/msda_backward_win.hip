@@ -25,7 +25,6 @@
 //
 // fp32, D == 16, P == 4 (the shapes PCTrans runs); anything else goes to msda_backward.hip.
 #include <math.h>
-#include <stdlib.h>
 
 #include <utility>
 
@@ -33,17 +32,17 @@
 
 namespace pct {
 
-// pixels per pool: NS = 1 -> 3 workgroups per CU (3 x 53.8 KB), NS = 2 -> 2 per CU (2 x 74.2 KB)
-__host__ __device__ constexpr int bwd_win_pool_px(int ns) { return ns == 1 ? 418 : 578; }
+// NS = 2 query slots per lane, 578 pixels per pool: 2 workgroups per CU (2 x 74.2 KB)
+constexpr int BWD_WIN_NS = 2, BWD_WIN_POOL_PX = 578;
 
-template <int L, int NS>
+template <int L>
 __global__ __launch_bounds__(WIN_BLOCK, 2) void msda_backward_win_kernel(
     const float *__restrict__ grad_out, const float *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ starts, const float *__restrict__ loc, const float *__restrict__ attn, const int N,
     const int S, const int M, const int Lq, const int pyramid, float *__restrict__ grad_value,
     float *__restrict__ grad_loc, float *__restrict__ grad_attn, unsigned *__restrict__ queue)
 {
-  constexpr int D = 16, P = 4, VEC = 4, QL = 4;
+  constexpr int D = 16, P = 4, VEC = 4, QL = 4, NS = BWD_WIN_NS;
   constexpr int TQ = WIN_BLOCK / QL;              // queries per slot (64)
   constexpr int TW = TQ / WIN_TH;                 // 8 pixels wide
   constexpr int SH = TQ / TW;                     // 8 rows per slot
@@ -52,7 +51,7 @@ __global__ __launch_bounds__(WIN_BLOCK, 2) void msda_backward_win_kernel(
   // Window capacity in pixels.  The grad windows are channel-planar: plane ch holds GPX floats, so that the lanes of
   // one ds_add_u32 (32-lane groups = 8 queries x 4 channel quarters, banks = dword mod 32) fall on 8*c + pixel, and
   // the lanes of the flush's ds_read_b32 (2 pixels x 16 channels) on 2*ch + pixel: GPX = 2 (mod 32).
-  constexpr int GPX = bwd_win_pool_px(NS);
+  constexpr int GPX = BWD_WIN_POOL_PX;
   constexpr int pool_px = GPX;
   static_assert(GPX % 32 == 2, "plane stride must keep the LDS atomics conflict-free");
   static_assert(L <= WIN_MAXL, "too many levels");
@@ -282,13 +281,7 @@ __global__ __launch_bounds__(WIN_BLOCK, 2) void msda_backward_win_kernel(
         const bool inside = y >= 0 && y < H && x >= 0 && x < W;
         const int gi = srcw[ch * GPX + px];
         const float g = (float)gi * inv_scale;
-#if defined(PCT_BWD_KO_FLUSH)      // timing experiments only (wrong results)
-        if (inside && gi == 0x12345678) unsafeAtomicAdd(glev + (long long)(y * W + x) * MD + ch, g);
-#elif defined(PCT_BWD_PLAIN_FLUSH)
-        if (inside && gi != 0) glev[(long long)(y * W + x) * MD + ch] = g;
-#else
         if (inside && gi != 0) unsafeAtomicAdd(glev + (long long)(y * W + x) * MD + ch, g);
-#endif
       }
     };
 #pragma unroll
@@ -428,9 +421,6 @@ __global__ __launch_bounds__(WIN_BLOCK, 2) void msda_backward_win_kernel(
             constexpr int MAGIC_BITS = 0x4B400000;
             // (element reads go through scalars: __builtin_bit_cast on an ext-vector element reads element 0)
             auto fx = [](float f) { return __float_as_int(f) - MAGIC_BITS; };
-#if defined(PCT_BWD_KO_LDSADD)
-            if (a1 == 0x7fffffff)
-#endif
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
               const float p0 = add1[e].x, p1 = add1[e].y, q0 = add2[e].x, q1 = add2[e].y;
@@ -562,25 +552,19 @@ int launch_msda_backward_win(const float *value, const int64_t *shapes, const in
   if ((long long)N * Lq * M < 32768) return -100;
   if ((long long)N * ((long long)S + 64 * L) * M >= 0x7fffffffLL) return -100;
   if ((long long)S * M * D >= 0x7fffffffLL) return -100;            // per-image element offsets are 32-bit
-  static const int ns_env = [] { const char *e = getenv("PCT_BWD_NS"); return e ? atoi(e) : 2; }();
-  const int NS = ns_env == 1 ? 1 : 2;
-  const int pool_px = bwd_win_pool_px(NS);                           // value pool + grad pool + boxes per workgroup
+  const int pool_px = BWD_WIN_POOL_PX;                               // value pool + grad pool + boxes per workgroup
   const size_t lds = 2 * (size_t)pool_px * 64 + (WIN_BLOCK / 64) * (WIN_MAXL + 1) * 2 * sizeof(unsigned) + 16;
   const int wg_fit = (int)((160 * 1024) / lds);
   const int wg_per_cu = wg_fit < 1 ? 1 : (wg_fit > 3 ? 3 : wg_fit);
   const int pyramid = Lq == S ? 1 : 0;
   const dim3 grid(256 * wg_per_cu), block(WIN_BLOCK);
   unsigned *queue = win_queue_slot(stream);                        // nullptr: static item stride
-#define PCT_BWIN(L_, NS_)                                                                                          \
-  hipLaunchKernelGGL((msda_backward_win_kernel<L_, NS_>), grid, block, lds, stream, grad_out, value, shapes, starts, \
-                     loc, attn, N, S, M, Lq, pyramid, grad_value, grad_loc, grad_attn, queue)
-#define PCT_BWIN_L(NS_)              \
-  if (L == 3) PCT_BWIN(3, NS_);      \
-  else if (L == 4) PCT_BWIN(4, NS_); \
-  else PCT_BWIN(5, NS_)
-  if (NS == 1) { PCT_BWIN_L(1); }
-  else { PCT_BWIN_L(2); }
-#undef PCT_BWIN_L
+#define PCT_BWIN(L_)                                                                                               \
+  hipLaunchKernelGGL((msda_backward_win_kernel<L_>), grid, block, lds, stream, grad_out, value, shapes, starts, loc, \
+                     attn, N, S, M, Lq, pyramid, grad_value, grad_loc, grad_attn, queue)
+  if (L == 3) PCT_BWIN(3);
+  else if (L == 4) PCT_BWIN(4);
+  else PCT_BWIN(5);
 #undef PCT_BWIN
   return (int)hipGetLastError();
 }

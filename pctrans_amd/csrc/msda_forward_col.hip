@@ -18,120 +18,20 @@
 //     (piece (j + lane/8) % 4 in instruction j): the 16 lanes the LDS serves together would otherwise meet on 4 of
 //     the 16 bank groups (pixels are 64 B apart) -- 4-way conflicts; the rotation only permutes which accumulator
 //     register holds which 4 channels, which the final store undoes with address arithmetic;
-//   * one workgroup of 1024 threads per CU with a pool of up to ~150 KB of LDS, windows = per-level bounding boxes of
-//     the column's samples (packed-u16 min/max: DPP inside a wave, one LDS hop across the 16 waves) staged by LDS-DMA
+//   * three workgroups of 256 threads per CU, each with a pool of ~50 KB of LDS, windows = per-level bounding boxes of
+//     the column's samples (packed-u16 min/max: DPP inside a wave, one LDS hop across the 4 waves) staged by LDS-DMA
 //     with a zero apron; levels that do not fit the pool together are staged and gathered in successive PHASES
 //     (accumulators stay in registers), a level whose box alone exceeds the pool is gathered from global memory
 //     through a bounds-checked buffer descriptor;
 //   * persistent grid, items handed out per XCD from self-resetting counters with the 8 heads of a column adjacent
 //     (the heads share every 128-byte line of the column's windows, two heads per line).
 #include <math.h>
-#include <stdlib.h>
 
 #include <utility>
 
 #include "msda_col_common.hpp"
 
 namespace pct {
-
-#ifndef PCT_COL_STORE_NT
-#define PCT_COL_STORE_NT 1
-#endif
-#ifndef PCT_COL_LOC_NT
-#define PCT_COL_LOC_NT 0      /* experiment: nt on the location records only (whole lines, one reader) */
-#endif
-#ifndef PCT_COL_W_NT
-#define PCT_COL_W_NT 0
-#endif
-#ifndef PCT_COL_KO_NOLOC
-#define PCT_COL_KO_NOLOC 0    /* knock-out (WRONG RESULTS, timing only): 1 = the location records are not loaded, 2 = nor the weights */
-#endif
-#ifndef PCT_COL_KO_NOSTORE
-#define PCT_COL_KO_NOSTORE 0  /* knock-out (WRONG RESULTS, timing only): no output stores */
-#endif
-#ifndef PCT_COL_W_LATE
-#define PCT_COL_W_LATE 0      /* experiment: the odd head of a pair fetches its weights later (no effect on traffic or time) */
-#endif
-#ifndef PCT_COL_ITEM_ORDER
-#define PCT_COL_ITEM_ORDER 0
-#endif
-#ifndef PCT_COL_EARLY
-#define PCT_COL_EARLY 1       /* the second phase's windows are staged into the finest level's region as soon as that level is gathered */
-#endif
-#ifndef PCT_COL_EARLY_WAIT
-#define PCT_COL_EARLY_WAIT 1  /* the early-staged second phase is waited for with a counted vmcnt (the next item's record stays in flight) */
-#endif
-#ifndef PCT_COL_PRIO
-#define PCT_COL_PRIO 8        /* wave priorities (s_setprio): 0 = none, 8 = by part of an item as set below; 1..7: A/B variants.  A wave
-                                 in its gather is served before the waves of the other workgroups that are decoding, planning or
-                                 staging -- the gather is the LDS-latency chain of an item, everything else fills its gaps --
-                                 and the first (finest, largest) level before the later ones.  Same-box A/B, P2 batch 128:
-                                 I 1.70 -> 1.65 ms, M 2.24 -> 2.16 ms; other splits (gather 3 / 3, 1 / 1, planning raised) were
-                                 within 1 % of each other on I and 2 % worse on M */
-#endif
-#ifndef PCT_COL_PRIO_TOP      /* wave priorities (s_setprio, 0..3) by part of an item, PCT_COL_PRIO == 8: records + pre-pass, */
-#define PCT_COL_PRIO_TOP 0    /* planning + staging + decode, first gathered level, other levels                             */
-#define PCT_COL_PRIO_PLAN 0
-#define PCT_COL_PRIO_L0 3
-#define PCT_COL_PRIO_REST 2
-#endif
-#ifndef PCT_COL_PRIO_FRONT
-#define PCT_COL_PRIO_FRONT 0
-#endif
-#ifndef PCT_COL_KO_NOSTAGE
-#define PCT_COL_KO_NOSTAGE 0  /* knock-out (WRONG RESULTS, timing only): no window staging (LDS-DMA) at all */
-#endif
-#ifndef PCT_COL_KO_NOGATHER
-#define PCT_COL_KO_NOGATHER 0 /* knock-out (WRONG RESULTS, timing only): 1 = no LDS reads + FMAs in the gather, 2 = no gather at all */
-#endif
-#ifndef PCT_COL_LATIN
-#define PCT_COL_LATIN 2       /* LDS gather with a per-lane corner order that is bank-conflict free for ANY locations (see
-                                 gather_level_lds_latin): 0 = off, 1 = every level, 2 = levels whose window is much larger than the
-                                 column's cell (wide offset distributions).  Same-box A/B, P2 batch 128 (profiles/
-                                 r04_forward_structural_ab.txt): 2 against 0: M 2.168 -> 2.085 ms as an op, 2.290 -> 2.209 ms in the
-                                 bench step; I 1.649 -> 1.700 (the two code paths cost the init-like case 3 spilled registers); 1: M 2.038,
-                                 I 1.779 */
-#endif
-#ifndef PCT_COL_LATIN_HALO
-#define PCT_COL_LATIN_HALO 16
-#endif
-#ifndef PCT_COL_KO_ALIAS
-#define PCT_COL_KO_ALIAS 0    /* knock-out (WRONG RESULTS, timing only): every image reads and writes image 0's tensors -- the same instruction
-                                 stream with (almost) no HBM traffic: what the kernel costs when memory bandwidth is free */
-#endif
-#ifndef PCT_COL_KO_NOCONF
-#define PCT_COL_KO_NOCONF 0   /* knock-out (WRONG RESULTS, timing only): LDS gather addresses forced conflict-free */
-#endif
-#ifndef PCT_COL_ORDER
-#define PCT_COL_ORDER 1       /* gather order of the levels: 0 = finest .. coarsest, 1 = finest, coarsest, then the rest */
-#endif
-#ifndef PCT_COL_LOC_AT
-#define PCT_COL_LOC_AT 0      /* the gather step behind which the next item's location record is fetched, all groups at once (the
-                                 two 64-byte halves of a 128-byte line back to back: -2 % on I and M against one group
-                                 per gathered level, same-box A/B) */
-#endif
-#ifndef PCT_COL_STREAM_NT
-#define PCT_COL_STREAM_NT 0   /* measured: nt on the record loads re-fetches the half lines two heads / two load groups share
-                                (I: 7.9 -> 9.7 GB read per launch, 1.95 -> 2.14 ms); kept as a build switch */
-#endif
-
-// The knock-out switches produce WRONG RESULTS by design (timing experiments, tools/variant.sh): a library built with one
-// of them must say so -- refused unless the build declares itself an experiment, and reported by pct_build_info().
-#if (PCT_COL_KO_NOLOC || PCT_COL_KO_NOSTORE || PCT_COL_KO_NOSTAGE || PCT_COL_KO_NOGATHER || PCT_COL_KO_NOCONF || PCT_COL_KO_ALIAS) && \
-    !defined(PCT_EXPERIMENT_BUILD)
-#error "PCT_COL_KO_* knock-outs give wrong results: add -DPCT_EXPERIMENT_BUILD (tools/variant.sh does) to build one"
-#endif
-#define PCT_STR2(x) #x
-#define PCT_STR(x) PCT_STR2(x)
-const char *msda_forward_col_build_flags()
-{
-  return "col: KO=" PCT_STR(PCT_COL_KO_NOLOC) PCT_STR(PCT_COL_KO_NOSTORE) PCT_STR(PCT_COL_KO_NOSTAGE) PCT_STR(PCT_COL_KO_NOGATHER)
-         PCT_STR(PCT_COL_KO_NOCONF) PCT_STR(PCT_COL_KO_ALIAS) " STORE_NT=" PCT_STR(PCT_COL_STORE_NT) " LOC_NT=" PCT_STR(PCT_COL_LOC_NT) " W_NT=" PCT_STR(PCT_COL_W_NT)
-         " STREAM_NT=" PCT_STR(PCT_COL_STREAM_NT) " W_LATE=" PCT_STR(PCT_COL_W_LATE) " ITEM_ORDER=" PCT_STR(PCT_COL_ITEM_ORDER)
-         " EARLY=" PCT_STR(PCT_COL_EARLY) " EARLY_WAIT=" PCT_STR(PCT_COL_EARLY_WAIT) " PRIO=" PCT_STR(PCT_COL_PRIO) "/" PCT_STR(PCT_COL_PRIO_TOP)
-         PCT_STR(PCT_COL_PRIO_PLAN) PCT_STR(PCT_COL_PRIO_L0) PCT_STR(PCT_COL_PRIO_REST) PCT_STR(PCT_COL_PRIO_FRONT) " ORDER=" PCT_STR(PCT_COL_ORDER)
-         " LOC_AT=" PCT_STR(PCT_COL_LOC_AT) " LATIN=" PCT_STR(PCT_COL_LATIN) "/" PCT_STR(PCT_COL_LATIN_HALO);
-}
 
 // Gather order of the levels (step ll -> level).  The finest level (the last one in PCTrans' pyramids) comes first; its
 // window is the largest, and the level that most often still fits beside it in the pool is the COARSEST one, so that
@@ -141,8 +41,12 @@ const char *msda_forward_col_build_flags()
 template <int L>
 __host__ __device__ constexpr int col_level_of_step(const int ll)
 {
-  return PCT_COL_ORDER == 0 ? L - 1 - ll : (ll == 0 ? L - 1 : (ll == 1 ? 0 : L - ll));
+  return ll == 0 ? L - 1 : (ll == 1 ? 0 : L - ll);
 }
+
+// 256 threads per workgroup, 3 workgroups per CU, a ~50 KB LDS pool each (168 registers): the memory phases of one
+// workgroup (records, staging) overlap the gather of the others.
+constexpr int COL_BLOCK = 256, COL_WG_PER_CU = 3, COL_POOL_KB = 50;
 
 // PP ("piece planes", an MI355X-native operand layout for the callers that control the producers -- the encoder's own
 // projection GEMM writes it, pct_ms_deform_attn_forward_planes_f32): value, locations / offsets and weights / logits are
@@ -151,29 +55,14 @@ __host__ __device__ constexpr int col_level_of_step(const int ll)
 // consecutive queries, i.e. whole 128-byte lines, 2 - 8 tag look-ups per instruction -- and the quad-cooperative access with
 // its register transposes (176 vector instructions per wave and item), the half lines a record shares with its sibling
 // head's and the 64-byte-in-512 pixel slices of the window staging are all gone.  Same arithmetic, bit-identical output.
-template <int L, bool FUSED, int BLOCK, bool STAMP = false, bool PP = false>
-__global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) void msda_forward_col_kernel(
+template <int L, bool FUSED, bool PP = false>
+__global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_kernel(
     const float *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ starts,
     const float *__restrict__ loc, const float *__restrict__ attn, const int N, const int S, const int M,
     const int pool_px, float *__restrict__ out, const float *__restrict__ ref, const long long ref_batch_stride,
-    unsigned *__restrict__ queue, unsigned long long *__restrict__ stamps = nullptr)
+    unsigned *__restrict__ queue)
 {
-  constexpr int P = 4, D = 16, PXB = 64, NW = BLOCK / 64;
-  // locations, weights and outputs are touched exactly once: non-temporal, so that they do not push the value lines (which
-  // neighbouring columns and the sibling head re-use) out of the XCD's L2
-  constexpr bool STREAM_NT = PCT_COL_STREAM_NT;
-  // diagnostic build only (STAMP): per-phase cycle sums of wave 0, written to a buffer nothing else reads
-  unsigned long long t_prev = 0, t_sum[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  auto stamp = [&](int phase) {
-    if constexpr (STAMP) {
-      __builtin_amdgcn_sched_barrier(0);
-      unsigned long long t;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-      __builtin_amdgcn_sched_barrier(0);
-      if (phase >= 0) t_sum[phase] += t - t_prev;
-      t_prev = t;
-    }
-  };
+  constexpr int P = 4, D = 16, PXB = 64, BLOCK = COL_BLOCK, NW = BLOCK / 64;
   static_assert(L >= 1 && L <= 5 && NW <= 16, "unsupported geometry");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -325,17 +214,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
     // L2: measured 1.41x / 1.92x the algorithmic bytes on the memory side for distributions I / M.)
     b_ = udiv_s(it, dv_ncolM);
     const int r_img = it - b_ * (ncol * M);
-    if (PCT_COL_KO_ALIAS) b_ = 0;
     int col;
-    if (PCT_COL_ITEM_ORDER == 1 && M == 8) {                                   // (experiment) column outermost, the 8 heads adjacent
-      col = r_img >> 3;
-      m_ = r_img & 7;
-    } else if (PCT_COL_ITEM_ORDER == 2 && M == 8) {                            // (experiment) two pairs, then column, then 4 heads
-      const int pg = udiv_s(r_img, make_udiv(4 * ncol));
-      const int rr = r_img - pg * 4 * ncol;
-      col = rr >> 2;
-      m_ = 4 * pg + (rr & 3);
-    } else if (r_img < 2 * ncol * (M >> 1)) {
+    if (r_img < 2 * ncol * (M >> 1)) {
       const int pr = udiv_s(r_img, dv_2ncol);
       const int rr = r_img - pr * 2 * ncol;
       col = rr >> 1;
@@ -408,24 +288,17 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
         for (int g = 0; g < NGL; ++g)
           raw[g][s4] = g * 4 + s4 < NPL
                            ? __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                 rs, (int)qo, (int)(p0 + (unsigned)(g * 4 + s4) * s16), PCT_COL_LOC_NT ? 2 : 0))
+                                 rs, (int)qo, (int)(p0 + (unsigned)(g * 4 + s4) * s16), 0))
                            : col_f32x4{0.f, 0.f, 0.f, 0.f};
       return;
     }
     unsigned off[4];
     quad_offsets(rec_index(qv_, m_) * (unsigned)(L * P * 8), off);
-    if (PCT_COL_KO_NOLOC == 1 || PCT_COL_KO_NOLOC == 2) {
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-        for (int g = 0; g < NGL; ++g) raw[g][s4] = col_f32x4{(float)off[s4], 0.3f, 0.4f, 0.6f};
-      return;
-    }
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
       for (int g = 0; g < NGL; ++g)                // (a partial last group reads into the next record: never looked at)
-        raw[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[s4] + g * 64), 0, PCT_COL_LOC_NT ? 2 : 0));
+        raw[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[s4] + g * 64), 0, 0));
   };
   // FUSED: the query's reference points (one (x, y) per level), fetched with the record
   auto issue_ref = [&](const int b_, const int qv_, col_f32x2 (&rr)[L]) {
@@ -460,7 +333,6 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
     if (queue && tid == 0) next_idx[1] = atomicAdd(queue + xcd * WIN_QUEUE_STRIDE, 1u);
   }
 
-  stamp(-1);
   while (have) {
     // (opaque per iteration: the compiler otherwise hoists every per-lane expression of tid / qi out of the item loop --
     // a dozen 64-bit piece offsets, float copies of tid, ... -- and spills them)
@@ -508,7 +380,6 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
         for (int k = 0; k < P; ++k) asm volatile("" : "+v"(lxy[l][k]));
     }
     __builtin_amdgcn_sched_barrier(0);
-    stamp(7);                                                                 // records waited for, transposed, lxy formed
     // ---- publish the next item's index, fetch the one after it (its value is parked in LDS behind the staging barrier).
     // Issued behind the loads the pre-pass waits for: the memory counter is in-order, a wait for those would include it. ---
     unsigned f_new = 0u;
@@ -565,7 +436,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
           for (int g = 0; g < NGW; ++g)
             wraw[g][s4] = g * 4 + s4 < L
                               ? __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                    rs, (int)qo, (int)(p0 + (unsigned)(g * 4 + s4) * s16), PCT_COL_W_NT ? 2 : 0))
+                                    rs, (int)qo, (int)(p0 + (unsigned)(g * 4 + s4) * s16), 0))
                               : col_f32x4{0.f, 0.f, 0.f, 0.f};
         return;
       }
@@ -575,21 +446,18 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
       for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
         for (int g = 0; g < NGW; ++g)
-          wraw[g][s4] = (PCT_COL_KO_NOLOC == 2 || PCT_COL_KO_NOLOC == 3) ? col_f32x4{(float)off[s4], 0.1f, 0.2f, 0.3f} :
-              __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[s4] + g * 64), 0, PCT_COL_W_NT ? 2 : 0));
+          wraw[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[s4] + g * 64), 0, 0));
     };
-    // A weight record is 64 bytes: HALF a 128-byte line, the other half being the sibling head's, which the neighbouring
-    // workgroup fetches at about the same moment -- and two misses on one line in flight together are two fills on the
-    // memory side (measured: the weights came in 1.75x (I) / 2.08x (M) over).  So the odd head of a pair asks later, once
-    // the even head's fill has landed in L2.
-    const bool w_late = PCT_COL_W_LATE && (m & 1);
-    if (!w_late) load_weights();
+    load_weights();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       // boxes in LDS before the barrier
-    stamp(0);
     __syncthreads();                                                          // (A) boxes visible; pool free
-    stamp(1);
-    if (PCT_COL_PRIO == 3 || PCT_COL_PRIO == 4) __builtin_amdgcn_s_setprio(3);
-    if (PCT_COL_PRIO == 8) __builtin_amdgcn_s_setprio(PCT_COL_PRIO_PLAN);
+    // Wave priorities (s_setprio) by part of an item: records, pre-pass, planning, staging and decode 0, the first gathered
+    // level 3, the other levels 2.  A wave in its gather is served before the waves of the other workgroups that are
+    // decoding, planning or staging -- the gather is the LDS-latency chain of an item, everything else fills its gaps --
+    // and the first (finest, largest) level before the later ones.  Same-box A/B, P2 batch 128: I 1.70 -> 1.65 ms, M 2.24
+    // -> 2.16 ms against no priorities; other splits (gather 3 / 3, 1 / 1, planning raised) were within 1 % of each other
+    // on I and 2 % worse on M.
+    __builtin_amdgcn_s_setprio(0);
 
     // ---- the next item: its query per lane, its location loads issued (in flight until the next iteration) --------------
     int item_n, b_n = 0, m_n = 0, qv_n = 0;
@@ -602,8 +470,6 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
     // ---- windows and phases (uniform) --------------------------------------------------------------------------------
     int wx0[L], wy0[L], wwid[L], whgt[L], wsize[L], wbase[L], phase_of[L];
     bool latin[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) latin[l] = false;
     bool starts_phase[L];
     {
 #pragma unroll
@@ -618,12 +484,13 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
         wwid[l] = (int)((hi & 0xFFFFu) - lx) + 1;
         // (conflict-free corner order, below: the four corners of a sample must fall into four different bank classes --
         // pool index mod 4 -- which they do when the window is 2 mod 4 pixels wide; the extra columns are staged like any other)
-        // PCT_COL_LATIN == 2: only where the box is much larger than the column's cell on this level, i.e. where the lanes'
-        // offsets differ by several pixels and their pixel classes collide (model-like offsets: halo ~14 + 14 pixels; the
-        // init-like ones, whose classes are consecutive by construction, stay at 4 - 10 and keep the cheaper fixed order)
-        if (PCT_COL_LATIN == 1) latin[l] = true;
-        if (PCT_COL_LATIN == 2)
-          latin[l] = (wwid[l] - col_max_cell(Ws[l], CX)) + ((int)((hi >> 16) - ly) + 1 - col_max_cell(Hs[l], CY)) >= PCT_COL_LATIN_HALO;
+        // Taken only where the box is much larger than the column's cell on this level, i.e. where the lanes' offsets
+        // differ by several pixels and their pixel classes collide (model-like offsets: halo ~14 + 14 pixels; the init-like
+        // ones, whose classes are consecutive by construction, stay at 4 - 10 and keep the cheaper fixed order).  Same-box
+        // A/B, P2 batch 128 (profiles/r04_forward_structural_ab.txt), against the fixed order everywhere: M 2.168 -> 2.085 ms
+        // as an op, 2.290 -> 2.209 ms in the bench step; I 1.649 -> 1.700 (the two code paths cost the init-like case 3
+        // spilled registers).  The conflict-free order on every level: M 2.038, I 1.779.
+        latin[l] = (wwid[l] - col_max_cell(Ws[l], CX)) + ((int)((hi >> 16) - ly) + 1 - col_max_cell(Hs[l], CY)) >= 16;
         if (latin[l]) wwid[l] += (2 - wwid[l]) & 3;
         whgt[l] = (int)((hi >> 16) - ly) + 1;
         wsize[l] = wwid[l] * whgt[l];
@@ -661,7 +528,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
     // finest level's gather (one barrier: every wave is done with that region) and FLY while the coarsest level is gathered
     // from its own region above -- instead of the workgroup sitting through that flight between two barriers later.
     bool early_ok = false;
-    if constexpr (PCT_COL_EARLY && L >= 3) {
+    if constexpr (L >= 3) {
       int used1 = 0;
       bool has1 = false;
 #pragma unroll
@@ -677,7 +544,6 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
 #pragma unroll
     for (int l = 0; l < L; ++l) woff[l] = wbase[l] - wy0[l] * wwid[l] - wx0[l];
     float wts[L][P];
-    stamp(2);
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(value + (long long)b * S * MD), 0,
                                                         (int)((unsigned)S * (unsigned)MD * 4u), 0x00020000);
 
@@ -738,11 +604,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
         ([&] {
           const Geo g = geometry(lc, std::integral_constant<int, Ks>{});
           // pixel (x0, y0) sits at pool index woff + y0 * width + x0 (woff folds the window origin and base: one scalar)
-#if PCT_COL_KO_NOCONF
-          const unsigned a = (unsigned)(((__mul24(g.y0, wwid[l]) + g.x0 + woff[l]) & ~3) | (lane & 3)) << 6;
-#else
           const unsigned a = (unsigned)(__mul24(g.y0, wwid[l]) + g.x0 + woff[l]) << 6;
-#endif
           const unsigned rowb = (unsigned)wwid[l] << 6;
           {
             col_f32x4 va[4], vb[4];
@@ -930,7 +792,6 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
               for (int r = wv; r < whgt[l]; r += NW) {
                 const int y = wy0[l] + r;
                 const bool in_y = (unsigned)y < (unsigned)Hs[l];
-                if (PCT_COL_KO_NOSTAGE) continue;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rsrc, (__attribute__((address_space(3))) void *)(dst + (size_t)(r * wwid[l] + c0) * PXB), 16,
                     (int)(in_y ? voff : OOB), (int)(in_y ? lvl_off + (unsigned)y * row_bytes : 0u), 0, 0);
@@ -992,25 +853,20 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
           // staged early (below): landed + visible.  The memory counter is in order and the NEXT item's location record
           // was requested behind that staging: wait for everything BUT those youngest loads -- a plain barrier's
           // vmcnt(0) made every two-phase item sit through the best part of an HBM round trip here
-#if PCT_COL_EARLY_WAIT
           if (have_n) {
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(NGL * 4) : "memory");
           } else
-#endif
             __syncthreads();
         } else {
           if (ll > 0) __syncthreads();                                        // every wave is done with the pool
           stage_phase(phase_of[l]);
-          if (ll == 0) stamp(8);                                              // first phase's LDS-DMA issued
           if constexpr (ll == 0) {
             if (have_n) decode(item_n, b_n, m_n, qv_n);                        // while the LDS-DMA pieces are in flight
-            if (w_late) load_weights();
+            // (an unevaluated use: level_step keeps load_weights among its captures, and with that closure layout the
+            // compiler allocates this kernel's registers exactly as in the build the recorded timings were taken with)
+            (void)load_weights;
           }
-          if (ll == 0) stamp(3);
           __syncthreads();                                                    // windows staged (vmcnt(0) + barrier)
-          if (ll == 0) stamp(4);
-          if (ll == 0 && PCT_COL_PRIO == 4) __builtin_amdgcn_s_setprio(0);
-          if (ll == 0 && PCT_COL_PRIO == 8 && PCT_COL_PRIO_FRONT) __builtin_amdgcn_s_setprio(PCT_COL_PRIO_L0);   // weights / soft-max too
         }
       }
       if constexpr (ll == 0) {
@@ -1021,54 +877,37 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
           next_idx[1] = f_new;
         }
         front_end();
-        stamp(9);                                                             // weights waited for, transposed (FUSED: soft-max)
       }
-      if (PCT_COL_PRIO == 6) __builtin_amdgcn_s_setprio(ll + 1 < 3 ? ll + 1 : 3);     // (the further into the item, the more urgent)
-      if (PCT_COL_PRIO == 7) __builtin_amdgcn_s_setprio(ll == 0 ? 3 : 2);
-      if (PCT_COL_PRIO == 8) __builtin_amdgcn_s_setprio(ll == 0 ? PCT_COL_PRIO_L0 : PCT_COL_PRIO_REST);
-      if (PCT_COL_KO_NOGATHER == 2) {
-      } else if (phase_of[l] >= 0) {
-        if constexpr (PCT_COL_LATIN == 1) gather_level_lds_latin(std::integral_constant<int, l>{});
-        else if constexpr (PCT_COL_LATIN == 2) {
-          if (latin[l]) gather_level_lds_latin(std::integral_constant<int, l>{});
-          else gather_level_lds(std::integral_constant<int, l>{});
-        } else
-          gather_level_lds(std::integral_constant<int, l>{});
+      __builtin_amdgcn_s_setprio(ll == 0 ? 3 : 2);                            // (wave priorities: see the planning above)
+      if (phase_of[l] >= 0) {
+        if (latin[l]) gather_level_lds_latin(std::integral_constant<int, l>{});
+        else gather_level_lds(std::integral_constant<int, l>{});
       }
       else gather_level_global(std::integral_constant<int, l>{});             // box larger than the pool: global memory
       // (marking the global-memory path unlikely makes hipcc outline it behind a real call: 544 bytes of scratch per lane, 10x slower)
-      if (ll == 0) stamp(10);                                                 // first level gathered
-      if constexpr (ll == 0 && PCT_COL_EARLY && L >= 3) {
+      if constexpr (ll == 0 && L >= 3) {
         if (early_ok) {
           __syncthreads();                                                    // every wave is done with the finest window
           stage_phase(1);
         }
       }
-      // one group of the next item's location record per level: its registers are the ones this level's points freed
-      // the next item's location record (32 registers: the ones this level's points and the weights freed)
-      if constexpr (ll == (PCT_COL_LOC_AT < L ? PCT_COL_LOC_AT : L - 1)) {
+      // the next item's location record (32 registers: the ones this level's points and the weights freed), all groups at
+      // once behind the first gathered level: the two 64-byte halves of a 128-byte line back to back (-2 % on I and M
+      // against one group per gathered level, same-box A/B)
+      if constexpr (ll == 0) {
         if (have_n) issue_loc(b_n, m_n, qv_n, raw);
       }
 
     };
     if (!starts_phase[L - 1]) {                                               // (the finest level is gathered from global)
       if (have_n) decode(item_n, b_n, m_n, qv_n);
-      if (w_late) load_weights();
-      stamp(3);
-      stamp(4);
     }
-    if (PCT_COL_PRIO == 1) __builtin_amdgcn_s_setprio(3);
-    if (PCT_COL_PRIO == 2) __builtin_amdgcn_s_setprio(0);
-    if (PCT_COL_PRIO == 5) __builtin_amdgcn_s_setprio(1);
     [&]<int... LLs>(std::integer_sequence<int, LLs...>) {
       (level_step(std::integral_constant<int, LLs>{}), ...);
     }(std::make_integer_sequence<int, L>{});
-    if (PCT_COL_PRIO == 1 || PCT_COL_PRIO == 3 || (PCT_COL_PRIO >= 5 && PCT_COL_PRIO < 8)) __builtin_amdgcn_s_setprio(0);
-    if (PCT_COL_PRIO == 8) __builtin_amdgcn_s_setprio(PCT_COL_PRIO_TOP);
-    if (PCT_COL_PRIO == 2) __builtin_amdgcn_s_setprio(3);
+    __builtin_amdgcn_s_setprio(0);
     static_assert(NGL <= L, "one location group per level");
 
-    stamp(5);
     {
       // store, quad-cooperatively: register j of lane c holds piece (j + rho) % 4 of ITS record (rho is the same in the
       // whole quad).  A quad_perm rotation by k hands lane i the register k of lane (i - k) % 4; rotating the four received
@@ -1091,10 +930,11 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
       const unsigned oo[4] = {dpp_u<0x00>(own_o), dpp_u<0x55>(own_o), dpp_u<0xAA>(own_o), dpp_u<0xFF>(own_o)};
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4)
-        if (!PCT_COL_KO_NOSTORE || w4[s4][0] == 1.2345e30f)
+        // (non-temporal: the outputs are written once and must not push the value lines, which neighbouring columns and the
+        // sibling head re-use, out of the XCD's L2.  The records are loaded with default caching: nt there re-fetches the
+        // half lines two heads / two load groups share -- I: 7.9 -> 9.7 GB read per launch, 1.95 -> 2.14 ms.)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(col_u32x4, w4[s4]), rs,
-                                               (int)(oo[s4] + ((unsigned)(((qi - s4) + (int)rho) & 3) << 4)), 0,
-                                               (STREAM_NT || PCT_COL_STORE_NT) ? 2 : 0);
+                                               (int)(oo[s4] + ((unsigned)(((qi - s4) + (int)rho) & 3) << 4)), 0, 2);
     }
 
     item = item_n;
@@ -1102,15 +942,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 1024 ? 4 : (BLOCK == 512 ? 4 : 3)) 
     b = b_n;
     m = m_n;
     qv = qv_n;
-    stamp(6);
-  }
-  if constexpr (STAMP) {
-    if (tid == 0 && stamps)
-      for (int i = 0; i < 16; ++i) stamps[(size_t)blockIdx.x * 16 + i] = t_sum[i];
   }
 }
-
-unsigned long long *win_stamp_buffer();                                      // msda_forward_win.hip (diagnostic)
 
 // ---- launcher: returns -100 when this geometry is not covered (caller uses another kernel) ----------------------------
 // ref == nullptr: plain op; ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits).
@@ -1126,79 +959,35 @@ int launch_msda_forward_col(const void *value, const int64_t *shapes, const int6
   if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return -100;               // 32-bit byte offsets inside an image, all tensors
   if ((long long)S * M * D * 4 >= 0x7fffffffLL) return -100;                   // (0x80000000 is the out-of-range sentinel)
   if (S >= (1 << 24) || M >= (1 << 16)) return -100;                           // 24-bit multiplies in the record index
-  // threads per workgroup x workgroups per CU: 1024 x 1 (~150 KB pool, 128 registers), 512 x 2 (~75 KB each, 128 registers),
-  // 384 x 2 (~75 KB, 168 registers), 256 x 3 (~50 KB, 168 registers).  With more than one workgroup per CU the memory
-  // phases of one (records, staging) overlap the gather of the others.
-  static const int block_env = [] { const char *e = getenv("PCT_COL_BLOCK"); const int v = e ? atoi(e) : 0;
-                                    return (v == 256 || v == 384 || v == 512 || v == 768 || v == 1024) ? v : 256; }();
-  static const int pool_env = [] { const char *e = getenv("PCT_COL_POOL_KB"); return e ? atoi(e) : 0; }();
-  const int BLOCKV = block_env;
-  const bool one_wg = BLOCKV == 1024 || BLOCKV == 768;
-  const int pool_max = one_wg ? 158 : 78;
-  const int pool_kb = (pool_env >= 16 && pool_env <= pool_max) ? pool_env : (one_wg ? 150 : (BLOCKV == 256 ? 50 : 74));
-  const int wg_per_cu = one_wg ? 1 : ((BLOCKV == 256 && pool_kb <= 52) ? 3 : 2);
-  const int pool_px = pool_kb * 1024 / 64;
-  const size_t lds = (size_t)pool_px * 64 + ((size_t)(BLOCKV / 64) * L * 2 + 4) * sizeof(unsigned);   // pool, boxes, queue words
-  static const int grid_env = [] { const char *e = getenv("PCT_COL_GRID_WG"); return e ? atoi(e) : 0; }();   // (diagnostic: workgroups per CU launched)
-  const dim3 grid(256 * ((grid_env >= 1 && grid_env <= wg_per_cu) ? grid_env : wg_per_cu)), block(BLOCKV);
+  const int pool_px = COL_POOL_KB * 1024 / 64;
+  const size_t lds = (size_t)pool_px * 64 + ((size_t)(COL_BLOCK / 64) * L * 2 + 4) * sizeof(unsigned);   // pool, boxes, queue words
+  const dim3 grid(256 * COL_WG_PER_CU), block(COL_BLOCK);
   unsigned *queue = win_queue_slot(stream);                                    // nullptr: static item stride
   const float *v = static_cast<const float *>(value);
   const float *lc = static_cast<const float *>(loc), *at = static_cast<const float *>(attn);
   float *o = static_cast<float *>(out);
-#define PCT_COL_K(L_, FU_, B_, ST_)                                                                                     \
+#define PCT_COL(L_, FU_, PP_)                                                                                           \
   do {                                                                                                                  \
-    const hipError_t attr_rc = func_attr_per_device(reinterpret_cast<const void *>(&msda_forward_col_kernel<L_, FU_, B_, ST_>)); \
+    const hipError_t attr_rc = func_attr_per_device(reinterpret_cast<const void *>(&msda_forward_col_kernel<L_, FU_, PP_>)); \
     if (attr_rc != hipSuccess) return (int)attr_rc;                                                                     \
-    hipLaunchKernelGGL((msda_forward_col_kernel<L_, FU_, B_, ST_>), grid, block, lds, stream, v, shapes, starts, lc,    \
-                       at, N, S, M, pool_px, o, ref, ref_batch_stride, queue, ST_ ? win_stamp_buffer() : nullptr);      \
+    hipLaunchKernelGGL((msda_forward_col_kernel<L_, FU_, PP_>), grid, block, lds, stream, v, shapes, starts, lc, at, N, \
+                       S, M, pool_px, o, ref, ref_batch_stride, queue);                                                 \
   } while (0)
-#define PCT_COL_B(L_, FU_, ST_)                                \
-  do {                                                         \
-    if (BLOCKV == 1024) PCT_COL_K(L_, FU_, 1024, ST_);         \
-    else if (BLOCKV == 768) PCT_COL_K(L_, FU_, 768, ST_);      \
-    else if (BLOCKV == 512) PCT_COL_K(L_, FU_, 512, ST_);      \
-    else if (BLOCKV == 384) PCT_COL_K(L_, FU_, 384, ST_);      \
-    else PCT_COL_K(L_, FU_, 256, ST_);                         \
+#define PCT_COL_L(FU_, PP_)               \
+  do {                                    \
+    if (L == 3) PCT_COL(3, FU_, PP_);     \
+    else if (L == 4) PCT_COL(4, FU_, PP_); \
+    else PCT_COL(5, FU_, PP_);            \
   } while (0)
-#define PCT_COL(L_, FU_) PCT_COL_B(L_, FU_, false)
-  if (planes) {                         // piece-plane operands (see the kernel): 256-thread workgroups only
-    if (BLOCKV != 256) return -100;
-#define PCT_COL_PP(L_, FU_)                                                                                             \
-  do {                                                                                                                  \
-    const hipError_t attr_rc = func_attr_per_device(reinterpret_cast<const void *>(&msda_forward_col_kernel<L_, FU_, 256, false, true>)); \
-    if (attr_rc != hipSuccess) return (int)attr_rc;                                                                     \
-    hipLaunchKernelGGL((msda_forward_col_kernel<L_, FU_, 256, false, true>), grid, block, lds, stream, v, shapes, starts, lc, \
-                       at, N, S, M, pool_px, o, ref, ref_batch_stride, queue, nullptr);                                 \
-  } while (0)
-    if (ref) {
-      if (L == 3) PCT_COL_PP(3, true);
-      else if (L == 4) PCT_COL_PP(4, true);
-      else PCT_COL_PP(5, true);
-    } else {
-      if (L == 3) PCT_COL_PP(3, false);
-      else if (L == 4) PCT_COL_PP(4, false);
-      else PCT_COL_PP(5, false);
-    }
-#undef PCT_COL_PP
-    return (int)hipGetLastError();
-  }
-  if (win_stamp_buffer() && L == 4) {   // diagnostic: per-phase cycle stamps (tools/stamp_msda.py)
-    if (ref) PCT_COL_B(4, true, true);
-    else PCT_COL_B(4, false, true);
-    return (int)hipGetLastError();
-  }
-  if (ref) {
-    if (L == 3) PCT_COL(3, true);
-    else if (L == 4) PCT_COL(4, true);
-    else PCT_COL(5, true);
+  if (planes) {                         // piece-plane operands (see the kernel)
+    if (ref) PCT_COL_L(true, true);
+    else PCT_COL_L(false, true);
   } else {
-    if (L == 3) PCT_COL(3, false);
-    else if (L == 4) PCT_COL(4, false);
-    else PCT_COL(5, false);
+    if (ref) PCT_COL_L(true, false);
+    else PCT_COL_L(false, false);
   }
+#undef PCT_COL_L
 #undef PCT_COL
-#undef PCT_COL_B
-#undef PCT_COL_K
   return (int)hipGetLastError();
 }
 

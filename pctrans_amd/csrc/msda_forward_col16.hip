@@ -15,7 +15,6 @@
 //     soft-max statistics and the final sums cross the pair by DPP, and lane h stores channels 8h .. 8h + 7;
 //   * records are loaded lane by lane (no quad transposes): a lane's 32 / 64 contiguous bytes per level.
 #include <math.h>
-#include <stdlib.h>
 
 #include <utility>
 
@@ -652,9 +651,7 @@ int launch_msda_forward_col16(const void *value, const int64_t *shapes, const in
   if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return -100;
   if ((long long)S * M * L * P * 8 >= 0xffffffffLL) return -100;               // 32-bit byte offsets inside an image
   constexpr int BLOCK = 256;
-  static const int pool_kb = [] { const char *e = getenv("PCT_COL_POOL_KB"); const int v = e ? atoi(e) : 0;
-                                  return (v >= 16 && v <= 52) ? v : 50; }();
-  const int pool_px = pool_kb * 1024 / 32;
+  const int pool_px = 50 * 1024 / 32;                                          // ~50 KB of LDS per workgroup, 3 per CU
   const size_t lds = (size_t)pool_px * 32 + ((size_t)(BLOCK / 64) * L * 2 + 4) * sizeof(unsigned);
   const dim3 grid(256 * 3), block(BLOCK);
   unsigned *queue = win_queue_slot(stream);

@@ -36,13 +36,13 @@ namespace pct {
 // FUSED: `loc` holds raw sampling offsets, `attn` raw attention logits, `ref` the reference points; the kernel forms
 // location = ref[q, l] + offset / (W_l, H_l) and weight = softmax over the record's L*P logits itself
 // (ops/modules/ms_deform_attn.py:100-109), as msda_forward_dpp.hip does.
-template <typename T, int D, int L, int P, int NS, bool FUSED, bool STAMP = false>
-__global__ __launch_bounds__(WIN_BLOCK, (NS == 4 || P == 8) ? 3 : 4) void msda_forward_win_kernel(   // 50 KB LDS -> 3 WG/CU
+template <typename T, int D, int L, int P, int NS, bool FUSED>
+__global__ __launch_bounds__(WIN_BLOCK, 3) void msda_forward_win_kernel(   // 50 KB LDS -> 3 WG/CU
     const typename Traits<T>::store_t *__restrict__ value, const int64_t *__restrict__ shapes,
     const int64_t *__restrict__ starts, const float *__restrict__ loc, const float *__restrict__ attn, const int N,
     const int S, const int M, const int Lq, const int pyramid, const int pool_px,
     typename Traits<T>::store_t *__restrict__ out, const float *__restrict__ ref, const long long ref_batch_stride,
-    unsigned *__restrict__ queue, unsigned long long *__restrict__ stamps = nullptr)
+    unsigned *__restrict__ queue)
 {
   using ST = typename Traits<T>::store_t;
   constexpr int VEC = 16 / (int)sizeof(ST);       // channels per lane
@@ -55,18 +55,6 @@ __global__ __launch_bounds__(WIN_BLOCK, (NS == 4 || P == 8) ? 3 : 4) void msda_f
   constexpr int THT = SH * NS;                    // tile height
   constexpr int PPL = P / QL;                     // points each lane owns per level
   constexpr int PXB = QL * 16;                    // bytes per head-pixel
-  // diagnostic build only (STAMP): per-phase cycle sums of wave 0, written to a buffer nothing else reads
-  unsigned long long t_prev = 0, t_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto stamp = [&](int phase) {
-    if constexpr (STAMP) {
-      __builtin_amdgcn_sched_barrier(0);
-      unsigned long long t;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-      __builtin_amdgcn_sched_barrier(0);
-      if (phase >= 0) t_sum[phase] += t - t_prev;
-      t_prev = t;
-    }
-  };
   static_assert(D % VEC == 0 && (QL == 2 || QL == 4) && P % QL == 0 && L <= WIN_MAXL, "unsupported geometry");
   using v16 = vec_t<ST, VEC>;
   typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -230,13 +218,10 @@ __global__ __launch_bounds__(WIN_BLOCK, (NS == 4 || P == 8) ? 3 : 4) void msda_f
   // traffic, so each head fetched the lines again; the counter starts the heads of a tile within ~2 us of each other.
   int item = xcd * chunk + slot0;
   int par = 0;
-  stamp(-1);
   if (item < item_end) prepass(item, bb);
   while (item < item_end) {
     const unsigned *bbr = bb + par * BB_HALF;
-    stamp(0);
     __syncthreads();                                               // (A) boxes visible; pool free
-    stamp(1);
     // (the counter's answer is first looked at right before barrier (2): the round trip hides behind the staging)
     unsigned rfetch = 0u;
     if (queue && tid == 0) rfetch = atomicAdd(queue + xcd * WIN_QUEUE_STRIDE, 1u);
@@ -259,7 +244,6 @@ __global__ __launch_bounds__(WIN_BLOCK, (NS == 4 || P == 8) ? 3 : 4) void msda_f
         used += in_lds[l] ? w.size : 0;
       }
     }
-    stamp(2);
 
     // ---- stage the boxes that fit by LDS-DMA (global_load_lds_dwordx4): no VGPR round trip, every piece of every
     // level in flight at once; LDS address of a piece = wave-uniform base + lane*16 = dst + i*16 for
@@ -288,7 +272,6 @@ __global__ __launch_bounds__(WIN_BLOCK, (NS == 4 || P == 8) ? 3 : 4) void msda_f
         }
       }
     }
-    stamp(3);
     // ---- gather, one slot after the other.  Locations come from the registers the pre-pass filled; a slot's attention
     // weights (FUSED: logits) are only ISSUED here and consumed a whole slot later (`finish_points`), so the wave never
     // sits on a fresh load: the first slot's are in flight across barrier (2) together with the LDS-DMA pieces, slot
@@ -330,7 +313,6 @@ __global__ __launch_bounds__(WIN_BLOCK, (NS == 4 || P == 8) ? 3 : 4) void msda_f
       next_idx[0] = fetched;
     }
     __syncthreads();                                               // (2) windows staged; next item known
-    stamp(4);
 
     const ST *vlane = vimg + c * VEC;                               // + lane's channel slice (global path)
     const unsigned char *pool_lane = pool + c * 16;
@@ -523,18 +505,12 @@ __global__ __launch_bounds__(WIN_BLOCK, (NS == 4 || P == 8) ? 3 : 4) void msda_f
         *reinterpret_cast<v16 *>(out + rec * D + c * VEC) = o;
       }
     }
-    stamp(5);
     par ^= 1;
     {                                                               // (written before barrier (2) of this item)
       const unsigned nxt = __builtin_amdgcn_readfirstlane(next_idx[0]);
       item = nxt < (unsigned)(item_end - xcd * chunk) ? xcd * chunk + (int)nxt : item_end;   // never out of the chunk
     }
     if (item < item_end) prepass(item, bb + par * BB_HALF);
-    stamp(6);
-  }
-  if constexpr (STAMP) {
-    if (tid == 0 && stamps)
-      for (int i = 0; i < 8; ++i) stamps[(size_t)blockIdx.x * 8 + i] = t_sum[i];
   }
 }
 
@@ -590,10 +566,6 @@ int prepare_win_queue_device()
   return win_queue_slot(null_stream) ? 0 : 0;      // (nullptr = queues disabled or no memory: launches then use the static stride)
 }
 
-static unsigned long long *g_stamp_buffer = nullptr;
-void set_win_stamp_buffer(void *p) { g_stamp_buffer = static_cast<unsigned long long *>(p); }
-unsigned long long *win_stamp_buffer() { return g_stamp_buffer; }
-
 // ---- launcher: returns -100 when this geometry is not covered (caller uses another kernel) ----------------------
 // ref == nullptr: plain op; ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits).
 template <typename T>
@@ -609,59 +581,35 @@ int launch_msda_forward_win(const void *value, const int64_t *shapes, const int6
   if ((long long)N * Lq * M < 32768) return -100;                  // too small to fill a persistent grid
   if ((long long)N * ((long long)S + 64 * L) * M >= 0x7fffffffLL) return -100;   // item counter is 32-bit
   constexpr int QL = 16 / VEC;
-  static const int ns_env = [] { const char *e = getenv("PCT_WIN_NS"); return e ? atoi(e) : 4; }();
-  // P = 8 (config 5): twice the points per lane -> 2 slots per lane, but still the 50 KB pool / 3 workgroups per CU
-  const int NS = P == 8 ? (sizeof(ST) == 2 ? 1 : 2) : ((ns_env == 1 || ns_env == 2) ? ns_env : 4);   // 16-bit: 128 queries per slot
-  const int pool_bytes = P == 8 ? 50 * 1024 : (NS == 1 ? 28 * 1024 : (NS == 2 ? 36 * 1024 : 50 * 1024));
-  const int pool_px = pool_bytes / (QL * 16);
+  // a 50 KB pool, 3 workgroups per CU; P = 4: NS = 4 query slots per lane.  P = 8 (config 5): twice the points per lane
+  // -> 2 slots per lane (16-bit: 1, 128 queries per slot)
+  const int pool_px = 50 * 1024 / (QL * 16);
   const size_t lds = (size_t)pool_px * QL * 16 + 2 * (WIN_BLOCK / 64) * WIN_MAXL * 2 * sizeof(unsigned) + 16;
   const int pyramid = Lq == S ? 1 : 0;
-  const int wg_per_cu = (NS == 4 || P == 8) ? 3 : 4;
-  const dim3 grid(256 * wg_per_cu), block(WIN_BLOCK);
+  const dim3 grid(256 * 3), block(WIN_BLOCK);
   unsigned *queue = win_queue_slot(stream);                        // nullptr: static item stride
   const ST *v = static_cast<const ST *>(value);
   const float *lc = static_cast<const float *>(loc), *at = static_cast<const float *>(attn);
   ST *o = static_cast<ST *>(out);
-  if constexpr (sizeof(ST) == 4) {
-    if (g_stamp_buffer && !ref && L == 4 && NS == 4) {   // diagnostic build: per-phase cycle stamps (tools/stamp_msda.py)
-      hipLaunchKernelGGL((msda_forward_win_kernel<T, 16, 4, 4, 4, false, true>), grid, block, lds, stream, v, shapes,
-                         starts, lc, at, N, S, M, Lq, pyramid, pool_px, o, ref, ref_batch_stride, queue, g_stamp_buffer);
-      return (int)hipGetLastError();
-    }
-  }
-#define PCT_WINP(L_, P_, NS_, FU_)                                                                                    \
+#define PCT_WIN(L_, P_, NS_, FU_)                                                                                     \
   hipLaunchKernelGGL((msda_forward_win_kernel<T, 16, L_, P_, NS_, FU_>), grid, block, lds, stream, v, shapes, starts, \
-                     lc, at, N, S, M, Lq, pyramid, pool_px, o, ref, ref_batch_stride, queue, nullptr)
-#define PCT_WIN(L_, NS_, FU_) PCT_WINP(L_, 4, NS_, FU_)
+                     lc, at, N, S, M, Lq, pyramid, pool_px, o, ref, ref_batch_stride, queue)
+#define PCT_WIN_L(P_, NS_, FU_)             \
+  do {                                      \
+    if (L == 3) PCT_WIN(3, P_, NS_, FU_);   \
+    else if (L == 4) PCT_WIN(4, P_, NS_, FU_); \
+    else PCT_WIN(5, P_, NS_, FU_);          \
+  } while (0)
+  constexpr int NS8 = sizeof(ST) == 2 ? 1 : 2;
   if (P == 8) {
-    constexpr int NS8 = sizeof(ST) == 2 ? 1 : 2;
-    if (ref) {
-      if (L == 3) PCT_WINP(3, 8, NS8, true);
-      else if (L == 4) PCT_WINP(4, 8, NS8, true);
-      else PCT_WINP(5, 8, NS8, true);
-    } else {
-      if (L == 3) PCT_WINP(3, 8, NS8, false);
-      else if (L == 4) PCT_WINP(4, 8, NS8, false);
-      else PCT_WINP(5, 8, NS8, false);
-    }
-    return (int)hipGetLastError();
-  }
-#define PCT_WIN_L(NS_, FU_)                 \
-  if (L == 3) PCT_WIN(3, NS_, FU_);         \
-  else if (L == 4) PCT_WIN(4, NS_, FU_);    \
-  else PCT_WIN(5, NS_, FU_)
-  if (ref) {
-    if (NS == 4) { PCT_WIN_L(4, true); }
-    else if (NS == 2) { PCT_WIN_L(2, true); }
-    else { PCT_WIN_L(1, true); }
+    if (ref) PCT_WIN_L(8, NS8, true);
+    else PCT_WIN_L(8, NS8, false);
   } else {
-    if (NS == 4) { PCT_WIN_L(4, false); }
-    else if (NS == 2) { PCT_WIN_L(2, false); }
-    else { PCT_WIN_L(1, false); }
+    if (ref) PCT_WIN_L(4, 4, true);
+    else PCT_WIN_L(4, 4, false);
   }
 #undef PCT_WIN_L
 #undef PCT_WIN
-#undef PCT_WINP
   return (int)hipGetLastError();
 }
 

@@ -114,10 +114,7 @@ inline hipError_t func_attr_per_device(const void *fn, const int bytes = 160 * 1
 // 87 040 items whether 1, 2 or 3 workgroups per CU ran it -- the figure rounds 2 and 3 read as "the record stream's
 // skeleton" -- and 0.34 ms with the counters apart (profiles/r04_forward_structural_ab.txt).  The product kernels draw
 // ~40 items per microsecond and hide the fetch two items ahead, so they did not get faster; the cap is gone.
-#ifndef PCT_QUEUE_STRIDE
-#define PCT_QUEUE_STRIDE 64
-#endif
-constexpr int WIN_QUEUE_STRIDE = PCT_QUEUE_STRIDE;
+constexpr int WIN_QUEUE_STRIDE = 64;
 unsigned *win_queue_slot(hipStream_t stream);
 int prepare_win_queue_device();     // allocate the ring now (outside any capture)
 

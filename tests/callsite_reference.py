@@ -188,7 +188,7 @@ def mask_head_autocast(feats, ref_xy, params, stride, target_size):
     """bf16 yardstick: the bf16 chain of test_dyn_mask_head_gpu (features, generated weights and hidden activations rounded
     to bf16 as bf16 1x1 convolutions see them; fp32 accumulation, rel-coord term and biases), with the third layer's
     operands rounded too -- the chain there keeps w2 and its input in fp32, where autocast (and the bf16 kernels, which run
-    that layer on the matrix cores: csrc/dmh_common.hpp, PCT_DMH_L2_MFMA) round both -- then the logits rounded to bf16
+    that layer on the matrix cores: csrc/dmh_common.hpp, DmhPair) round both -- then the logits rounded to bf16
     and resized as torch resizes a bf16 tensor."""
     N, C, H, W = feats.shape
     r = lambda t: t.bfloat16().float()
