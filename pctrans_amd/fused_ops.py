@@ -93,15 +93,17 @@ def linear_k128(x, weight, bias=None, relu=False, x_add=None):
 
 
 def conv1x1_from_token_rows_supported(x, conv):
-    """A 1x1 convolution of 128 channels-last feature maps with at most 32 output channels, forward only, small batch:
-    the decoder's `mask_head` (dec.py:539) on the pixel decoder's finest map, which is a transposed VIEW of the encoder's
-    [N, S, 128] token rows."""
+    """A 1x1 convolution of 128-channel feature maps with at most 32 output channels, forward only, small batch: the
+    decoder's `mask_head` (dec.py:539) on the pixel decoder's finest map.  That map is a transposed VIEW of the encoder's
+    [N, S, 128] token rows with four levels, and the FPN output with three: channels-last, except at batch 1, where it
+    comes out NCHW-contiguous (its rows are then gathered into a copy)."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 128 and x.shape[0] <= 4):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
         return False
     H, W = x.shape[2], x.shape[3]
-    return (x.stride(1) == 1 and x.stride(3) == 128 and x.stride(2) == 128 * W and H * W >= 4096
+    token_rows = x.stride(1) == 1 and x.stride(3) == 128 and x.stride(2) == 128 * W
+    return ((token_rows or x.is_contiguous()) and H * W >= 4096
             and x.data_ptr() % 16 == 0 and (x.stride(0) * 4) % 16 == 0
             and conv.kernel_size == (1, 1) and conv.in_channels == 128 and conv.out_channels <= 32
             and conv.weight.dtype == torch.float32 and getattr(conv, "norm", None) is None
@@ -131,7 +133,8 @@ def conv1x1_from_token_rows(x, conv):
             b32[:co] = b.detach()
         ent = (stamp, w32, b32)
         conv.__dict__["_pct_pad32"] = ent
-    outs = [linear_k128(x[n].permute(1, 2, 0).reshape(H * W, 128), ent[1], ent[2]) for n in range(N)]   # views: no copy
+    # token rows: views, no copy; an NCHW-contiguous map: reshape gathers each image's rows into a copy
+    outs = [linear_k128(x[n].permute(1, 2, 0).reshape(H * W, 128), ent[1], ent[2]) for n in range(N)]
     y = torch.stack(outs, 0)                                               # [N, HW, 32]
     return y[..., :co].permute(0, 2, 1).reshape(N, co, H, W).contiguous()
 

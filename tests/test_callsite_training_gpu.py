@@ -38,11 +38,18 @@ import torch
 
 import callsite_reference as ref
 from callsite_capture import ENTRY_POINTS, TRAINING_ENTRIES, CallsiteCapture
-from test_callsite_parity_gpu import K_DPP, Report, _check, no_tf32  # noqa: F401  (no_tf32: fixture)
+from callsite_check import K_DPP, Report
+from callsite_check import check as _check
 
 pytestmark = pytest.mark.gpu
 
 B_GENERIC, B_COL = 2, 3
+
+
+@pytest.fixture
+def no_tf32(monkeypatch):
+    monkeypatch.setattr(torch.backends.cuda.matmul, "allow_tf32", False)
+    monkeypatch.setattr(torch.backends.cudnn, "allow_tf32", False)
 
 # name -> (ResNet depth, batch, H, W, queries, targets per image, dataset)
 CONFIGS = {

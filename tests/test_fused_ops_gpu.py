@@ -620,6 +620,31 @@ def test_token_row_conv_never_serves_another_modules_weights():
     assert float((c - a).abs().max()) < 1e-4
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,H,W", [(1, 64, 64), (1, 68, 64), (3, 72, 64)])
+def test_token_row_conv_takes_an_nchw_contiguous_map(N, H, W):
+    """With three encoder levels the mask features are the FPN output, which is NCHW-contiguous at batch 1 (channels-last
+    from batch 2 on).  The projection accepts both layouts and gives the same bits from either, within the fp32 bound
+    of float64."""
+    from pctrans_amd import fused_ops
+    from pctrans_amd.layers import Conv2d
+    dev = torch.device("cuda")
+    g = torch.Generator(device="cpu").manual_seed(N * H + W)
+    rows = torch.randn(N, H * W, 128, generator=g).to(dev)
+    view = rows.view(N, H, W, 128).permute(0, 3, 1, 2)
+    nchw = view.contiguous()
+    torch.manual_seed(7)
+    conv = Conv2d(128, 16, kernel_size=1).to(dev)
+    with torch.no_grad():
+        assert fused_ops.conv1x1_from_token_rows_supported(nchw, conv)
+        got, from_view = fused_ops.conv1x1_from_token_rows(nchw, conv), fused_ops.conv1x1_from_token_rows(view, conv)
+        want = torch.nn.functional.conv2d(nchw.double(), conv.weight.double(), conv.bias.double())
+        yard = torch.nn.functional.conv2d(nchw, conv.weight, conv.bias)
+    assert torch.equal(got, from_view)
+    err, err32 = float((got.double() - want).abs().max()), float((yard.double() - want).abs().max())
+    assert err <= max(2.0 * err32, 5e-6 * max(1.0, float(want.abs().max()))), (err, err32)
+
+
 @pytest.mark.parametrize("N,K,H,W,bias", [(2, 256, 128, 128, True), (3, 512, 68, 64, True), (1, 2048, 16, 16, True),
                                           (2, 32, 8, 16, False), (5, 1024, 32, 32, True), (1, 16, 16, 8, True)])
 def test_conv1x1_nchw_is_as_accurate_as_fp32(N, K, H, W, bias):
