@@ -19,7 +19,8 @@
 //     16 s + 4 h + e for e < 4, 16 s + 8 + 4 h + e - 4 else): no LDS round trip, no shuffles;
 //   * both weight matrices are pre-split per call into the exact LDS image of every chunk (W1: 32 rows x 128 k, row stride
 //     272 B; W2: 128 rows x 32 permuted k, row stride 80 B; both conflict-free for ds_read_b128), 56 KB per chunk, streamed from
-//     L2 through registers into a double-buffered stage, one barrier per chunk;
+//     L2 by LDS-DMA into a double-buffered stage, one barrier per chunk;
+//   * a tile's LayerNorm and stores run under the next tile's first product;
 //   * the row statistics of the LayerNorm are complete inside a wave (a lane and its partner in the other half hold a row's 128
 //     columns).
 #include <hip/hip_runtime.h>
@@ -124,19 +125,18 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
   const long long ntiles = (M + FF_BM - 1) / FF_BM;
   const int nch = F / FF_CH;
 
+  // An image travels to LDS by LDS-DMA: piece p (0 .. 13) of 4 KiB is ONE 16-byte buffer_load ... lds per thread, wave w writing
+  // bytes 1024 w .. + 1023 of the piece lane-linearly -- the global image is the exact LDS image (ffn_split_weights_kernel), so no
+  // register holds it on the way and the 272 / 80 B row strides stay as they are.  A stage's DMAs are retired by a counted vmcnt
+  // before the barrier that precedes its first read (never __syncthreads(): its fence would drain every DMA in flight).  Image
+  // c + 1 into the free stage: its W2 / bias pieces 7 .. 13 behind the barrier of chunk c - 1 (the W1 part of that stage may still
+  // be read at a tile seam), its W1 pieces 0 .. 6 in phase A of chunk c.  (The buffer form: one lane offset and a scalar one per
+  // DMA, where global_load_lds's 64-bit lane addresses of the loop-invariant images were hoisted and spilled.)
   const auto img_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(img), 0, (int)((long long)nch * FF_STAGE),
                                                           0x00020000);
-  // An image travels to LDS through registers, 14 pieces of 16 bytes per thread, ONE load and one store per MFMA group of six: the
-  // CU's vector-memory path takes a 1 KiB wave-instruction per ~16 cycles, so the four waves' loads issued together in bursts of
-  // seven backed up into the issuing waves (stamps: ~50 cycles per load, 700 per chunk).  Window position p = 0 .. 13 is piece
-  // ORD[p] (the W2 / bias part first: see the tile seam below), stored six groups after it was requested, slot p % 7.
-  ff_i32x4 gst[7];
-  auto t_piece = [](const int p) { return p < 7 ? p + 7 : p - 7; };
-  auto t_load = [&](const int p, const int image) {
-    gst[p % 7] = __builtin_amdgcn_raw_buffer_load_b128(img_rsrc, tid * 16, image * FF_STAGE + t_piece(p) * (FF_BLOCK * 16), 0);
-  };
-  auto t_store = [&](const int p, unsigned char *stage) {
-    *reinterpret_cast<ff_i32x4 *>(stage + t_piece(p) * (FF_BLOCK * 16) + tid * 16) = gst[p % 7];
+  auto t_dma = [&](const int piece, const int image, unsigned char *stage) {
+    auto *dst = (__attribute__((address_space(3))) void *)(stage + piece * (FF_BLOCK * 16) + wave * 1024);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(img_rsrc, dst, 16, tid * 16, image * FF_STAGE + piece * (FF_BLOCK * 16), 0, 0);
   };
 
   // fragment addresses inside a stage: W1 (A operand of GEMM 1): hidden row r, k = 16 s + 8 h ..; W2 (A operand of GEMM 2):
@@ -144,18 +144,20 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
   const int w1_off = r * FF_W1ROW + 16 * h;                       // + 32 s, + plane
   const int w2_off = FF_W2OFF + r * FF_W2ROW + 16 * h;            // + cb * 32 rows, + 32 s, + plane
 
-  // stage 1 <- the last image (W1 of chunk 0), stage 0 <- image 0; then what the groups before "iteration 0" would have done for
-  // image 1 (into stage 1: its W2 part only, the W1 part there is still needed): positions 0 and 1 stored, 2 .. 7 requested
+  // s_waitcnt vmcnt(n) lgkmcnt(0) as the builtin, so that hipcc's own wait bookkeeping sees the DMAs retired (while it counts one
+  // as pending it waits vmcnt(0) at the next use of any loaded register), then the barrier
+  auto wait_barrier = [](auto n_tag) {
+    constexpr int n = decltype(n_tag)::value;
+    static_assert(n >= 0 && n < 16, "vmcnt field");
+    __builtin_amdgcn_s_waitcnt(0x70 | n);                         // gfx9 encoding: vmcnt [3:0], expcnt [6:4] = 7 (no wait), lgkmcnt [11:8] = 0
+    asm volatile("s_barrier" ::: "memory");
+  };
+
+  // stage 1 <- the last image (W1 of chunk 0), stage 0 <- image 0, retired before the barrier below
 #pragma unroll
-  for (int p0 = 0; p0 < 14; p0 += 7) {
-#pragma unroll
-    for (int p = p0; p < p0 + 7; ++p) t_load(p, nch - 1);
-#pragma unroll
-    for (int p = p0; p < p0 + 7; ++p) t_store(p, ff_smem + FF_STAGE);
-#pragma unroll
-    for (int p = p0; p < p0 + 7; ++p) t_load(p, 0);
-#pragma unroll
-    for (int p = p0; p < p0 + 7; ++p) t_store(p, ff_smem);
+  for (int p = 0; p < FF_PIECES; ++p) {
+    t_dma(p, nch - 1, ff_smem + FF_STAGE);
+    t_dma(p, 0, ff_smem);
   }
   if (tid < FF_D) {                                               // b2, gamma, beta behind the stages
     float *par = reinterpret_cast<float *>(ff_smem + 2 * FF_STAGE);
@@ -163,13 +165,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
     par[FF_D + tid] = gamma[tid];
     par[2 * FF_D + tid] = beta[tid];
   }
-  t_load(0, 1 % nch);
-  t_load(1, 1 % nch);
-  t_store(0, ff_smem + FF_STAGE);
-  t_store(1, ff_smem + FF_STAGE);
-#pragma unroll
-  for (int p = 2; p < 8; ++p) t_load(p, 1 % nch);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  wait_barrier(std::integral_constant<int, 0>{});
   int cur = 0;                                                    // stage holding the image of the chunk about to be used
 
   // a tile's rows of x are requested one tile ahead (under GEMM 2 of the last chunk of the tile before, when the fragments of the
@@ -187,59 +183,76 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
       xraw[2 * s + 1] = __builtin_amdgcn_raw_buffer_load_b128(xq, xoff, s * 64 + 16, 0);
     }
   };
+
+  // GEMM 1: D1[hidden 8 q + 4 h + t][row r] over k = 128 from the W1 part of stage `st`.  One wave per SIMD: nobody else covers an
+  // LDS round trip, so the fragments of k-step s + 1 are requested before the MFMAs of step s
+  ff_bf16x8 xp[8][3];                                             // this wave's 32 rows of x as GEMM 1's B fragments
+  ff_f32x16 h_hi, h_lo;
+  ff_bf16x8 wa[2][3];
+  auto split_x = [&](const int s) {
+    ff_split8(__builtin_bit_cast(ff_f32x4, xraw[2 * s]), __builtin_bit_cast(ff_f32x4, xraw[2 * s + 1]), xp[s]);
+  };
+  auto w1_frags = [&](const unsigned char *st, const int s) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) wa[s & 1][p] = *reinterpret_cast<const ff_bf16x8 *>(st + w1_off + 32 * s + p * FF_W1PLANE);
+  };
+  auto gemm1_step = [&](const int s) {
+    const ff_bf16x8 a1 = wa[s & 1][0], a2 = wa[s & 1][1], a3 = wa[s & 1][2];
+    h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][2], h_lo, 0, 0, 0);
+    h_hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][0], h_hi, 0, 0, 0);
+    h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, xp[s][0], h_lo, 0, 0, 0);
+    h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xp[s][1], h_lo, 0, 0, 0);
+    h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][1], h_lo, 0, 0, 0);
+    h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xp[s][0], h_lo, 0, 0, 0);
+  };
+  // a tile's chunk 0 starts with its first product alone: its W1 is in the image the tile before ended on, in the stage that is not
+  // `cur`.  Its k-step s + 1 of x is split under k-step s, with the LayerNorm of the tile before (`epi(s)`; nothing for the first
+  // tile), and it takes image 1's W2 / bias pieces by DMA into the part of that stage it does not read; iteration 0 then refills the
+  // W1 part
+  auto first_gemm1 = [&](auto epi) {
+    unsigned char *pst = ff_smem + (cur ^ 1) * FF_STAGE;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) h_hi[j] = h_lo[j] = 0.f;
+    w1_frags(pst, 0);
+    split_x(0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      if (s < 7) w1_frags(pst, s + 1);
+      gemm1_step(s);
+      if (s < 7) split_x(s + 1);
+      if (s < 7) t_dma(FF_HALF + s, 1 % nch, pst);
+      epi(s);
+      __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);          // the reads first (left alone the scheduler sinks them)
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {                               // the epilogue's arithmetic and stores between the MFMAs
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);
+        if (i == 1 && s < 7) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        if (s >= 4 && i < 4) __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  };
+
   x_request(blockIdx.x, 0, 8);
+  first_gemm1([](int) {});
 
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    // ---- this wave's 32 rows of x as GEMM 1's B fragments ---------------------------------------------------------------------
     const long long row0 = tile * FF_BM + 32 * wave;
     const long long left = M - row0;
     const unsigned xbytes = (unsigned)((left < 32 ? (left < 0 ? 0 : left) : 32) * ldx * 4);
     const auto xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(X + row0 * ldx), 0, (int)xbytes, 0x00020000);
-    ff_bf16x8 xp[8][3];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) ff_split8(__builtin_bit_cast(ff_f32x4, xraw[2 * s]), __builtin_bit_cast(ff_f32x4, xraw[2 * s + 1]), xp[s]);
     ff_f32x16 y_hi[4], y_lo[4];                                   // D2[col block][cols 32][rows 32]
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
       for (int j = 0; j < 16; ++j) y_hi[cb][j] = y_lo[cb][j] = 0.f;
+    ff_f32x4 res[16];                                             // the residual: columns 32 cb + 8 q + 4 h .. + 3 of row r, [4 cb + q]
 
-    // GEMM 1: D1[hidden 8 q + 4 h + t][row r] over k = 128 from the W1 part of stage `st`.  One wave per SIMD: nobody else covers an
-    // LDS round trip, so the fragments of k-step s + 1 are requested before the MFMAs of step s
-    ff_f32x16 h_hi, h_lo;
-    ff_bf16x8 wa[2][3];
-    auto w1_frags = [&](const unsigned char *st, const int s) {
-#pragma unroll
-      for (int p = 0; p < 3; ++p) wa[s & 1][p] = *reinterpret_cast<const ff_bf16x8 *>(st + w1_off + 32 * s + p * FF_W1PLANE);
-    };
-    auto gemm1_step = [&](const int s) {
-      const ff_bf16x8 a1 = wa[s & 1][0], a2 = wa[s & 1][1], a3 = wa[s & 1][2];
-      h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][2], h_lo, 0, 0, 0);
-      h_hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][0], h_hi, 0, 0, 0);
-      h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, xp[s][0], h_lo, 0, 0, 0);
-      h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xp[s][1], h_lo, 0, 0, 0);
-      h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][1], h_lo, 0, 0, 0);
-      h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, xp[s][0], h_lo, 0, 0, 0);
-    };
-    // chunk 0's first product stands alone (its W1 is in the image the previous tile ended on); every later one runs under the
-    // bias / ReLU / split arithmetic of the chunk before it
-    {
-      const unsigned char *pst = ff_smem + (cur ^ 1) * FF_STAGE;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) h_hi[j] = h_lo[j] = 0.f;
-      w1_frags(pst, 0);
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        if (s < 7) w1_frags(pst, s + 1);
-        gemm1_step(s);
-        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);        // the reads first (left alone the scheduler sinks them)
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_s_barrier();                               // iteration 0 refills that stage
-    }
-
-    // entering iteration `chunk`: wa[0] = step 0 of the W1 fragments and bq = the biases it needs, gst = the first half of image
-    // chunk + 1 on its way
+    // entering iteration `chunk`: wa[0] = step 0 of the W1 fragments and bq = the biases it needs, the W2 / bias pieces of image
+    // chunk + 1 on their way
     ff_f32x4 bq[4];
     auto load_bias = [&](const unsigned char *st) {
 #pragma unroll
@@ -262,8 +275,10 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
       __builtin_amdgcn_sched_barrier(0);
       // ---- phase A: GEMM 1 of chunk + 1 under bias, ReLU, split of this chunk: value pair m of the B fragments of GEMM 2 is k-step
       // sg = m / 4, word w = m % 4 (accumulator quartet q = 2 sg + w / 2, elements 2 (w % 2) and + 1); pairs 0 - 3 (k-step 0) behind
-      // the odd steps here, pairs 4 - 7 (k-step 1, first used by group 4) behind groups 0 - 3 of phase B; image chunk + 1: positions
-      // 2 .. 9 stored, 8 .. 13 requested ------------------------------------------------------------------------------------------
+      // the odd steps here, pairs 4 - 7 (k-step 1, first used by group 4) behind groups 0 - 3 of phase B; image chunk + 1: the W1
+      // pieces 0 .. 6 by DMA into the stage nobody reads since the previous barrier, two per step in steps 0 - 3 (as early as that:
+      // 6.545 -> 6.525 ms against one per step in steps 0 - 6).  The last chunk (no product here) requests the tile's residual rows
+      // in steps 0 - 5: the barrier's wait, which leaves only the x loads of phase B in flight, retires them ---------------------
       unsigned hpw[2][3][4];
       ff_bf16x8 wb[2][3], wc[3];
       auto valu_slice = [&](const int m) {
@@ -286,26 +301,35 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
           for (int p = 0; p < 3; ++p) wb[0][p] = *reinterpret_cast<const ff_bf16x8 *>(st + w2_off + p * FF_W2PLANE);
         }
         if (s & 1) valu_slice(s >> 1);
-        t_store(s + 2, nst);
-        if (s <= 5) t_load(s + 8, nxt);
+        if constexpr (LAST) {
+          if (s < 6) {
+#pragma unroll
+            for (int i = s < 4 ? 3 * s : 2 * s + 4; i < (s < 4 ? 3 * s + 3 : 2 * s + 6); ++i)     // column 8 i + 4 h
+              res[i] = __builtin_bit_cast(ff_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)((r * ldx + 4 * h) * 4), 32 * i, 0));
+          }
+        }
+        if (s < 3) {
+          t_dma(2 * s, nxt, nst);
+          t_dma(2 * s + 1, nxt, nst);
+        }
+        if (s == 3) t_dma(6, nxt, nst);
         if constexpr (!LAST) {                                    // reads first; vector instructions, the load and the store between MFMAs
 #pragma unroll
           for (int i = 0; i < 6; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             if (s & 1) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
             if (!(i & 1)) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // fragment reads spread between the MFMAs
-            if (i == 1 && s <= 5) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            if (i == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+            if ((i == 1 || (i == 3 && s < 3)) && s < 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
       }
       __builtin_amdgcn_sched_barrier(0);
       // ---- phase B: GEMM 2: D2[col 32 cb + 8 q + 4 h + t][row r] += W2 . h over this chunk's 32 hidden units; group g = (s, cb),
-      // the next group's fragments requested before this group's MFMAs.  Image chunk + 1 is complete behind group 3 and the last two
-      // groups' fragments are in registers before group 6, so the chunk's barrier sits after group 5: groups 6 and 7 cover it, the
-      // first reads of the next iteration and the first two stores of image chunk + 2 into the stage just read (its W2 part: at a
-      // tile seam the W1 part is still needed by the next tile's first product); image chunk + 2 is requested from group 0 on -------
+      // the next group's fragments requested before this group's MFMAs.  The last two groups' fragments are in registers before
+      // group 6, so the chunk's barrier sits after group 5, behind the wait that retires image chunk + 1's DMAs: groups 6 and 7 cover
+      // it, the first reads of the next iteration and the W2 / bias pieces of image chunk + 2 into the stage just read (the last
+      // chunk leaves them to the next tile's first product: no DMA is in flight in the epilogue, whose loads then have counted waits)
       auto w2_frags = [&](ff_bf16x8 (&dst)[3], const int g) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
@@ -320,15 +344,17 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
           w2_frags(wc, 7);
         }
         if (g < 4) valu_slice(4 + g);
-        t_load(g, nxt2);
         if constexpr (LAST) x_request(tile + gridDim.x, g, g + 1);     // the next tile's rows, two row-strided loads per group
-        if (g < 4) t_store(10 + g, nst);
-        if (g >= 6) t_store(g - 6, const_cast<unsigned char *>(st));   // behind the barrier: this stage is free, image chunk + 2
-        if (g == 6) {
-          if constexpr (!LAST) {
+        if constexpr (!LAST) {                                    // behind the barrier: this stage is free, image chunk + 2
+          if (g == 6) {
+#pragma unroll
+            for (int p = FF_HALF; p < FF_HALF + 4; ++p) t_dma(p, nxt2, const_cast<unsigned char *>(st));
             w1_frags(nst, 0);
             load_bias(nst);
           }
+          if (g == 7)
+#pragma unroll
+            for (int p = FF_HALF + 4; p < FF_PIECES; ++p) t_dma(p, nxt2, const_cast<unsigned char *>(st));
         }
         const ff_bf16x8 a1 = g == 7 ? wc[0] : wb[g & 1][0], a2 = g == 7 ? wc[1] : wb[g & 1][1], a3 = g == 7 ? wc[2] : wb[g & 1][2];
         y_lo[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, h_frag(sg, 2), y_lo[cb], 0, 0, 0);
@@ -346,12 +372,13 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
           if (g == 5) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           if (g == 6 && !LAST) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           if (g == 6 && !LAST && i == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          if (i == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-          if (i == 3 && (g < 4 || g >= 6)) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+          if (g == 6 && !LAST && i < 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+          if (g == 7 && !LAST && i < 3) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (g == 5) {
-          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (g == 5) {                                             // (the last chunk: the 12 x loads of groups 0 - 5 stay in flight)
+          if constexpr (LAST) wait_barrier(std::integral_constant<int, 12>{});
+          else wait_barrier(std::integral_constant<int, 0>{});
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -360,7 +387,8 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
     for (int chunk = 0; chunk + 1 < nch; ++chunk) chunk_body(std::false_type{}, chunk);
     chunk_body(std::true_type{}, nch - 1);
 
-    // ---- epilogue: y_*[cb][4 q + t] = y[row r][column 32 cb + 8 q + 4 h + t]; + b2 + residual, LayerNorm, store -----------------
+    // ---- epilogue: y_*[cb][4 q + t] = y[row r][column 32 cb + 8 q + 4 h + t]; + b2 + residual, then the LayerNorm and the stores in
+    // eight slices, one per k-step of the next tile's first product, which they run under ---------------------------------------
     const unsigned ybytes = (unsigned)((left < 32 ? (left < 0 ? 0 : left) : 32) * ldy * 4);
     const auto yr = __builtin_amdgcn_make_buffer_rsrc(Y + row0 * ldy, 0, (int)ybytes, 0x00020000);
     float v[64];
@@ -369,38 +397,50 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c0 = 32 * cb + 8 * q + 4 * h;
-        const ff_f32x4 res = __builtin_bit_cast(ff_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)((r * ldx + c0) * 4), 0, 0));
         const ff_f32x4 bb = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + c0 * 4);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) v[16 * cb + 4 * q + t] = ((y_hi[cb][4 * q + t] + y_lo[cb][4 * q + t]) + bb[t]) + res[t];
+        for (int t = 0; t < 4; ++t) v[16 * cb + 4 * q + t] = ((y_hi[cb][4 * q + t] + y_lo[cb][4 * q + t]) + bb[t]) + res[4 * cb + q][t];
       }
-    float sm = 0.f;
+    __builtin_amdgcn_sched_barrier(0);
+    float sm = 0.f, s2 = 0.f, mean, rstd;
+    auto epi = [&](const int s) {
+      if (s < 2) {                                                // the row sum
 #pragma unroll
-    for (int j = 0; j < 64; ++j) sm += v[j];
-    sm += __shfl_xor(sm, 32);
-    const float mean = sm * (1.f / 128.f);
-    float s2 = 0.f;
+        for (int j = 32 * s; j < 32 * s + 32; ++j) sm += v[j];
+        if (s == 1) {
+          sm += __shfl_xor(sm, 32);
+          mean = sm * (1.f / 128.f);
+        }
+      } else if (s < 4) {                                         // centred, the sum of squares
 #pragma unroll
-    for (int j = 0; j < 64; ++j) {
-      v[j] -= mean;
-      s2 += v[j] * v[j];
-    }
-    s2 += __shfl_xor(s2, 32);
-    const float rstd = rsqrtf(s2 * (1.f / 128.f) + eps);
+        for (int j = 32 * (s - 2); j < 32 * (s - 2) + 32; ++j) {
+          v[j] -= mean;
+          s2 += v[j] * v[j];
+        }
+        if (s == 3) {
+          s2 += __shfl_xor(s2, 32);
+          rstd = rsqrtf(s2 * (1.f / 128.f) + eps);
+        }
+      } else {                                                    // scaled, shifted, stored: column block s - 4
+        const int cb = s - 4;
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
+        for (int q = 0; q < 4; ++q) {
+          const int c0 = 32 * cb + 8 * q + 4 * h;
+          const ff_f32x4 gq = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + (FF_D + c0) * 4);
+          const ff_f32x4 eq = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + (2 * FF_D + c0) * 4);
+          ff_f32x4 o;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c0 = 32 * cb + 8 * q + 4 * h;
-        const ff_f32x4 gq = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + (FF_D + c0) * 4);
-        const ff_f32x4 eq = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + (2 * FF_D + c0) * 4);
-        ff_f32x4 o;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) o[t] = v[16 * cb + 4 * q + t] * rstd * gq[t] + eq[t];
-        // (y rows with the non-temporal hint: 6.79 -> 6.97 ms)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ff_i32x4, o), yr, (int)((r * ldy + c0) * 4), 0, 0);
+          for (int t = 0; t < 4; ++t) o[t] = v[16 * cb + 4 * q + t] * rstd * gq[t] + eq[t];
+          // (y rows with the non-temporal hint: 6.79 -> 6.97 ms)
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ff_i32x4, o), yr, (int)((r * ldy + 4 * h) * 4), 4 * (c0 - 4 * h), 0);
+        }
       }
+    };
+    // (also after the last tile, on the zero rows x_request returns past the end: with a use on one path only, the compiler sinks
+    // the x loads out of the last chunk into that path, behind the barrier whose counted wait assumes them)
+    first_gemm1(epi);
   }
+  __builtin_amdgcn_s_waitcnt(0x70);                               // no DMA outlives the workgroup's LDS
 }
 
 // the kernel's LDS attribute for the current device, outside any stream capture (pct_prepare_device)
