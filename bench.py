@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- MSDeformAttn pixel decoder + PCTrans transformer decoder forward throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and no more: set-up, the untimed warm-up (pre-warm, settle blocks, W
+steps), the K timed steps, --dump-outputs, the JSON line.  --full adds the measurements that take runs of their own
+(cpu_baseline below, ~25 s on the host); the timed steps and every other field of the line are the same either way.
 
 N > 1: one rank per GPU over RCCL.  Started bare (`python bench.py --gpus N`, no WORLD_SIZE in the environment) this
 process never touches a GPU: it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
@@ -21,8 +25,8 @@ The JSON line carries, besides the throughput:
   roofline      the MSDeformAttn forward kernel (the hot kernel north_star names), timed live with HIP events on its
                 launch stream inside the timed steps; achieved = algorithmic bytes per launch / mean launch time,
                 algorithmic bytes = N * S * (2*M*D*e + 3*M*L*P*4)  (SURVEY.md 8d), peak = 8 TB/s HBM3E.
-  cpu_baseline  the C/OpenMP oracle (oracle/msda_oracle.c, kind "port") timed on this host for the same MSDeformAttn
-                layer shape, rank 0 / N=1 only, bounded to ~10 s.
+  cpu_baseline  --full only: the C/OpenMP oracle (oracle/msda_oracle.c, kind "port") timed on this host for the same
+                MSDeformAttn layer shape, and configs[0]'s whole head on the CPU; rank 0 / N=1 only, bounded to ~25 s.
 """
 import argparse
 import json
@@ -89,7 +93,9 @@ def parse():
                          "sampling_offsets.weight ~ N(0, s) scaled per layer so that offsets are N(0, 2 px) on the sampled "
                          "level; I = the reference's initialisation (zero weight, head-directional bias of 1..4 px: what an "
                          "untrained network gives)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (cpu_baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0's predictions and mask "
@@ -225,6 +231,12 @@ def host_cpu():
     except OSError:
         pass
     return model, (len(cores) or logical or 1), (logical or 1)
+
+
+def wants_cpu_baseline(args, world):
+    """The CPU baseline is an extra of --full (unless --no-cpu-baseline), and only a 1-rank run takes it: a plain run does
+    what its headline figure needs and no more."""
+    return args.full and not args.no_cpu_baseline and world == 1
 
 
 def cpu_baseline(args, levels_hw):
@@ -581,6 +593,7 @@ def main():
             "vs_baseline": None,
             "dtype": "bf16 decoder (autocast) / f32 MSDeformAttn pixel decoder" if args.dtype == "bf16" else "f32",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": "configs[1]: %dx%d synthetic, ResNet-50 feature shapes (backbone not in the timed path), "
                             "MSDeformAttn pixel decoder over %d levels %s + 9-layer masked-attention decoder, "
@@ -689,7 +702,7 @@ def main():
                 "issue": issue_from_profile(args, "pct::cross_attention_kernel"),
                 "note": "algorithmic bytes: K-content, K-position, V, the query halves and the output once (bf16), mask bytes once",
             }
-        if not args.no_cpu_baseline and world == 1:
+        if wants_cpu_baseline(args, world):
             out["cpu_baseline"] = cpu_baseline(args, levels_hw)
             out["cpu_baseline"]["gpu_same_unit"] = args.batch / (mean_ms * 1e-3) if fwd else None
         print(json.dumps(out), flush=True)
