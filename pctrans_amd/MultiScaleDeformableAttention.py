@@ -134,6 +134,22 @@ def fused_forward_supported(value, reference_points, sampling_offsets):
             and value.shape[1] * value.shape[2] * value.shape[3] * 4 < 2 ** 31 - 1)      # per image; larger batches are chunked inside the library
 
 
+def _reference_points(ref, N, Lq, L, lq_name):
+    """Checks reference points [N or 1, Lq, L, 2] and returns (ref, batch_stride) as the fused entry points take them: rows
+    contiguous, images batch_stride floats apart, 0 for one set shared by the batch (an expanded, stride-0 batch dim)."""
+    if ref.dtype != torch.float32 or not ref.is_cuda:
+        raise RuntimeError("reference_points must be a float32 device tensor")
+    if tuple(ref.shape[1:]) != (Lq, L, 2) or ref.shape[0] not in (1, N):
+        raise RuntimeError("reference_points must be [N or 1, %s, L, 2]" % lq_name)
+    if ref.stride()[1:] != (L * 2, 2, 1):
+        ref = ref.contiguous()
+    batch_stride = 0 if (ref.shape[0] == 1 or ref.stride(0) == 0) else ref.stride(0)
+    if batch_stride not in (0, Lq * L * 2):
+        ref = ref.contiguous()
+        batch_stride = Lq * L * 2
+    return ref, batch_stride
+
+
 def ms_deform_attn_fused_forward(value, spatial_shapes, level_start_index, reference_points, sampling_offsets,
                                  attention_logits):
     """MSDeformAttn.forward's middle section in one launch (OPS/modules/ms_deform_attn.py:100-118):
@@ -153,17 +169,7 @@ def ms_deform_attn_fused_forward(value, spatial_shapes, level_start_index, refer
         raise RuntimeError("ms_deform_attn_fused_forward: unsupported geometry (use the unfused op)")
     if sampling_offsets.dtype != torch.float32 or attention_logits.dtype != torch.float32:
         raise RuntimeError("ms_deform_attn_fused_forward: offsets / logits must be float32")
-    ref = reference_points
-    if ref.dtype != torch.float32 or not ref.is_cuda:
-        raise RuntimeError("reference_points must be a float32 device tensor")
-    if tuple(ref.shape[1:]) != (Lq, L, 2) or ref.shape[0] not in (1, N):
-        raise RuntimeError("reference_points must be [N or 1, Lq, L, 2]")
-    if ref.stride()[1:] != (L * 2, 2, 1):
-        ref = ref.contiguous()
-    batch_stride = 0 if (ref.shape[0] == 1 or ref.stride(0) == 0) else ref.stride(0)
-    if batch_stride not in (0, Lq * L * 2):
-        ref = ref.contiguous()
-        batch_stride = Lq * L * 2
+    ref, batch_stride = _reference_points(reference_points, N, Lq, L, "Lq")
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     _lib.prepare_device(value.device)
     with torch.cuda.device(value.device), _timed("forward", value, _last_kernel):
@@ -222,17 +228,7 @@ def ms_deform_attn_forward_planes(value_planes, spatial_shapes, level_start_inde
         raise RuntimeError("ms_deform_attn_forward_planes: unsupported geometry (use the reference layout)")
     ref, batch_stride = None, 0
     if reference_points is not None:
-        ref = reference_points
-        if ref.dtype != torch.float32 or not ref.is_cuda:
-            raise RuntimeError("reference_points must be a float32 device tensor")
-        if tuple(ref.shape[1:]) != (S, L, 2) or ref.shape[0] not in (1, N):
-            raise RuntimeError("reference_points must be [N or 1, S, L, 2]")
-        if ref.stride()[1:] != (L * 2, 2, 1):
-            ref = ref.contiguous()
-        batch_stride = 0 if (ref.shape[0] == 1 or ref.stride(0) == 0) else ref.stride(0)
-        if batch_stride not in (0, S * L * 2):
-            ref = ref.contiguous()
-            batch_stride = S * L * 2
+        ref, batch_stride = _reference_points(reference_points, N, S, L, "S")
     out = torch.empty((N, S, M * D), dtype=torch.float32, device=value_planes.device)
     _lib.prepare_device(value_planes.device)
     with torch.cuda.device(value_planes.device), _timed("forward", value_planes, _last_kernel):

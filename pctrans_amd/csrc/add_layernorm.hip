@@ -7,6 +7,7 @@
 // per wave at COLS = 128), x and y are read once, mean / variance are two-pass in registers (sum, then centred sum of
 // squares, reduced with wave shuffles) and the result is written once: 3 HBM passes instead of 5, all 16-byte coalesced.
 #include "msda_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -49,7 +50,7 @@ int launch_add_layernorm(const float *x, const float *y, const float *gamma, con
                          long long rows, int cols, float *out, hipStream_t stream)
 {
   if (rows == 0) return 0;
-  if (cols != 128 && cols != 256 && cols != 64) return -4;
+  if (cols != 128 && cols != 256 && cols != 64) return PCT_ERR_UNSUPPORTED;
   const int rpb = ALN_BLOCK / (cols / 4);
   long long nblk = (rows + rpb - 1) / rpb;
   if (nblk > 256 * 16) nblk = 256 * 16;               // grid-stride beyond 16 blocks per CU

@@ -5,12 +5,9 @@
 #include <math.h>
 
 #include "msda_common.hpp"
+#include "split_bf16.hpp"    // bf16x8, bf16x4, f32x4
 
 namespace pct {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Reductions over the four 16-lane groups of a wave (lane ^ 16, lane ^ 32) on the vector unit: v_permlane16_swap hands the
 // even rows the odd rows' value and the reverse, v_permlane32_swap does the same for the two halves; op(first result, second

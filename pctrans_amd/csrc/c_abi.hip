@@ -5,61 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/pctrans_hip.h"
+#include "launchers.hpp"
 #include "msda_common.hpp"
-
-namespace pct {
-template <typename T>
-int launch_msda_forward(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int, int,
-                        int, int, int, int, void *, hipStream_t);
-int launch_linear_k128(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period, const float *w,
-                       const float *bias,
-                       long long rows, int n, int epi,
-                       float *y, long long ldy, const float *residual, long long ldr, const float *gamma,
-                       const float *beta, float eps, hipStream_t stream);
-void set_msda_kernel_choice(int v);
-int msda_last_kernel();
-void set_msda_bwd_kernel_choice(int c);
-int msda_bwd_last_kernel();
-int launch_linear_k128_split_multi(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period,
-                                   int nseg, const float *const *w, const float *const *bias, const int *n,
-                                   const int *use_add, float *const *y, const long long *ldy, long long rows,
-                                   hipStream_t stream);
-int launch_linear_ln_split(const float *x, long long ldx, const float *w, unsigned short *w_pieces, int K, const float *bias,
-                           const float *residual, long long ldr, const float *gamma, const float *beta, float eps,
-                           long long rows, float *out, long long ldo, hipStream_t stream);
-template <typename A>
-int launch_msda_backward(const void *, const int64_t *, const int64_t *, const void *, const void *, const void *,
-                         int, int, int, int, int, int, int, void *, void *, void *, hipStream_t);
-int launch_dyn_mask_head_fused(const float *, const float *, const float *, int, int, int, int, int, int, int, int, int,
-                               void *, void *, unsigned char *, hipStream_t);
-int launch_dyn_mask_head_mfma(const float *, const float *, const float *, int, int, int, int, int, int, int, int, int,
-                              void *, void *, unsigned char *, hipStream_t);
-int prepare_win_queue_device();
-int prepare_msda_backward_col_device();
-int prepare_ffn_device();
-int launch_msda_forward_planes(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int, int, int,
-                               int, int, int, void *, hipStream_t, const float *, long long);
-int launch_ffn_fused_split(const float *, long long, const float *, const float *, const float *, const float *, const float *,
-                           const float *, float, int, long long, void *, float *, long long, hipStream_t);
-int launch_conv1x1_nchw_split(const float *, const float *, const float *, unsigned short *, int, int, int, float *, hipStream_t);
-int launch_conv1x1_groupnorm_tokens(const float *, const float *, const float *, unsigned short *, const float *, const float *, float,
-                                    int, int, int, float *, float *, float *, long long, hipStream_t);
-int launch_cross_attention(const void *, const void *, const void *, const void *, const void *, const unsigned char *,
-                           const unsigned char *, int, int, int, int, float, void *, hipStream_t);
-int launch_masked_attention(const void *, const void *, const void *, const unsigned char *, int, int, int, int, int,
-                            int, float, int, void *, hipStream_t);
-int launch_groupnorm_flatten(const float *, const float *, const float *, int, int, int, int, float, float *, float *,
-                             long long, long long, hipStream_t);
-int launch_lsap(const float *, int, int, int, const int *, int *, int *, hipStream_t);
-int launch_add_layernorm(const float *, const float *, const float *, const float *, float, long long, int, float *,
-                         hipStream_t);
-template <typename T>
-int launch_msda_forward_special(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int,
-                                int, int, int, int, int, void *, hipStream_t, const float *, long long);
-int launch_dyn_mask_head(const float *, const float *, const float *, int, int, int, int, int, int, int, int, int,
-                         int, void *, unsigned char *, hipStream_t);
-}  // namespace pct
 
 namespace {
 
@@ -81,12 +28,24 @@ int check_common(const void *value, const int64_t *shapes, const int64_t *starts
   return PCT_OK;
 }
 
-// largest number of images per launch whose value tensor stays below 2 GiB (at least 1)
-int images_per_launch(int N, long long image_bytes)
+// A launcher's status as the ABI reports it.  PCT_NOT_COVERED never crosses the ABI: from a launcher that has no other kernel to
+// fall back on it is PCT_ERR_UNSUPPORTED (`not_covered`: where a launcher uses it for something else); every other status is
+// a PCT_ERR_* or a hipError_t already.
+int abi_status(int rc, int not_covered = PCT_ERR_UNSUPPORTED) { return rc == pct::PCT_NOT_COVERED ? not_covered : rc; }
+
+// launch(b0, n) for images b0 .. b0 + n - 1, the batch in chunks whose value tensor stays below 2 GiB (at least one image): the
+// specialised kernels address one launch's value tensor with 32-bit byte offsets, as the reference chunks with im2col_step
+// (cu:66-80) -- same results.  Stops at the first status that is not 0 and returns it.
+template <typename Launch>
+int for_image_chunks(int N, long long image_bytes, Launch launch)
 {
   int chunk = N;
   while (chunk > 1 && (long long)chunk * image_bytes >= 0x7fffffffLL) chunk = (chunk + 1) / 2;
-  return chunk;
+  for (int b0 = 0; b0 < N; b0 += chunk) {
+    const int rc = launch(b0, N - b0 < chunk ? N - b0 : chunk);
+    if (rc != 0) return rc;
+  }
+  return PCT_OK;
 }
 
 template <typename T, typename LT>
@@ -99,19 +58,12 @@ int forward_impl(const void *value, const int64_t *shapes, const int64_t *starts
   if (N == 0 || Lq == 0) return PCT_OK;
   if (!out) return PCT_ERR_BAD_ARG;
   if ((uintptr_t)out % sizeof(typename pct::Traits<T>::store_t)) return PCT_ERR_ALIGNMENT;
-  // The specialised kernels address one launch's value tensor with 32-bit byte offsets: a batch whose value tensor
-  // reaches 2 GiB goes out in chunks of images, as the reference does with im2col_step (cu:66-80) -- same results.
   using ST = typename pct::Traits<T>::store_t;
-  const int chunk = images_per_launch(N, (long long)S * M * D * (long long)sizeof(ST));
-  for (int b0 = 0; b0 < N; b0 += chunk) {
-    const int n = N - b0 < chunk ? N - b0 : chunk;
-    const int rc2 = pct::launch_msda_forward<T>(
-        static_cast<const ST *>(value) + (long long)b0 * S * M * D, shapes, starts, loc + (long long)b0 * Lq * M * L * P * 2,
-        attn + (long long)b0 * Lq * M * L * P, n, S, M, D, L, Lq, P, static_cast<ST *>(out) + (long long)b0 * Lq * M * D,
-        static_cast<hipStream_t>(stream));
-    if (rc2 != 0) return rc2;
-  }
-  return PCT_OK;
+  return for_image_chunks(N, (long long)S * M * D * (long long)sizeof(ST), [&](const long long b0, const int n) {
+    return pct::launch_msda_forward<T>(static_cast<const ST *>(value) + b0 * S * M * D, shapes, starts, loc + b0 * Lq * M * L * P * 2,
+                                       attn + b0 * Lq * M * L * P, n, S, M, D, L, Lq, P, static_cast<ST *>(out) + b0 * Lq * M * D,
+                                       static_cast<hipStream_t>(stream));
+  });
 }
 
 template <typename A>
@@ -129,6 +81,33 @@ int backward_impl(const A *value, const int64_t *shapes, const int64_t *starts, 
     return PCT_ERR_ALIGNMENT;
   return pct::launch_msda_backward<A>(value, shapes, starts, loc, attn, grad_out, N, S, M, D, L, Lq, P,
                                       grad_value, grad_loc, grad_attn, static_cast<hipStream_t>(stream));
+}
+
+// The arguments the three dynamic-mask-head entry points share.  They differ in the workspace (`has_ws`: required, aligned to
+// ws_mask + 1) and in the alignment of up_logits (up_mask + 1).  PCT_OK also for an empty call: the caller returns then.
+int check_dyn_mask_head(const float *mask_feat, const float *ref_points, const float *params, int batch, int channels,
+                        int num_query, int height, int width, int stride, int rel_coord, int target_h, int target_w,
+                        const void *up_logits, unsigned up_mask, bool has_ws, const void *ws, unsigned ws_mask,
+                        const unsigned char *attn_mask)
+{
+  if (batch < 0 || num_query < 0 || channels <= 0 || height <= 0 || width <= 0 || stride <= 0 || target_h <= 0 ||
+      target_w <= 0)
+    return PCT_ERR_BAD_ARG;
+  if (batch == 0 || num_query == 0) return PCT_OK;
+  if (!mask_feat || !params || !up_logits || !attn_mask || (has_ws && !ws) || (rel_coord && !ref_points)) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)mask_feat | (uintptr_t)params | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
+  if (((uintptr_t)up_logits & up_mask) || (has_ws && ((uintptr_t)ws & ws_mask))) return PCT_ERR_ALIGNMENT;
+  if ((long long)height * width >= 0x7fffffffLL / 64) return PCT_ERR_UNSUPPORTED;
+  return PCT_OK;
+}
+
+// the second operand of the K = 128 entry points (x_add == NULL: none)
+int check_x_add(const float *x_add, long long ld_add, long long add_period)
+{
+  if (!x_add) return PCT_OK;
+  if (ld_add < 128 || (ld_add & 3) || ((uintptr_t)x_add & 15u)) return PCT_ERR_ALIGNMENT;
+  if (add_period < 32 || add_period * ld_add * 4 > 0x7fffffffLL) return PCT_ERR_BAD_ARG;
+  return PCT_OK;
 }
 
 }  // namespace
@@ -204,16 +183,12 @@ int pct_ms_deform_attn_fused_forward_f32(const float *value, const int64_t *spat
   if (!output || !ref_points || ref_batch_stride < 0) return PCT_ERR_BAD_ARG;
   if (((uintptr_t)output | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
   const long long S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-  const int chunk = images_per_launch(batch, S * M * D * 4);               // as forward_impl: < 2 GiB of value per launch
-  for (int b0 = 0; b0 < batch; b0 += chunk) {
-    const int n = batch - b0 < chunk ? batch - b0 : chunk;
-    const int r = pct::launch_msda_forward_special<float>(
+  return abi_status(for_image_chunks(batch, S * M * D * 4, [&](const long long b0, const int n) {
+    return pct::launch_msda_forward_special<float>(
         value + b0 * S * M * D, spatial_shapes, level_start, offsets + b0 * Lq * M * L * P * 2, attn_logits + b0 * Lq * M * L * P,
         n, spatial_size, num_heads, channels, num_levels, num_query, num_point, output + b0 * Lq * M * D,
         static_cast<hipStream_t>(stream), ref_points + b0 * ref_batch_stride, ref_batch_stride);
-    if (r != 0) return r == -100 ? PCT_ERR_UNSUPPORTED : r;
-  }
-  return PCT_OK;
+  }));
 }
 
 int pct_ms_deform_attn_forward_planes_f32(const float *value_planes, const int64_t *spatial_shapes, const int64_t *level_start,
@@ -229,17 +204,13 @@ int pct_ms_deform_attn_forward_planes_f32(const float *value_planes, const int64
   if (((uintptr_t)output | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
   if (num_query != spatial_size || channels != 16 || num_point != 4) return PCT_ERR_UNSUPPORTED;
   const long long S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-  const int chunk = images_per_launch(batch, S * M * D * 4);               // as forward_impl: < 2 GiB of value per launch
-  for (int b0 = 0; b0 < batch; b0 += chunk) {
-    const int n = batch - b0 < chunk ? batch - b0 : chunk;
-    const int r = pct::launch_msda_forward_planes(
+  return abi_status(for_image_chunks(batch, S * M * D * 4, [&](const long long b0, const int n) {
+    return pct::launch_msda_forward_planes(
         value_planes + b0 * S * M * D, spatial_shapes, level_start, loc_planes + b0 * Lq * M * L * P * 2,
         attn_planes + b0 * Lq * M * L * P, n, spatial_size, num_heads, channels, num_levels, num_query, num_point,
         output + b0 * Lq * M * D, static_cast<hipStream_t>(stream), ref_points ? ref_points + b0 * ref_batch_stride : nullptr,
         ref_batch_stride);
-    if (r != 0) return r == -100 ? PCT_ERR_UNSUPPORTED : r;
-  }
-  return PCT_OK;
+  }));
 }
 
 int pct_ms_deform_attn_backward_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
@@ -270,14 +241,9 @@ int pct_dynamic_mask_head_forward(const float *mask_feat, const float *ref_point
                                   int target_h, int target_w, int out_dtype, void *up_logits,
                                   unsigned char *attn_mask, void *stream)
 {
-  if (batch < 0 || num_query < 0 || channels <= 0 || height <= 0 || width <= 0 || stride <= 0 || target_h <= 0 ||
-      target_w <= 0)
-    return PCT_ERR_BAD_ARG;
-  if (batch == 0 || num_query == 0) return PCT_OK;
-  if (!mask_feat || !params || !up_logits || !attn_mask || (rel_coord && !ref_points)) return PCT_ERR_BAD_ARG;
-  if (((uintptr_t)mask_feat | (uintptr_t)params | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
-  if ((uintptr_t)up_logits & 15u) return PCT_ERR_ALIGNMENT;
-  if ((long long)height * width >= 0x7fffffffLL / 64) return PCT_ERR_UNSUPPORTED;
+  const int rc = check_dyn_mask_head(mask_feat, ref_points, params, batch, channels, num_query, height, width, stride, rel_coord,
+                                     target_h, target_w, up_logits, 15u, false, nullptr, 0u, attn_mask);
+  if (rc != PCT_OK || batch == 0 || num_query == 0) return rc;
   return pct::launch_dyn_mask_head(mask_feat, ref_points, params, batch, channels, num_query, height, width, stride,
                                    rel_coord, target_h, target_w, out_dtype, up_logits, attn_mask,
                                    static_cast<hipStream_t>(stream));
@@ -288,14 +254,9 @@ int pct_dynamic_mask_head_forward_mfma(const float *mask_feat, const float *ref_
                                        int target_h, int target_w, void *scratch, void *up_logits,
                                        unsigned char *attn_mask, void *stream)
 {
-  if (batch < 0 || num_query < 0 || channels <= 0 || height <= 0 || width <= 0 || stride <= 0 || target_h <= 0 ||
-      target_w <= 0)
-    return PCT_ERR_BAD_ARG;
-  if (batch == 0 || num_query == 0) return PCT_OK;
-  if (!mask_feat || !params || !up_logits || !attn_mask || !scratch || (rel_coord && !ref_points)) return PCT_ERR_BAD_ARG;
-  if (((uintptr_t)mask_feat | (uintptr_t)params | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
-  if (((uintptr_t)up_logits & 7u) || ((uintptr_t)scratch & 1u)) return PCT_ERR_ALIGNMENT;
-  if ((long long)height * width >= 0x7fffffffLL / 64) return PCT_ERR_UNSUPPORTED;
+  const int rc = check_dyn_mask_head(mask_feat, ref_points, params, batch, channels, num_query, height, width, stride, rel_coord,
+                                     target_h, target_w, up_logits, 7u, true, scratch, 1u, attn_mask);
+  if (rc != PCT_OK || batch == 0 || num_query == 0) return rc;
   return pct::launch_dyn_mask_head_mfma(mask_feat, ref_points, params, batch, channels, num_query, height, width,
                                         stride, rel_coord, target_h, target_w, scratch, up_logits, attn_mask,
                                         static_cast<hipStream_t>(stream));
@@ -306,18 +267,12 @@ int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, const float
                                              int rel_coord, int target_h, int target_w, void *workspace,
                                              void *up_logits, unsigned char *attn_mask, void *stream)
 {
-  if (batch < 0 || num_query < 0 || channels <= 0 || height <= 0 || width <= 0 || stride <= 0 || target_h <= 0 ||
-      target_w <= 0)
-    return PCT_ERR_BAD_ARG;
-  if (batch == 0 || num_query == 0) return PCT_OK;
-  if (!mask_feat || !params || !up_logits || !attn_mask || !workspace || (rel_coord && !ref_points)) return PCT_ERR_BAD_ARG;
-  if (((uintptr_t)mask_feat | (uintptr_t)params | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
-  if (((uintptr_t)up_logits | (uintptr_t)workspace) & 15u) return PCT_ERR_ALIGNMENT;
-  if ((long long)height * width >= 0x7fffffffLL / 64) return PCT_ERR_UNSUPPORTED;
-  const int r = pct::launch_dyn_mask_head_fused(mask_feat, ref_points, params, batch, channels, num_query, height, width,
-                                                stride, rel_coord, target_h, target_w, workspace, up_logits, attn_mask,
-                                                static_cast<hipStream_t>(stream));
-  return r == -100 ? PCT_ERR_UNSUPPORTED : r;
+  const int rc = check_dyn_mask_head(mask_feat, ref_points, params, batch, channels, num_query, height, width, stride, rel_coord,
+                                     target_h, target_w, up_logits, 15u, true, workspace, 15u, attn_mask);
+  if (rc != PCT_OK || batch == 0 || num_query == 0) return rc;
+  return abi_status(pct::launch_dyn_mask_head_fused(mask_feat, ref_points, params, batch, channels, num_query, height, width,
+                                                    stride, rel_coord, target_h, target_w, workspace, up_logits, attn_mask,
+                                                    static_cast<hipStream_t>(stream)));
 }
 
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
@@ -335,8 +290,7 @@ int pct_linear_k128_f32(const float *x, long long ldx, const float *x_add, long 
                         void *stream)
 {
   if (rows < 0 || n <= 0 || ldx < 128 || ldy < n || (act != 0 && act != 1)) return PCT_ERR_BAD_ARG;
-  if (x_add && (ld_add < 128 || (ld_add & 3) || ((uintptr_t)x_add & 15u))) return PCT_ERR_ALIGNMENT;
-  if (x_add && (add_period < 32 || add_period * ld_add * 4 > 0x7fffffffLL)) return PCT_ERR_BAD_ARG;
+  if (const int rc = check_x_add(x_add, ld_add, add_period); rc != PCT_OK) return rc;
   if (rows == 0) return PCT_OK;
   if (!x || !w || !y) return PCT_ERR_BAD_ARG;
   if (n % 32) return PCT_ERR_UNSUPPORTED;
@@ -358,8 +312,7 @@ int pct_linear_k128_multi_f32(const float *x, long long ldx, const float *x_add,
                               float *const *y, const long long *ldy, long long rows, void *stream)
 {
   if (rows < 0 || nseg < 1 || nseg > 4 || ldx < 128 || !w || !bias || !n || !use_add || !y || !ldy) return PCT_ERR_BAD_ARG;
-  if (x_add && (ld_add < 128 || (ld_add & 3) || ((uintptr_t)x_add & 15u))) return PCT_ERR_ALIGNMENT;
-  if (x_add && (add_period < 32 || add_period * ld_add * 4 > 0x7fffffffLL)) return PCT_ERR_BAD_ARG;
+  if (const int rc = check_x_add(x_add, ld_add, add_period); rc != PCT_OK) return rc;
   if (rows == 0) return PCT_OK;
   if (!x) return PCT_ERR_BAD_ARG;
   if (((uintptr_t)x & 15u) || (ldx & 3)) return PCT_ERR_ALIGNMENT;
@@ -367,9 +320,10 @@ int pct_linear_k128_multi_f32(const float *x, long long ldx, const float *x_add,
     if (!w[s] || !y[s] || n[s] <= 0 || ldy[s] < n[s]) return PCT_ERR_BAD_ARG;
     if (n[s] % 32) return PCT_ERR_UNSUPPORTED;
   }
-  const int rc = pct::launch_linear_k128_split_multi(x, ldx, x_add, ld_add, add_period, nseg, w, bias, n, use_add, y, ldy, rows,
-                                                     static_cast<hipStream_t>(stream));
-  return rc == -100 ? PCT_ERR_ALIGNMENT : (rc == -4 ? PCT_ERR_UNSUPPORTED : rc);
+  // (this launcher's PCT_NOT_COVERED: w[s], bias[s] or y[s] not 16-byte aligned or ldy[s] % 4 != 0, and no other kernel takes the call)
+  return abi_status(pct::launch_linear_k128_split_multi(x, ldx, x_add, ld_add, add_period, nseg, w, bias, n, use_add, y, ldy, rows,
+                                                        static_cast<hipStream_t>(stream)),
+                    PCT_ERR_ALIGNMENT);
 }
 
 int pct_linear_k128_add_layernorm_f32(const float *x, long long ldx, const float *w, const float *bias,
@@ -395,9 +349,8 @@ int pct_linear_add_layernorm_f32(const float *x, long long ldx, int k, const flo
   if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)w_split_ws | (uintptr_t)residual | (uintptr_t)out | (uintptr_t)bias |
         (uintptr_t)gamma | (uintptr_t)beta) & 15u) || (ldx & 3) || (ldr & 3) || (ldo & 3))
     return PCT_ERR_ALIGNMENT;
-  const int rc = pct::launch_linear_ln_split(x, ldx, w, static_cast<unsigned short *>(w_split_ws), k, bias, residual, ldr, gamma,
-                                             beta, eps, rows, out, ldo, static_cast<hipStream_t>(stream));
-  return rc == -4 ? PCT_ERR_UNSUPPORTED : rc;
+  return pct::launch_linear_ln_split(x, ldx, w, static_cast<unsigned short *>(w_split_ws), k, bias, residual, ldr, gamma, beta, eps,
+                                     rows, out, ldo, static_cast<hipStream_t>(stream));
 }
 
 int pct_groupnorm_flatten_f32(const float *x, const float *gamma, const float *beta, int batch, int channels, int hw,
@@ -421,9 +374,8 @@ int pct_conv1x1_nchw_f32(const float *x, const float *w, const float *bias, void
   if (!x || !w || !w_split_ws || !out) return PCT_ERR_BAD_ARG;
   if (out_channels != 128) return PCT_ERR_UNSUPPORTED;
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)w_split_ws | (uintptr_t)out | (uintptr_t)bias) & 15u) return PCT_ERR_ALIGNMENT;
-  const int rc = pct::launch_conv1x1_nchw_split(x, w, bias, static_cast<unsigned short *>(w_split_ws), batch, in_channels, hw, out,
-                                                static_cast<hipStream_t>(stream));
-  return rc == -4 ? PCT_ERR_UNSUPPORTED : rc;
+  return pct::launch_conv1x1_nchw_split(x, w, bias, static_cast<unsigned short *>(w_split_ws), batch, in_channels, hw, out,
+                                        static_cast<hipStream_t>(stream));
 }
 
 int pct_conv1x1_groupnorm_tokens_f32(const float *x, const float *w, const float *bias, void *w_split_ws, const float *gamma,
@@ -438,10 +390,9 @@ int pct_conv1x1_groupnorm_tokens_f32(const float *x, const float *w, const float
   if ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)w_split_ws | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)gamma | (uintptr_t)beta |
         (uintptr_t)partial_ws | (uintptr_t)stats) & 15u) || (out_batch_stride & 3) || (out_offset & 3))
     return PCT_ERR_ALIGNMENT;
-  const int rc = pct::launch_conv1x1_groupnorm_tokens(x, w, bias, static_cast<unsigned short *>(w_split_ws), gamma, beta, eps, batch,
-                                                      in_channels, hw, partial_ws, stats, out + out_offset, out_batch_stride,
-                                                      static_cast<hipStream_t>(stream));
-  return rc == -4 ? PCT_ERR_UNSUPPORTED : rc;
+  return pct::launch_conv1x1_groupnorm_tokens(x, w, bias, static_cast<unsigned short *>(w_split_ws), gamma, beta, eps, batch,
+                                              in_channels, hw, partial_ws, stats, out + out_offset, out_batch_stride,
+                                              static_cast<hipStream_t>(stream));
 }
 
 int pct_ffn_layernorm_f32(const float *x, long long ldx, const float *w1, const float *b1, const float *w2, const float *b2,
@@ -455,9 +406,8 @@ int pct_ffn_layernorm_f32(const float *x, long long ldx, const float *w1, const 
   if ((((uintptr_t)x | (uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)b2 | (uintptr_t)gamma | (uintptr_t)beta |
         (uintptr_t)w_image_ws | (uintptr_t)out) & 15u) || (ldx & 3) || (ldo & 3))
     return PCT_ERR_ALIGNMENT;
-  const int rc = pct::launch_ffn_fused_split(x, ldx, w1, b1, w2, b2, gamma, beta, eps, hidden, rows, w_image_ws, out, ldo,
-                                             static_cast<hipStream_t>(stream));
-  return rc == -4 ? PCT_ERR_UNSUPPORTED : rc;
+  return pct::launch_ffn_fused_split(x, ldx, w1, b1, w2, b2, gamma, beta, eps, hidden, rows, w_image_ws, out, ldo,
+                                     static_cast<hipStream_t>(stream));
 }
 
 int pct_lsap_f32(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
@@ -466,9 +416,7 @@ int pct_lsap_f32(const float *cost, int batch, int num_query, int ld_target, con
   if (batch < 0 || num_query <= 0 || ld_target <= 0) return PCT_ERR_BAD_ARG;
   if (batch == 0) return PCT_OK;
   if (!cost || !num_target || !row_for_target || !status) return PCT_ERR_BAD_ARG;
-  const int rc = pct::launch_lsap(cost, batch, num_query, ld_target, num_target, row_for_target, status,
-                                  static_cast<hipStream_t>(stream));
-  return rc == -4 ? PCT_ERR_UNSUPPORTED : rc;
+  return pct::launch_lsap(cost, batch, num_query, ld_target, num_target, row_for_target, status, static_cast<hipStream_t>(stream));
 }
 
 int pct_masked_attention_bf16(const void *q, const void *k, const void *vT, const unsigned char *mask, int batch,
@@ -486,8 +434,6 @@ int pct_masked_attention_bf16(const void *q, const void *k, const void *vT, cons
 
 int pct_prepare_device(void)
 {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)cap;
   const int a = pct::prepare_win_queue_device();
   const int b = pct::prepare_msda_backward_col_device();
   const int c = pct::prepare_ffn_device();
@@ -506,9 +452,8 @@ int pct_cross_attention_bf16(const void *q_content, const void *q_pos, const voi
   if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v) & 15u)
     return PCT_ERR_ALIGNMENT;
   if ((uintptr_t)out & 7u) return PCT_ERR_ALIGNMENT;
-  const int r = pct::launch_cross_attention(q_content, q_pos, k_content, k_pos, v, mask, mask ? row_open : nullptr, batch, heads,
-                                            num_query, num_key, scale, out, static_cast<hipStream_t>(stream));
-  return r == -100 ? PCT_ERR_UNSUPPORTED : r;
+  return abi_status(pct::launch_cross_attention(q_content, q_pos, k_content, k_pos, v, mask, mask ? row_open : nullptr, batch, heads,
+                                                num_query, num_key, scale, out, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -19,18 +19,11 @@
 // Workgroup = (image, 128 pixels), 4 waves = 2 x 2 blocks of 64 output channels x 64 pixels (4 MFMA tiles, 8 accumulators:
 // the a1w1 chain and the five small terms apart, as in the Linear kernels); x and W of step s + 1 are fetched into registers
 // while step s is multiplied, one barrier per step; 54 KB of LDS, two workgroups per CU.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 
-#include "attn_common.hpp"
+#include "attn_common.hpp"    // lds_read_tr16_b64; split_bf16.hpp
+#include "launchers.hpp"
 
 namespace pct {
-
-typedef float c1_f32x16 __attribute__((ext_vector_type(16)));
-typedef float c1_f32x4 __attribute__((ext_vector_type(4)));
-typedef float c1_f32x2 __attribute__((ext_vector_type(2)));
-typedef int c1_i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 c1_bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int C1_CO = 128;                 // output channels
 constexpr int C1_PT = 128;                 // pixels per workgroup
@@ -42,16 +35,6 @@ constexpr int C1_XBUF = 3 * C1_XPLANE;     // 15 360
 constexpr int C1_WPLANE = C1_CO * 32;      // 128 rows x 16 k x 2 B
 constexpr int C1_WBUF = 3 * C1_WPLANE;     // 12 288
 
-// (x, y) -> three packed bf16 pairs (low half = x's piece), x = x1 + x2 + x3 exactly (as linear_k128_split.hip)
-__device__ __forceinline__ void c1_split(const float x, const float y, unsigned &p1, unsigned &p2, unsigned &p3)
-{
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(c1_f32x2{x, y}, c1_bf16x2));
-  const float rx = x - __uint_as_float(p1 << 16), ry = y - __uint_as_float(p1 & 0xffff0000u);
-  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(c1_f32x2{rx, ry}, c1_bf16x2));
-  const float sx = rx - __uint_as_float(p2 << 16), sy = ry - __uint_as_float(p2 & 0xffff0000u);
-  p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(c1_f32x2{sx, sy}, c1_bf16x2));
-}
-
 // W [128][K] fp32 -> ws [K / 16][3][128][16] bf16 in the LDS image order (see the header): one thread per element pair
 __global__ __launch_bounds__(256) void conv1x1_split_weights_kernel(const float *__restrict__ w, const int K,
                                                                     unsigned short *__restrict__ ws)
@@ -60,7 +43,7 @@ __global__ __launch_bounds__(256) void conv1x1_split_weights_kernel(const float 
   if (e >= C1_CO * K) return;
   const int co = e / K, k = e - co * K;
   unsigned p1, p2, p3;
-  c1_split(w[e], w[e + 1], p1, p2, p3);
+  split_bf16x3(w[e], w[e + 1], p1, p2, p3);
   const int step = k / C1_KS, kk = k % C1_KS;
   const size_t base = (size_t)step * (C1_WBUF / 2) + (size_t)co * 16 + (size_t)((((kk >> 3) ^ ((co >> 3) & 1)) << 3) + (kk & 7));
   *reinterpret_cast<unsigned *>(ws + base) = p1;
@@ -97,27 +80,27 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
   const int sx_row = tid >> 4, sx_px = (tid & 15) * 8;
   const float *xsrc = xn + (size_t)sx_row * HW + sx_px;
   const int sx_off = sx_row * C1_XROW + sx_px * 2;
-  c1_f32x4 gx[2];
-  c1_i32x4 gw[3];
+  f32x4 gx[2];
+  i32x4 gw[3];
   auto fetch = [&](const int step) {
     const float *p = xsrc + (size_t)step * C1_KS * HW;
-    gx[0] = *reinterpret_cast<const c1_f32x4 *>(p);
-    gx[1] = *reinterpret_cast<const c1_f32x4 *>(p + 4);
-    const c1_i32x4 *wp = reinterpret_cast<const c1_i32x4 *>(ws + (size_t)step * (C1_WBUF / 2)) + tid;
+    gx[0] = *reinterpret_cast<const f32x4 *>(p);
+    gx[1] = *reinterpret_cast<const f32x4 *>(p + 4);
+    const i32x4 *wp = reinterpret_cast<const i32x4 *>(ws + (size_t)step * (C1_WBUF / 2)) + tid;
 #pragma unroll
     for (int i = 0; i < 3; ++i) gw[i] = wp[i * C1_BLOCK];
   };
   auto stash = [&](const int buf) {
     unsigned a[4], b[4], c[4];
-    c1_split(gx[0][0], gx[0][1], a[0], b[0], c[0]);
-    c1_split(gx[0][2], gx[0][3], a[1], b[1], c[1]);
-    c1_split(gx[1][0], gx[1][1], a[2], b[2], c[2]);
-    c1_split(gx[1][2], gx[1][3], a[3], b[3], c[3]);
+    split_bf16x3(gx[0][0], gx[0][1], a[0], b[0], c[0]);
+    split_bf16x3(gx[0][2], gx[0][3], a[1], b[1], c[1]);
+    split_bf16x3(gx[1][0], gx[1][1], a[2], b[2], c[2]);
+    split_bf16x3(gx[1][2], gx[1][3], a[3], b[3], c[3]);
     unsigned char *d = xs[buf] + sx_off;
-    *reinterpret_cast<c1_i32x4 *>(d) = c1_i32x4{(int)a[0], (int)a[1], (int)a[2], (int)a[3]};
-    *reinterpret_cast<c1_i32x4 *>(d + C1_XPLANE) = c1_i32x4{(int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-    *reinterpret_cast<c1_i32x4 *>(d + 2 * C1_XPLANE) = c1_i32x4{(int)c[0], (int)c[1], (int)c[2], (int)c[3]};
-    c1_i32x4 *wd = reinterpret_cast<c1_i32x4 *>(wsm[buf]) + tid;
+    *reinterpret_cast<i32x4 *>(d) = i32x4{(int)a[0], (int)a[1], (int)a[2], (int)a[3]};
+    *reinterpret_cast<i32x4 *>(d + C1_XPLANE) = i32x4{(int)b[0], (int)b[1], (int)b[2], (int)b[3]};
+    *reinterpret_cast<i32x4 *>(d + 2 * C1_XPLANE) = i32x4{(int)c[0], (int)c[1], (int)c[2], (int)c[3]};
+    i32x4 *wd = reinterpret_cast<i32x4 *>(wsm[buf]) + tid;
 #pragma unroll
     for (int i = 0; i < 3; ++i) wd[i * C1_BLOCK] = gw[i];
   };
@@ -139,7 +122,7 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
   for (int cb = 0; cb < 2; ++cb)
     b_off[cb] = (8 * (g16 >> 1) + q4) * C1_XROW + (px_half * 64 + cb * 32 + 16 * (g16 & 1) + 4 * pp) * 2;
 
-  c1_f32x16 acc_hi[2][2], acc_lo[2][2];
+  f32x16 acc_hi[2][2], acc_lo[2][2];
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -170,14 +153,8 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[rb][0], xb[cb][2], acc_lo[rb][cb], 0, 0, 0);
-        acc_hi[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[rb][0], xb[cb][0], acc_hi[rb][cb], 0, 0, 0);
-        acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[rb][2], xb[cb][0], acc_lo[rb][cb], 0, 0, 0);
-        acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[rb][1], xb[cb][1], acc_lo[rb][cb], 0, 0, 0);
-        acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[rb][0], xb[cb][1], acc_lo[rb][cb], 0, 0, 0);
-        acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[rb][1], xb[cb][0], acc_lo[rb][cb], 0, 0, 0);
-      }
+      for (int cb = 0; cb < 2; ++cb)
+        split_mfma6(wa[rb][0], wa[rb][1], wa[rb][2], xb[cb][0], xb[cb][1], xb[cb][2], acc_hi[rb][cb], acc_lo[rb][cb]);
     if (step + 1 < nsteps) stash(buf ^ 1);                       // (everyone left that buffer before the previous barrier)
     __syncthreads();
   }
@@ -192,15 +169,15 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
       const int co0 = co_half * 64 + rb * 32 + 4 * h;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const c1_f32x4 bq = bias ? *reinterpret_cast<const c1_f32x4 *>(bias + co0 + 8 * q) : c1_f32x4{0.f, 0.f, 0.f, 0.f};
-        c1_f32x4 v[2];
+        const f32x4 bq = bias ? *reinterpret_cast<const f32x4 *>(bias + co0 + 8 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 v[2];
         float sm = 0.f;
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
 #pragma unroll
           for (int t = 0; t < 4; ++t) v[cb][t] = (acc_hi[rb][cb][4 * q + t] + acc_lo[rb][cb][4 * q + t]) + bq[t];
           sm += (v[cb][0] + v[cb][1]) + (v[cb][2] + v[cb][3]);
-          *reinterpret_cast<c1_f32x4 *>(yn + (size_t)(px_half * 64 + cb * 32 + r) * C1_CO + co0 + 8 * q) = v[cb];
+          *reinterpret_cast<f32x4 *>(yn + (size_t)(px_half * 64 + cb * 32 + r) * C1_CO + co0 + 8 * q) = v[cb];
         }
         // the group's 256 values of this wave: 8 per lane over the 32 lanes of a half wave (same h)
 #pragma unroll
@@ -218,7 +195,7 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
         for (int o = 1; o < 32; o <<= 1) m2 += __shfl_xor(m2, o);
         if (r == 0) {
           const int g = co_half * 16 + rb * 8 + 2 * q + h;
-          *reinterpret_cast<c1_f32x2 *>(prec + 2 * g) = c1_f32x2{mean, m2};
+          *reinterpret_cast<f32x2 *>(prec + 2 * g) = f32x2{mean, m2};
         }
       }
     }
@@ -229,10 +206,10 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb) {
     const int co0 = co_half * 64 + rb * 32 + 4 * h;
-    c1_f32x4 bq[4];
+    f32x4 bq[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      bq[q] = bias ? *reinterpret_cast<const c1_f32x4 *>(bias + co0 + 8 * q) : c1_f32x4{0.f, 0.f, 0.f, 0.f};
+      bq[q] = bias ? *reinterpret_cast<const f32x4 *>(bias + co0 + 8 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
       float *dst = yn + px_half * 64 + cb * 32 + r;
@@ -280,22 +257,22 @@ __global__ __launch_bounds__(256) void gn_apply_tokens_kernel(float *__restrict_
   if (i >= (long long)HW * 32) return;
   const int g = (int)(i & 31);
   const float mean = stats[2 * (n * 32 + g)], rstd = stats[2 * (n * 32 + g) + 1];
-  const c1_f32x4 ga = *reinterpret_cast<const c1_f32x4 *>(gamma + 4 * g), be = *reinterpret_cast<const c1_f32x4 *>(beta + 4 * g);
-  c1_f32x4 *p = reinterpret_cast<c1_f32x4 *>(y + (size_t)n * y_batch_stride) + i;
-  const c1_f32x4 v = *p;
-  c1_f32x4 o;
+  const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + 4 * g), be = *reinterpret_cast<const f32x4 *>(beta + 4 * g);
+  f32x4 *p = reinterpret_cast<f32x4 *>(y + (size_t)n * y_batch_stride) + i;
+  const f32x4 v = *p;
+  f32x4 o;
 #pragma unroll
   for (int t = 0; t < 4; ++t) o[t] = (v[t] - mean) * rstd * ga[t] + be[t];
   *p = o;
 }
 
-// -4: geometry not covered (the caller keeps the library convolution)
+// PCT_ERR_UNSUPPORTED: geometry not covered (the caller keeps the library convolution)
 int launch_conv1x1_nchw_split(const float *x, const float *w, const float *bias, unsigned short *w_split_ws, int N, int K, int HW,
                               float *y, hipStream_t stream)
 {
   if (N == 0) return 0;
-  if (K % C1_KS != 0 || HW % C1_PT != 0 || K <= 0) return -4;
-  if ((long long)N * (HW / C1_PT) >= 0x7fffffffLL) return -4;
+  if (K % C1_KS != 0 || HW % C1_PT != 0 || K <= 0) return PCT_ERR_UNSUPPORTED;
+  if ((long long)N * (HW / C1_PT) >= 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(conv1x1_split_weights_kernel, dim3((unsigned)((C1_CO * K / 2 + 255) / 256)), dim3(256), 0, stream, w, K,
                      w_split_ws);
   hipLaunchKernelGGL(conv1x1_nchw_split_kernel<false>, dim3((unsigned)(N * (HW / C1_PT))), dim3(C1_BLOCK), 0, stream, x, w_split_ws,
@@ -310,8 +287,8 @@ int launch_conv1x1_groupnorm_tokens(const float *x, const float *w, const float 
                                     float *out, long long out_batch_stride, hipStream_t stream)
 {
   if (N == 0) return 0;
-  if (K % C1_KS != 0 || HW % C1_PT != 0 || K <= 0) return -4;
-  if ((long long)N * (HW / C1_PT) >= 0x7fffffffLL || N > 65535) return -4;
+  if (K % C1_KS != 0 || HW % C1_PT != 0 || K <= 0) return PCT_ERR_UNSUPPORTED;
+  if ((long long)N * (HW / C1_PT) >= 0x7fffffffLL || N > 65535) return PCT_ERR_UNSUPPORTED;
   const int tiles = HW / C1_PT;
   hipLaunchKernelGGL(conv1x1_split_weights_kernel, dim3((unsigned)((C1_CO * K / 2 + 255) / 256)), dim3(256), 0, stream, w, K,
                      w_split_ws);

@@ -24,6 +24,7 @@
 //   * the two workgroups of an (image, head group) -- query tiles 0-3 and 4-6 at 100 queries -- sit next to each other in
 //     the XCD-chunked block order, so the second one finds the K / V lines in L2.
 #include "attn_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -205,19 +206,19 @@ __global__ __launch_bounds__(256, 2) void cross_attention_kernel(const __bf16 *_
   else cross_attention_body<HAS_MASK, 1>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, scale, tgroups, out);
 }
 
-// -100: geometry not covered (the caller concatenates the halves and uses pct_masked_attention_bf16)
+// PCT_NOT_COVERED: geometry not covered (the caller concatenates the halves and uses pct_masked_attention_bf16)
 int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
                            const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S,
                            float scale, void *out, hipStream_t stream)
 {
-  if (heads <= 0 || heads % XA_HG != 0 || S <= 0 || S % XA_CH != 0) return -100;
+  if (heads <= 0 || heads % XA_HG != 0 || S <= 0 || S % XA_CH != 0) return PCT_NOT_COVERED;
   if (N == 0 || Q == 0) return 0;
-  if ((long long)S * N * heads * 16 >= 0x7fffffffLL) return -100;
-  if ((((uintptr_t)q_c | (uintptr_t)q_s | (uintptr_t)k_c | (uintptr_t)k_p | (uintptr_t)v) & 15u) || ((uintptr_t)out & 7u)) return -100;
-  if (mask && (((uintptr_t)mask & 15u) || (S & 15))) return -100;
+  if ((long long)S * N * heads * 16 >= 0x7fffffffLL) return PCT_NOT_COVERED;
+  if ((((uintptr_t)q_c | (uintptr_t)q_s | (uintptr_t)k_c | (uintptr_t)k_p | (uintptr_t)v) & 15u) || ((uintptr_t)out & 7u)) return PCT_NOT_COVERED;
+  if (mask && (((uintptr_t)mask & 15u) || (S & 15))) return PCT_NOT_COVERED;
   const int qtiles = (Q + 15) / 16, tgroups = (qtiles + XA_T - 1) / XA_T;
   const long long nblk = (long long)N * (heads / XA_HG) * tgroups;
-  if (nblk > 0x7fffffffLL) return -100;
+  if (nblk > 0x7fffffffLL) return PCT_NOT_COVERED;
   const dim3 grid((unsigned)nblk), block(256);
   const __bf16 *qc = static_cast<const __bf16 *>(q_c), *qs = static_cast<const __bf16 *>(q_s);
   const __bf16 *kc = static_cast<const __bf16 *>(k_c), *kp = static_cast<const __bf16 *>(k_p);

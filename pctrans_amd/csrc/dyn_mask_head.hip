@@ -19,6 +19,7 @@
 // inputs/outputs to bf16 -- with OutT = bf16 the logits are rounded to bf16 where the reference's conv output is,
 // and the sigmoid threshold is evaluated on bf16-rounded values like torch's bf16 kernels do).
 #include "msda_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -220,17 +221,17 @@ int launch_dyn_mask_head(const float *feat, const float *ref, const float *param
                          int stride, int rel_coord, int th, int tw, int out_dtype, void *up, unsigned char *amask,
                          hipStream_t stream)
 {
-  if (C != 16) return -4;
+  if (C != 16) return PCT_ERR_UNSUPPORTED;
   if ((long long)N * Q == 0 || H == 0 || W == 0) return 0;
   // rows per band: enough blocks to fill the chip several times over, LDS tile <= 48 KB
   int TR = H;
   const int max_rows = (48 * 1024 - 16) / (W * 4) - 2;
-  if (max_rows < 1) return -4;
+  if (max_rows < 1) return PCT_ERR_UNSUPPORTED;
   if (TR > max_rows) TR = max_rows;
   while (TR > 8 && (long long)N * Q * ((H + TR - 1) / TR) < 4096) TR = (TR + 1) / 2;
   const int nbands = (H + TR - 1) / TR;
   const long long nblk = (long long)N * Q * nbands;
-  if (nblk > 0x7fffffffLL) return -4;
+  if (nblk > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   const size_t lds = ((size_t)(TR + 2) * W + 4) * sizeof(float);   // + dummy slot for tail lanes
   const dim3 grid((unsigned)nblk), block(DMH_BLOCK);
 #define PCT_DMH(REL_, OUT_)                                                                                   \
@@ -243,7 +244,7 @@ int launch_dyn_mask_head(const float *feat, const float *ref, const float *param
     if (rel_coord) PCT_DMH(true, __bf16);
     else PCT_DMH(false, __bf16);
   } else {
-    return -1;
+    return PCT_ERR_BAD_ARG;
   }
 #undef PCT_DMH
   return (int)hipGetLastError();

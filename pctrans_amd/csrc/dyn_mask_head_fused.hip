@@ -21,6 +21,7 @@
 //     inside one lane's pixels and in two rows a wave holds (its own pair, or the row above + its first row).
 #include "dmh_common.hpp"
 #include "msda_win_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -204,19 +205,19 @@ __global__ __launch_bounds__(256, FZ_WGS) void dmh_fused_kernel(const float *__r
   }
 }
 
-// -100: geometry not covered (the caller runs the two-launch path).  `workspace`: N * ceil(Q / 2) * 5120 bytes, 16-byte aligned.
+// PCT_NOT_COVERED: geometry not covered (the caller runs the two-launch path).  `workspace`: N * ceil(Q / 2) * 5120 bytes, 16-byte aligned.
 int launch_dyn_mask_head_fused(const float *feat, const float *ref, const float *params, int N, int C, int Q, int H, int W,
                                int stride, int rel_coord, int th, int tw, void *workspace, void *up, unsigned char *amask,
                                hipStream_t stream)
 {
-  if (C != DMH_C || W != FZ_W || H < FZ_BAND || (H % FZ_BAND) != 0) return -100;
-  if (th <= 0 || tw <= 0 || H % th != 0 || W % tw != 0 || H / th != W / tw) return -100;
+  if (C != DMH_C || W != FZ_W || H < FZ_BAND || (H % FZ_BAND) != 0) return PCT_NOT_COVERED;
+  if (th <= 0 || tw <= 0 || H % th != 0 || W % tw != 0 || H / th != W / tw) return PCT_NOT_COVERED;
   const int sc = H / th;
-  if (sc != 2 && sc != 4 && sc != 8) return -100;
+  if (sc != 2 && sc != 4 && sc != 8) return PCT_NOT_COVERED;
   const int npairs = (Q + 1) / 2;
-  if ((long long)N * (H / FZ_BAND) > 0x7fffffffLL || (long long)N * npairs > 0x7fffffffLL) return -100;
-  if (((uintptr_t)up & 15u) || ((uintptr_t)amask & 3u) || ((uintptr_t)workspace & 15u)) return -100;
-  if (sc == 2 && (((size_t)(H / 2) * (W / 2)) & 3u)) return -100;          // 4-byte mask stores
+  if ((long long)N * (H / FZ_BAND) > 0x7fffffffLL || (long long)N * npairs > 0x7fffffffLL) return PCT_NOT_COVERED;
+  if (((uintptr_t)up & 15u) || ((uintptr_t)amask & 3u) || ((uintptr_t)workspace & 15u)) return PCT_NOT_COVERED;
+  if (sc == 2 && (((size_t)(H / 2) * (W / 2)) & 3u)) return PCT_NOT_COVERED;          // 4-byte mask stores
   unsigned *ws = static_cast<unsigned *>(workspace);
   if (rel_coord)
     hipLaunchKernelGGL(dmh_prepare_kernel<true>, dim3((unsigned)(N * npairs)), dim3(64), 0, stream, params, ref, Q, H, W, stride, ws);

@@ -16,6 +16,7 @@
 // Under autocast the reference's convolutions take bf16 inputs/weights with fp32 accumulation and emit bf16; here the
 // hidden activations are likewise rounded to bf16 between layers 0 and 1 and the logits are stored as bf16.
 #include "dmh_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -195,7 +196,7 @@ int launch_dyn_mask_head_mfma(const float *feat, const float *ref, const float *
                               int W, int stride, int rel_coord, int th, int tw, void *scratch, void *up,
                               unsigned char *amask, hipStream_t stream)
 {
-  if (C != 16) return -4;
+  if (C != 16) return PCT_ERR_UNSUPPORTED;
   if ((long long)N * Q == 0 || H == 0 || W == 0) return 0;
   const int HW = H * W;
   const int px_per_block = (DMM_BLOCK / 64) * DMM_PT * 16;
@@ -212,12 +213,12 @@ int launch_dyn_mask_head_mfma(const float *feat, const float *ref, const float *
 
   int TR = H;
   const int max_rows = (16 * 1024) / (W * 4) - 2;                 // <= 16 KB of LDS per block: many blocks per CU
-  if (max_rows < 1) return -4;
+  if (max_rows < 1) return PCT_ERR_UNSUPPORTED;
   if (TR > max_rows) TR = max_rows;
   while (TR > 8 && (long long)N * Q * ((H + TR - 1) / TR) < 4096) TR = (TR + 1) / 2;
   const int nbands = (H + TR - 1) / TR;
   const long long nblk = (long long)N * Q * nbands;
-  if (nblk > 0x7fffffffLL) return -4;
+  if (nblk > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(dmh_resize_kernel, dim3((unsigned)nblk), dim3(256), (size_t)(TR + 2) * W * sizeof(float), stream, lg,
                      H, W, TR, nbands, th, tw, static_cast<__bf16 *>(up), amask);
   return (int)hipGetLastError();

@@ -23,20 +23,13 @@
 //   * a tile's LayerNorm and stores run under the next tile's first product;
 //   * the row statistics of the LayerNorm are complete inside a wave (a lane and its partner in the other half hold a row's 128
 //     columns).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
 #include "msda_win_common.hpp"    // func_attr_per_device
+#include "launchers.hpp"
+#include "split_bf16.hpp"
 
 namespace pct {
-
-typedef float ff_f32x16 __attribute__((ext_vector_type(16)));
-typedef float ff_f32x4 __attribute__((ext_vector_type(4)));
-typedef float ff_f32x2 __attribute__((ext_vector_type(2)));
-typedef int ff_i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 ff_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ff_bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int FF_BLOCK = 256;
 constexpr int FF_BM = 128;                        // rows per workgroup tile
@@ -53,24 +46,16 @@ constexpr int FF_HALF = FF_PIECES / 2;                  // 7
 constexpr int FF_LDS = 2 * FF_STAGE + 3 * FF_D * 4;     // two stages, then b2, gamma, beta
 constexpr int FF_B1OFF = 56832;                         // the chunk's 32 biases, in the padding
 
-__device__ __forceinline__ void ff_split(const float x, const float y, unsigned &p1, unsigned &p2, unsigned &p3)
-{
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(ff_f32x2{x, y}, ff_bf16x2));
-  const float rx = x - __uint_as_float(p1 << 16), ry = y - __uint_as_float(p1 & 0xffff0000u);   // exact
-  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(ff_f32x2{rx, ry}, ff_bf16x2));
-  const float sx = rx - __uint_as_float(p2 << 16), sy = ry - __uint_as_float(p2 & 0xffff0000u); // exact
-  p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(ff_f32x2{sx, sy}, ff_bf16x2));
-}
 // eight consecutive floats -> three bf16x8 pieces
-__device__ __forceinline__ void ff_split8(const ff_f32x4 a, const ff_f32x4 b, ff_bf16x8 (&out)[3])
+__device__ __forceinline__ void ff_split8(const f32x4 a, const f32x4 b, bf16x8 (&out)[3])
 {
   unsigned p[3][4];
-  ff_split(a[0], a[1], p[0][0], p[1][0], p[2][0]);
-  ff_split(a[2], a[3], p[0][1], p[1][1], p[2][1]);
-  ff_split(b[0], b[1], p[0][2], p[1][2], p[2][2]);
-  ff_split(b[2], b[3], p[0][3], p[1][3], p[2][3]);
+  split_bf16x3(a[0], a[1], p[0][0], p[1][0], p[2][0]);
+  split_bf16x3(a[2], a[3], p[0][1], p[1][1], p[2][1]);
+  split_bf16x3(b[0], b[1], p[0][2], p[1][2], p[2][2]);
+  split_bf16x3(b[2], b[3], p[0][3], p[1][3], p[2][3]);
 #pragma unroll
-  for (int q = 0; q < 3; ++q) out[q] = __builtin_bit_cast(ff_bf16x8, ff_i32x4{(int)p[q][0], (int)p[q][1], (int)p[q][2], (int)p[q][3]});
+  for (int q = 0; q < 3; ++q) out[q] = __builtin_bit_cast(bf16x8, i32x4{(int)p[q][0], (int)p[q][1], (int)p[q][2], (int)p[q][3]});
 }
 
 // W1 [F][128], W2 [128][F], b1 [F] fp32 -> img [F / 32][FF_STAGE bytes]: image c holds W2 and b1 of chunk c and W1 of chunk c + 1
@@ -85,7 +70,7 @@ __global__ __launch_bounds__(256) void ffn_split_weights_kernel(const float *__r
   unsigned p1, p2, p3;
   if (e < n1) {                                                   // W1[u][k], k even: row u % 32, k-contiguous
     const int u = (int)(e / FF_D), k = (int)(e - (long long)u * FF_D);
-    ff_split(w1[e], w1[e + 1], p1, p2, p3);
+    split_bf16x3(w1[e], w1[e + 1], p1, p2, p3);
     const int c = (u / FF_CH + nch - 1) % nch;
     unsigned short *d = img + (size_t)c * (FF_STAGE / 2) + (size_t)(u % FF_CH) * (FF_W1ROW / 2) + k;
     *reinterpret_cast<unsigned *>(d) = p1;
@@ -94,7 +79,7 @@ __global__ __launch_bounds__(256) void ffn_split_weights_kernel(const float *__r
   } else if (e < 2 * n1) {                                        // W2[c][u], u even: chunk u / 32, row c, slot of u in the chunk
     const long long e2 = e - n1;
     const int c = (int)(e2 / F), u = (int)(e2 - (long long)c * F);
-    ff_split(w2[e2], w2[e2 + 1], p1, p2, p3);
+    split_bf16x3(w2[e2], w2[e2 + 1], p1, p2, p3);
     const int uu = u % FF_CH;                                     // 0 .. 31 (even): s = uu / 16, inside: v = uu % 16
     const int s = uu >> 4, v = uu & 15;
     // hidden 16 s + v with v = 8 g + 4 h + t (g = 0, 1; h = 0, 1; t = 0 .. 3) sits in slot (h, e = 4 g + t) of k-step s:
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 
   // a tile's rows of x are requested one tile ahead (under GEMM 2 of the last chunk of the tile before, when the fragments of the
   // current rows are no longer needed; a row-strided load touches 32 lines: 16 of them back to back cost 3 k cycles): lane (r, h) takes k = 16 s + 8 h .. + 7 of row r, s = 0 .. 7
-  ff_i32x4 xraw[16];
+  i32x4 xraw[16];
   auto x_request = [&](const long long tile, const int s0, const int s1) {      // k-steps s0 .. s1 - 1
     const long long row0 = tile * FF_BM + 32 * wave;
     const long long left = M - row0;
@@ -186,18 +171,20 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 
   // GEMM 1: D1[hidden 8 q + 4 h + t][row r] over k = 128 from the W1 part of stage `st`.  One wave per SIMD: nobody else covers an
   // LDS round trip, so the fragments of k-step s + 1 are requested before the MFMAs of step s
-  ff_bf16x8 xp[8][3];                                             // this wave's 32 rows of x as GEMM 1's B fragments
-  ff_f32x16 h_hi, h_lo;
-  ff_bf16x8 wa[2][3];
+  bf16x8 xp[8][3];                                             // this wave's 32 rows of x as GEMM 1's B fragments
+  f32x16 h_hi, h_lo;
+  bf16x8 wa[2][3];
   auto split_x = [&](const int s) {
-    ff_split8(__builtin_bit_cast(ff_f32x4, xraw[2 * s]), __builtin_bit_cast(ff_f32x4, xraw[2 * s + 1]), xp[s]);
+    ff_split8(__builtin_bit_cast(f32x4, xraw[2 * s]), __builtin_bit_cast(f32x4, xraw[2 * s + 1]), xp[s]);
   };
   auto w1_frags = [&](const unsigned char *st, const int s) {
 #pragma unroll
-    for (int p = 0; p < 3; ++p) wa[s & 1][p] = *reinterpret_cast<const ff_bf16x8 *>(st + w1_off + 32 * s + p * FF_W1PLANE);
+    for (int p = 0; p < 3; ++p) wa[s & 1][p] = *reinterpret_cast<const bf16x8 *>(st + w1_off + 32 * s + p * FF_W1PLANE);
   };
   auto gemm1_step = [&](const int s) {
-    const ff_bf16x8 a1 = wa[s & 1][0], a2 = wa[s & 1][1], a3 = wa[s & 1][2];
+    const bf16x8 a1 = wa[s & 1][0], a2 = wa[s & 1][1], a3 = wa[s & 1][2];
+    // split_mfma6(a1, a2, a3, xp[s], h_hi, h_lo) written out, here and in phase B: through the shared function this kernel's
+    // schedule and register allocation come out different (the MFMAs are interleaved by hand below), the other GEMMs' do not
     h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][2], h_lo, 0, 0, 0);
     h_hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, xp[s][0], h_hi, 0, 0, 0);
     h_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, xp[s][0], h_lo, 0, 0, 0);
@@ -244,19 +231,19 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
     const long long left = M - row0;
     const unsigned xbytes = (unsigned)((left < 32 ? (left < 0 ? 0 : left) : 32) * ldx * 4);
     const auto xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(X + row0 * ldx), 0, (int)xbytes, 0x00020000);
-    ff_f32x16 y_hi[4], y_lo[4];                                   // D2[col block][cols 32][rows 32]
+    f32x16 y_hi[4], y_lo[4];                                   // D2[col block][cols 32][rows 32]
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
       for (int j = 0; j < 16; ++j) y_hi[cb][j] = y_lo[cb][j] = 0.f;
-    ff_f32x4 res[16];                                             // the residual: columns 32 cb + 8 q + 4 h .. + 3 of row r, [4 cb + q]
+    f32x4 res[16];                                             // the residual: columns 32 cb + 8 q + 4 h .. + 3 of row r, [4 cb + q]
 
     // entering iteration `chunk`: wa[0] = step 0 of the W1 fragments and bq = the biases it needs, the W2 / bias pieces of image
     // chunk + 1 on their way
-    ff_f32x4 bq[4];
+    f32x4 bq[4];
     auto load_bias = [&](const unsigned char *st) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const ff_f32x4 *>(st + FF_B1OFF + (8 * q + 4 * h) * 4);
+      for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const f32x4 *>(st + FF_B1OFF + (8 * q + 4 * h) * 4);
     };
     w1_frags(ff_smem + cur * FF_STAGE, 0);
     load_bias(ff_smem + cur * FF_STAGE);
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
       unsigned char *nst = ff_smem + (cur ^ 1) * FF_STAGE;        // nobody reads it since the previous barrier: image chunk + 1
       const int nxt = LAST ? 0 : chunk + 1, nxt2 = (chunk + 2) % nch;
       // this chunk's hidden accumulators move to the vector side; the same registers then take the next chunk's product
-      const ff_f32x16 c_hi = h_hi, c_lo = h_lo;
+      const f32x16 c_hi = h_hi, c_lo = h_lo;
       if constexpr (!LAST) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) h_hi[j] = h_lo[j] = 0.f;
@@ -280,15 +267,15 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
       // 6.545 -> 6.525 ms against one per step in steps 0 - 6).  The last chunk (no product here) requests the tile's residual rows
       // in steps 0 - 5: the barrier's wait, which leaves only the x loads of phase B in flight, retires them ---------------------
       unsigned hpw[2][3][4];
-      ff_bf16x8 wb[2][3], wc[3];
+      bf16x8 wb[2][3], wc[3];
       auto valu_slice = [&](const int m) {
         const int sg = m >> 2, w = m & 3, q = 2 * sg + (w >> 1), t0 = 2 * (w & 1), j0 = 4 * q + t0;
         const float v0 = fmaxf((c_hi[j0] + c_lo[j0]) + bq[q][t0], 0.f);
         const float v1 = fmaxf((c_hi[j0 + 1] + c_lo[j0 + 1]) + bq[q][t0 + 1], 0.f);
-        ff_split(v0, v1, hpw[sg][0][w], hpw[sg][1][w], hpw[sg][2][w]);
+        split_bf16x3(v0, v1, hpw[sg][0][w], hpw[sg][1][w], hpw[sg][2][w]);
       };
       auto h_frag = [&](const int sg, const int p) {
-        return __builtin_bit_cast(ff_bf16x8, ff_i32x4{(int)hpw[sg][p][0], (int)hpw[sg][p][1], (int)hpw[sg][p][2], (int)hpw[sg][p][3]});
+        return __builtin_bit_cast(bf16x8, i32x4{(int)hpw[sg][p][0], (int)hpw[sg][p][1], (int)hpw[sg][p][2], (int)hpw[sg][p][3]});
       };
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
@@ -298,14 +285,14 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
         }
         if (s == 7) {
 #pragma unroll
-          for (int p = 0; p < 3; ++p) wb[0][p] = *reinterpret_cast<const ff_bf16x8 *>(st + w2_off + p * FF_W2PLANE);
+          for (int p = 0; p < 3; ++p) wb[0][p] = *reinterpret_cast<const bf16x8 *>(st + w2_off + p * FF_W2PLANE);
         }
         if (s & 1) valu_slice(s >> 1);
         if constexpr (LAST) {
           if (s < 6) {
 #pragma unroll
             for (int i = s < 4 ? 3 * s : 2 * s + 4; i < (s < 4 ? 3 * s + 3 : 2 * s + 6); ++i)     // column 8 i + 4 h
-              res[i] = __builtin_bit_cast(ff_f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)((r * ldx + 4 * h) * 4), 32 * i, 0));
+              res[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, (int)((r * ldx + 4 * h) * 4), 32 * i, 0));
           }
         }
         if (s < 3) {
@@ -330,10 +317,10 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
       // group 6, so the chunk's barrier sits after group 5, behind the wait that retires image chunk + 1's DMAs: groups 6 and 7 cover
       // it, the first reads of the next iteration and the W2 / bias pieces of image chunk + 2 into the stage just read (the last
       // chunk leaves them to the next tile's first product: no DMA is in flight in the epilogue, whose loads then have counted waits)
-      auto w2_frags = [&](ff_bf16x8 (&dst)[3], const int g) {
+      auto w2_frags = [&](bf16x8 (&dst)[3], const int g) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-          dst[p] = *reinterpret_cast<const ff_bf16x8 *>(st + w2_off + (g & 3) * 32 * FF_W2ROW + 32 * (g >> 2) + p * FF_W2PLANE);
+          dst[p] = *reinterpret_cast<const bf16x8 *>(st + w2_off + (g & 3) * 32 * FF_W2ROW + 32 * (g >> 2) + p * FF_W2PLANE);
       };
 #pragma unroll
       for (int g = 0; g < 8; ++g) {
@@ -356,7 +343,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 #pragma unroll
             for (int p = FF_HALF + 4; p < FF_PIECES; ++p) t_dma(p, nxt2, const_cast<unsigned char *>(st));
         }
-        const ff_bf16x8 a1 = g == 7 ? wc[0] : wb[g & 1][0], a2 = g == 7 ? wc[1] : wb[g & 1][1], a3 = g == 7 ? wc[2] : wb[g & 1][2];
+        const bf16x8 a1 = g == 7 ? wc[0] : wb[g & 1][0], a2 = g == 7 ? wc[1] : wb[g & 1][1], a3 = g == 7 ? wc[2] : wb[g & 1][2];
         y_lo[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, h_frag(sg, 2), y_lo[cb], 0, 0, 0);
         y_hi[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, h_frag(sg, 0), y_hi[cb], 0, 0, 0);
         y_lo[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, h_frag(sg, 0), y_lo[cb], 0, 0, 0);
@@ -397,7 +384,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c0 = 32 * cb + 8 * q + 4 * h;
-        const ff_f32x4 bb = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + c0 * 4);
+        const f32x4 bb = *reinterpret_cast<const f32x4 *>(ff_smem + 2 * FF_STAGE + c0 * 4);
 #pragma unroll
         for (int t = 0; t < 4; ++t) v[16 * cb + 4 * q + t] = ((y_hi[cb][4 * q + t] + y_lo[cb][4 * q + t]) + bb[t]) + res[4 * cb + q][t];
       }
@@ -426,13 +413,13 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c0 = 32 * cb + 8 * q + 4 * h;
-          const ff_f32x4 gq = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + (FF_D + c0) * 4);
-          const ff_f32x4 eq = *reinterpret_cast<const ff_f32x4 *>(ff_smem + 2 * FF_STAGE + (2 * FF_D + c0) * 4);
-          ff_f32x4 o;
+          const f32x4 gq = *reinterpret_cast<const f32x4 *>(ff_smem + 2 * FF_STAGE + (FF_D + c0) * 4);
+          const f32x4 eq = *reinterpret_cast<const f32x4 *>(ff_smem + 2 * FF_STAGE + (2 * FF_D + c0) * 4);
+          f32x4 o;
 #pragma unroll
           for (int t = 0; t < 4; ++t) o[t] = v[16 * cb + 4 * q + t] * rstd * gq[t] + eq[t];
           // (y rows with the non-temporal hint: 6.79 -> 6.97 ms)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ff_i32x4, o), yr, (int)((r * ldy + 4 * h) * 4), 4 * (c0 - 4 * h), 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), yr, (int)((r * ldy + 4 * h) * 4), 4 * (c0 - 4 * h), 0);
         }
       }
     };
@@ -444,18 +431,18 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
 }
 
 // the kernel's LDS attribute for the current device, outside any stream capture (pct_prepare_device)
-int prepare_ffn_device() { return func_attr_per_device(reinterpret_cast<const void *>(&ffn_fused_split_kernel), FF_LDS) == hipSuccess ? 0 : -4; }
+int prepare_ffn_device() { return func_attr_per_device(reinterpret_cast<const void *>(&ffn_fused_split_kernel), FF_LDS) == hipSuccess ? 0 : PCT_ERR_UNSUPPORTED; }
 
-// img_ws: (F / 32) * 57 344 bytes, 16-byte aligned, refilled on every call.  -4: geometry not covered.
+// img_ws: (F / 32) * 57 344 bytes, 16-byte aligned, refilled on every call.  PCT_ERR_UNSUPPORTED: geometry not covered.
 int launch_ffn_fused_split(const float *x, long long ldx, const float *w1, const float *b1, const float *w2, const float *b2,
                            const float *gamma, const float *beta, float eps, int F, long long rows, void *img_ws, float *out,
                            long long ldo, hipStream_t stream)
 {
   if (rows <= 0) return 0;
-  if (F <= 0 || F % FF_CH) return -4;
-  if ((long long)(F / FF_CH) * FF_STAGE > 0x7fffffffLL) return -4;
-  if (32LL * (ldx > ldo ? ldx : ldo) * 4 > 0x7fffffffLL) return -4;
-  if (func_attr_per_device(reinterpret_cast<const void *>(&ffn_fused_split_kernel), FF_LDS) != hipSuccess) return -4;
+  if (F <= 0 || F % FF_CH) return PCT_ERR_UNSUPPORTED;
+  if ((long long)(F / FF_CH) * FF_STAGE > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
+  if (32LL * (ldx > ldo ? ldx : ldo) * 4 > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
+  if (func_attr_per_device(reinterpret_cast<const void *>(&ffn_fused_split_kernel), FF_LDS) != hipSuccess) return PCT_ERR_UNSUPPORTED;
   const long long pairs = (long long)F * FF_D + F / 2;            // element pairs of both matrices and the bias
   hipLaunchKernelGGL(ffn_split_weights_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, stream, w1, w2, b1, F,
                      static_cast<unsigned short *>(img_ws));

@@ -11,6 +11,7 @@
 //     channel, transpose through a padded LDS tile, 512-B coalesced writes along the channels of every pixel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -101,7 +102,7 @@ int launch_groupnorm_flatten(const float *x, const float *gamma, const float *be
                              hipStream_t stream)
 {
   if (N == 0 || HW == 0) return 0;
-  if (C != 128 || groups <= 0 || C % groups) return -4;
+  if (C != 128 || groups <= 0 || C % groups) return PCT_ERR_UNSUPPORTED;
   const long long count = (long long)(C / groups) * HW;
   hipLaunchKernelGGL(gn_stats_kernel, dim3((unsigned)(N * groups)), dim3(GN_BLOCK), 0, stream, x, count, eps, stats);
   hipLaunchKernelGGL(gn_apply_flatten_kernel, dim3((unsigned)((HW + 63) / 64), (unsigned)N), dim3(GN_BLOCK), 0, stream, x,

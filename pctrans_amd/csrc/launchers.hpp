@@ -1,0 +1,126 @@
+// The host side of the library in one place: the single declaration of every launcher, device-preparation and kernel-choice
+// function that crosses a translation unit, and the status and kernel-id names they speak in.  Every file that defines or
+// calls one of them includes this header, so a definition that drifts from its declaration fails to compile in its own file.
+//
+// Status convention.  A launcher returns 0 on success, a positive hipError_t from the launch, or a negative status.  A negative
+// status is one of the PCT_ERR_* names of include/pctrans_hip.h, with one exception that never crosses the C ABI:
+// PCT_NOT_COVERED, "this kernel does not cover the call, try the next one", which the routers consume and c_abi.hip
+// translates (abi_status) where a launcher without a fallback hands it up.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/pctrans_hip.h"
+
+namespace pct {
+
+constexpr int PCT_NOT_COVERED = -100;
+
+// MSDeformAttn kernel ids: what pct_msda_set_kernel_choice / pct_msda_set_bwd_kernel_choice take (AUTO = follow the routing)
+// and pct_msda_last_kernel / pct_msda_last_bwd_kernel report.  The numbers are part of the ABI's diagnostics.
+enum MsdaFwdKernel { MSDA_FWD_AUTO = 0, MSDA_FWD_WIN = 1, MSDA_FWD_GENERIC = 2, MSDA_FWD_QUAD = 3, MSDA_FWD_COL = 4 };
+enum MsdaBwdKernel { MSDA_BWD_AUTO = 0, MSDA_BWD_WIN = 1, MSDA_BWD_GENERIC = 2, MSDA_BWD_COL = 3 };
+
+// ---- MSDeformAttn forward (msda_forward*.hip).  ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits,
+// ref = reference points, images ref_batch_stride floats apart).  The specialised kernels return PCT_NOT_COVERED for a
+// geometry they do not cover -------------------------------------------------------------------------------------------
+template <typename T>
+int launch_msda_forward(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn, int N,
+                        int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream);
+template <typename T>
+int launch_msda_forward_special(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
+                                const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream,
+                                const float *ref, long long ref_batch_stride);
+int launch_msda_forward_planes(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
+                               int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
+                               long long ref_batch_stride);
+template <typename T>
+int launch_msda_forward_win(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
+                            int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
+                            long long ref_batch_stride);
+template <typename T>
+int launch_msda_forward_dpp(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
+                            int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
+                            long long ref_batch_stride);
+int launch_msda_forward_col(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
+                            int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
+                            long long ref_batch_stride, bool planes);
+template <typename T>
+int launch_msda_forward_col16(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
+                              int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
+                              long long ref_batch_stride);
+void set_msda_kernel_choice(int v);     // a MsdaFwdKernel; anything else: follow PCT_MSDA_KERNEL
+int msda_kernel_choice();
+void note_msda_kernel(int k);
+int msda_last_kernel();
+
+// ---- MSDeformAttn backward (msda_backward*.hip) ------------------------------------------------------------------------
+template <typename A>
+int launch_msda_backward(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
+                         const void *grad_out, int N, int S, int M, int D, int L, int Lq, int P, void *grad_value, void *grad_loc,
+                         void *grad_attn, hipStream_t stream);
+int launch_msda_backward_win(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
+                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
+                             float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream);
+int launch_msda_backward_col(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
+                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
+                             float *grad_value, float *grad_loc, float *grad_attn, bool forced, hipStream_t stream);
+void set_msda_bwd_kernel_choice(int c);  // a MsdaBwdKernel; anything else: follow PCT_MSDA_BWD_KERNEL
+int msda_bwd_kernel_choice();
+void note_msda_bwd_kernel(int k);
+int msda_bwd_last_kernel();
+
+// ---- once per device, outside any stream capture (pct_prepare_device) ---------------------------------------------------
+unsigned *win_queue_slot(hipStream_t stream);      // msda_win_common.hpp: a launch's set of per-XCD work-item counters
+int prepare_win_queue_device();
+int prepare_msda_backward_col_device();
+int prepare_ffn_device();
+
+// ---- dynamic mask head (dyn_mask_head*.hip).  out_dtype: 0 = f32, 2 = bf16 -------------------------------------------
+int launch_dyn_mask_head(const float *feat, const float *ref, const float *params, int N, int C, int Q, int H, int W, int stride,
+                         int rel_coord, int th, int tw, int out_dtype, void *up, unsigned char *amask, hipStream_t stream);
+int launch_dyn_mask_head_mfma(const float *feat, const float *ref, const float *params, int N, int C, int Q, int H, int W,
+                              int stride, int rel_coord, int th, int tw, void *scratch, void *up, unsigned char *amask,
+                              hipStream_t stream);
+int launch_dyn_mask_head_fused(const float *feat, const float *ref, const float *params, int N, int C, int Q, int H, int W,
+                               int stride, int rel_coord, int th, int tw, void *workspace, void *up, unsigned char *amask,
+                               hipStream_t stream);
+
+// ---- the encoder's GEMMs and norms.  epi: 0 = bias, 1 = bias + ReLU, 2 = residual + LayerNorm -------------------------
+int launch_linear_k128(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period, const float *w,
+                       const float *bias, long long rows, int n, int epi, float *y, long long ldy, const float *residual,
+                       long long ldr, const float *gamma, const float *beta, float eps, hipStream_t stream);
+// The two split-bf16 launchers return PCT_NOT_COVERED when an operand is not 16-byte aligned for the dwordx4 epilogue:
+// launch_linear_k128 then falls back to its fp32-MFMA kernel, pct_linear_k128_multi_f32 (no fallback) reports PCT_ERR_ALIGNMENT
+int launch_linear_k128_split(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period, const float *w,
+                             const float *bias, long long rows, int n, int epi, float *y, long long ldy, const float *residual,
+                             long long ldr, const float *gamma, const float *beta, float eps, hipStream_t stream);
+int launch_linear_k128_split_multi(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period, int nseg,
+                                   const float *const *w, const float *const *bias, const int *n, const int *use_add,
+                                   float *const *y, const long long *ldy, long long rows, hipStream_t stream);
+int launch_linear_ln_split(const float *x, long long ldx, const float *w, unsigned short *w_pieces, int K, const float *bias,
+                           const float *residual, long long ldr, const float *gamma, const float *beta, float eps, long long rows,
+                           float *out, long long ldo, hipStream_t stream);
+int launch_ffn_fused_split(const float *x, long long ldx, const float *w1, const float *b1, const float *w2, const float *b2,
+                           const float *gamma, const float *beta, float eps, int F, long long rows, void *img_ws, float *out,
+                           long long ldo, hipStream_t stream);
+int launch_conv1x1_nchw_split(const float *x, const float *w, const float *bias, unsigned short *w_split_ws, int N, int K, int HW,
+                              float *y, hipStream_t stream);
+int launch_conv1x1_groupnorm_tokens(const float *x, const float *w, const float *bias, unsigned short *w_split_ws,
+                                    const float *gamma, const float *beta, float eps, int N, int K, int HW, float *partial_ws,
+                                    float *stats, float *out, long long out_batch_stride, hipStream_t stream);
+int launch_add_layernorm(const float *x, const float *y, const float *gamma, const float *beta, float eps, long long rows,
+                         int cols, float *out, hipStream_t stream);
+int launch_groupnorm_flatten(const float *x, const float *gamma, const float *beta, int N, int C, int HW, int groups, float eps,
+                             float *stats, float *out, long long out_batch_stride, long long out_offset, hipStream_t stream);
+
+// ---- the decoder's attention and the matcher ------------------------------------------------------------------------
+int launch_masked_attention(const void *q, const void *k, const void *vT, const unsigned char *mask, int N, int heads, int Q,
+                            int S, int head_dim, int v_head_dim, float scale, int out_dtype, void *out, hipStream_t stream);
+int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
+                           const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S, float scale,
+                           void *out, hipStream_t stream);
+int launch_lsap(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
+                int *status, hipStream_t stream);
+
+}  // namespace pct

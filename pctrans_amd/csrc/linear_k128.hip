@@ -19,39 +19,16 @@
 //   * epilogue in the accumulator layout (lane = column, 16 rows per lane): bias, ReLU, or residual + two-pass
 //     LayerNorm with DPP/readlane row sums and one LDS hop across the 4 waves; loads/stores go through buffer
 //     descriptors re-based per tile (32-bit offsets, the row bound is the descriptor size), 128-B row segments.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
+#include "launchers.hpp"
+#include "split_bf16.hpp"    // vector types, half_wave_sum
 
 namespace pct {
-
-typedef float lin_f32x16 __attribute__((ext_vector_type(16)));
-typedef float lin_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int LIN_K = 128;
 constexpr int LIN_BLOCK = 256;
 
 enum { LIN_EPI_BIAS = 0, LIN_EPI_BIAS_RELU = 1, LIN_EPI_RES_LN = 2 };
-
-template <int CTRL>
-__device__ __forceinline__ float lin_dpp(float v)
-{
-  const int i = __float_as_int(v);
-  return __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, true));
-}
-
-// sum over the 32 lanes of each wave half (lanes 0-31 / 32-63); result valid in every lane of the half
-__device__ __forceinline__ float lin_half_sum(float v)
-{
-  v += lin_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += lin_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += lin_dpp<0x141>(v);   // row_half_mirror
-  v += lin_dpp<0x140>(v);   // row_mirror  -> every lane of a 16-lane row holds the row's sum
-  const int vi = __float_as_int(v);                                 // (readlane takes and returns the bit pattern)
-  const float r0 = __int_as_float(__builtin_amdgcn_readlane(vi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(vi, 16));
-  const float r2 = __int_as_float(__builtin_amdgcn_readlane(vi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(vi, 48));
-  return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
-}
 
 constexpr int LIN_LDA = 132;                      // LDS row stride of the A image (floats)
 
@@ -64,7 +41,6 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
   __shared__ __attribute__((aligned(16))) float abuf[2][32 * LIN_LDA];
   __shared__ float red[4][32];                     // LayerNorm: per-wave partial row sums
   __shared__ float stat[32];
-  typedef int lin_i32x4 __attribute__((ext_vector_type(4)));
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int r = lane & 31, h = lane >> 5;
@@ -79,7 +55,7 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
     const float *wp = W + (long long)col * LIN_K + 4 * h;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-      const lin_f32x4 t = *reinterpret_cast<const lin_f32x4 *>(wp + 8 * u);
+      const f32x4 t = *reinterpret_cast<const f32x4 *>(wp + 8 * u);
       wreg[4 * u] = t[0];
       wreg[4 * u + 1] = t[1];
       wreg[4 * u + 2] = t[2];
@@ -110,7 +86,7 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
   // x2_period rows and repeats (pos is the same for every image of the batch: row i of X pairs with row i % period).
   const auto rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(HAS_X2 ? X2 : X), 0,
                                                      (int)((long long)x2_period * ldx2 * 4), 0x00020000);
-  auto fetch = [&](const long long tile, lin_i32x4 (&g)[4], lin_i32x4 (&g2)[4]) {
+  auto fetch = [&](const long long tile, i32x4 (&g)[4], i32x4 (&g2)[4]) {
     const auto rs = tile_rsrc(X, ldx, tile);
 #pragma unroll
     for (int q = 0; q < 4; ++q) g[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, g_voff, q * g_step, 0);
@@ -124,12 +100,12 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
       }
     }
   };
-  auto stash = [&](float *dst, const lin_i32x4 (&g)[4], const lin_i32x4 (&g2)[4]) {
+  auto stash = [&](float *dst, const i32x4 (&g)[4], const i32x4 (&g2)[4]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      lin_f32x4 v = __builtin_bit_cast(lin_f32x4, g[q]);
-      if constexpr (HAS_X2) v += __builtin_bit_cast(lin_f32x4, g2[q]);
-      *reinterpret_cast<lin_f32x4 *>(dst + s_off + q * 8 * LIN_LDA) = v;
+      f32x4 v = __builtin_bit_cast(f32x4, g[q]);
+      if constexpr (HAS_X2) v += __builtin_bit_cast(f32x4, g2[q]);
+      *reinterpret_cast<f32x4 *>(dst + s_off + q * 8 * LIN_LDA) = v;
     }
   };
 
@@ -137,7 +113,7 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
   const int r_voff = (int)((4 * h * ldr + col) * 4);
   const int a_off = r * LIN_LDA + 4 * h;
 
-  lin_i32x4 g[4], g2[4] = {};
+  i32x4 g[4], g2[4] = {};
   long long tile = blockIdx.x;
   if (tile < ntiles) {
     fetch(tile, g, g2);
@@ -150,14 +126,14 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
 
     const bool compute = active || EPI == LIN_EPI_RES_LN;
     // two accumulator chains: consecutive MFMAs never wait on each other's result
-    lin_f32x16 acc0, acc1;
+    f32x16 acc0, acc1;
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc0[j] = acc1[j] = 0.f;
     if (compute) {
     const float *ap = abuf[buf] + a_off;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-      const lin_f32x4 a = *reinterpret_cast<const lin_f32x4 *>(ap + 8 * u);
+      const f32x4 a = *reinterpret_cast<const f32x4 *>(ap + 8 * u);
       acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], wreg[4 * u], acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], wreg[4 * u + 1], acc1, 0, 0, 0);
       acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], wreg[4 * u + 2], acc0, 0, 0, 0);
@@ -182,7 +158,7 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
       // pass 1: mean.  Row sums over my wave's 32 columns, then across the 4 waves through LDS.
       float part[16];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) part[j] = lin_half_sum(v[j]);
+      for (int j = 0; j < 16; ++j) part[j] = half_wave_sum(v[j]);
       if (r == 0) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) red[wave][8 * (j / 4) + 4 * h + (j % 4)] = part[j];
@@ -194,7 +170,7 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
       for (int j = 0; j < 16; ++j) v[j] -= stat[8 * (j / 4) + 4 * h + (j % 4)];
       // pass 2: variance of the centred values
 #pragma unroll
-      for (int j = 0; j < 16; ++j) part[j] = lin_half_sum(v[j] * v[j]);
+      for (int j = 0; j < 16; ++j) part[j] = half_wave_sum(v[j] * v[j]);
       __syncthreads();                                            // stat / red free again
       if (r == 0) {
 #pragma unroll
@@ -220,10 +196,6 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
   }
 }
 
-int launch_linear_k128_split(const float *, long long, const float *, long long, long long, const float *, const float *,
-                             long long, int, int, float *, long long, const float *, long long, const float *,
-                             const float *, float, hipStream_t);
-
 // n must be a multiple of 32 (LayerNorm variant: exactly 128); x rows 16-byte aligned.
 // Default: the split-bf16 kernel of linear_k128_split.hip (same results to fp32 accuracy, 6/16 of the MFMA cycles);
 // PCT_LIN_KERNEL=f32 selects the fp32-MFMA kernel of this file (A/B).
@@ -238,7 +210,7 @@ int launch_linear_k128(const float *x, long long ldx, const float *x2, long long
   if (!use_f32) {
     const int rc = launch_linear_k128_split(x, ldx, x2, ldx2, x2_period, w, bias, rows, n, epi, y, ldy, residual, ldr,
                                             gamma, beta, eps, stream);
-    if (rc != -100) return rc;                                     // -100: operands not 16-byte aligned for its epilogue
+    if (rc != PCT_NOT_COVERED) return rc;                                     // PCT_NOT_COVERED: operands not 16-byte aligned for its epilogue
   }
   const long long ntiles = (rows + 31) / 32;
   const long long cap = 256LL * 3;                                 // persistent: 3 workgroups per CU (LDS allows 4)

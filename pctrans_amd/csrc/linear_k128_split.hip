@@ -23,8 +23,8 @@
 // dwordx4 all the way (bias/gamma/beta vectors, residual loads, stores -- 4 store instructions per lane and tile
 // instead of 16; with dword stores the kernel was store-issue bound at ~60 cycles per wave store), and a LayerNorm row
 // sum is 15 in-lane adds + one cross-half exchange + one LDS hop across the 4 waves.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "launchers.hpp"
+#include "split_bf16.hpp"
 
 // output rows carry the non-temporal hint (aux bit 1 of the buffer store): written once, read by the NEXT kernel, far larger
 // than the L2 -- merged projections 1.127 -> 1.102 ms at 1.39 M rows, three same-box alternations
@@ -35,13 +35,6 @@ constexpr int SPL_IL_DELAY = 1;
 
 namespace pct {
 
-typedef float spl_f32x16 __attribute__((ext_vector_type(16)));
-typedef float spl_f32x4 __attribute__((ext_vector_type(4)));
-typedef float spl_f32x2 __attribute__((ext_vector_type(2)));
-typedef int spl_i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 spl_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 spl_bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int SPL_K = 128;
 constexpr int SPL_BLOCK = 256;
 constexpr int SPL_ROWB = 272;                     // bytes per row of a bf16 plane (256 + 16 pad)
@@ -50,36 +43,6 @@ constexpr int SPL_IMAGE = 3 * SPL_PLANE;          // three planes
 constexpr int SPL_OLD = 36;                       // row stride (floats) of a wave's 32 x 32 output scratch
 
 enum { SPL_EPI_BIAS = 0, SPL_EPI_BIAS_RELU = 1, SPL_EPI_RES_LN = 2 };
-
-template <int CTRL>
-__device__ __forceinline__ float spl_dpp(float v)
-{
-  const int i = __float_as_int(v);
-  return __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, true));
-}
-
-// sum over the 32 lanes of each wave half; result valid in every lane of the half
-__device__ __forceinline__ float spl_half_sum(float v)
-{
-  v += spl_dpp<0xB1>(v);
-  v += spl_dpp<0x4E>(v);
-  v += spl_dpp<0x141>(v);
-  v += spl_dpp<0x140>(v);
-  const int vi = __float_as_int(v);
-  const float r0 = __int_as_float(__builtin_amdgcn_readlane(vi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(vi, 16));
-  const float r2 = __int_as_float(__builtin_amdgcn_readlane(vi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(vi, 48));
-  return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
-}
-
-// (x, y) -> three packed bf16 pairs (low half = x's piece), x = x1 + x2 + x3 exactly
-__device__ __forceinline__ void spl_split(const float x, const float y, unsigned &p1, unsigned &p2, unsigned &p3)
-{
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(spl_f32x2{x, y}, spl_bf16x2));     // v_cvt_pk_bf16_f32 (RNE)
-  const float rx = x - __uint_as_float(p1 << 16), ry = y - __uint_as_float(p1 & 0xffff0000u);   // exact
-  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(spl_f32x2{rx, ry}, spl_bf16x2));
-  const float sx = rx - __uint_as_float(p2 << 16), sy = ry - __uint_as_float(p2 & 0xffff0000u); // exact
-  p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(spl_f32x2{sx, sy}, spl_bf16x2));
-}
 
 // Up to SPL_MAXSEG Linear layers that read the same rows in ONE launch (segment s: y_s = x_s W_s^T + b_s with
 // x_s = x or x + x2): their column slices are dealt to the same XCD like the slices of a single wide layer, so x is
@@ -99,7 +62,6 @@ struct SplSegs {
 // v_mfma_f32_32x32x16_bf16 -- the same flops per clock and the same fragments' worth of registers, but on a chip that holds
 // its clock down under matrix load the 16 x 16 shape is granted a higher clock (MI355X_MICROARCH.md, DVFS item 7: 1.12-1.15x
 // in bare loops on random data).  Taken by the bias / ReLU epilogues.
-typedef float spl_f32x4acc __attribute__((ext_vector_type(4)));
 
 template <int EPI, bool HAS_X2>
 __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
@@ -156,9 +118,9 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
   const bool active = slice * 128 + wave * 32 < N;           // n % 32 == 0: wave-uniform
 
   // W pieces: step t of the MFMA loop covers k = 16t + 8h + 0..7 on both operands
-  spl_i32x4 w1[8], w2[8], w3[8];
+  i32x4 w1[8], w2[8], w3[8];
 #pragma unroll
-  for (int t = 0; t < 8; ++t) w1[t] = w2[t] = w3[t] = spl_i32x4{0, 0, 0, 0};
+  for (int t = 0; t < 8; ++t) w1[t] = w2[t] = w3[t] = i32x4{0, 0, 0, 0};
   if (active) {
     // M16: piece t = 4 cw + s holds W row cbase + 16 cw + lane % 16, k = 32 s + 8 (lane / 16) .. + 7 (A operand of the 16 x 16 x 32 form)
     const float *wp = M16 ? W + (long long)(slice * 128 + wave * 32 + (lane & 15)) * SPL_K + 8 * (lane >> 4)
@@ -166,13 +128,13 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const float *wt = M16 ? wp + (long long)(t >> 2) * 16 * SPL_K + 32 * (t & 3) : wp + 16 * t;
-      const spl_f32x4 lo = *reinterpret_cast<const spl_f32x4 *>(wt);
-      const spl_f32x4 hi = *reinterpret_cast<const spl_f32x4 *>(wt + 4);
+      const f32x4 lo = *reinterpret_cast<const f32x4 *>(wt);
+      const f32x4 hi = *reinterpret_cast<const f32x4 *>(wt + 4);
       unsigned a, b, c;
-      spl_split(lo[0], lo[1], a, b, c); w1[t][0] = (int)a; w2[t][0] = (int)b; w3[t][0] = (int)c;
-      spl_split(lo[2], lo[3], a, b, c); w1[t][1] = (int)a; w2[t][1] = (int)b; w3[t][1] = (int)c;
-      spl_split(hi[0], hi[1], a, b, c); w1[t][2] = (int)a; w2[t][2] = (int)b; w3[t][2] = (int)c;
-      spl_split(hi[2], hi[3], a, b, c); w1[t][3] = (int)a; w2[t][3] = (int)b; w3[t][3] = (int)c;
+      split_bf16x3(lo[0], lo[1], a, b, c); w1[t][0] = (int)a; w2[t][0] = (int)b; w3[t][0] = (int)c;
+      split_bf16x3(lo[2], lo[3], a, b, c); w1[t][1] = (int)a; w2[t][1] = (int)b; w3[t][1] = (int)c;
+      split_bf16x3(hi[0], hi[1], a, b, c); w1[t][2] = (int)a; w2[t][2] = (int)b; w3[t][2] = (int)c;
+      split_bf16x3(hi[2], hi[3], a, b, c); w1[t][3] = (int)a; w2[t][3] = (int)b; w3[t][3] = (int)c;
     }
   }
   // accumulator layout of the transposed tile: acc[4q + i] = y[row r][column cbase + 8q + 4h + i]
@@ -183,12 +145,12 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
     if (tid < 128) gbuf[0][tid] = gamma[tid];
     else gbuf[1][tid - 128] = beta[tid - 128];
   }
-  spl_f32x4 bvec[4];
+  f32x4 bvec[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     // (M16: a lane holds columns cbase + 16 cw + 4 (lane / 16) + 0..3 of its x row: bvec[cw])
     const int bc = M16 ? cbase + 16 * (q & 1) + 4 * (lane >> 4) : cbase + 8 * q + 4 * h;
-    bvec[q] = (bias && active) ? *reinterpret_cast<const spl_f32x4 *>(bias + bc) : spl_f32x4{0.f, 0.f, 0.f, 0.f};
+    bvec[q] = (bias && active) ? *reinterpret_cast<const f32x4 *>(bias + bc) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
   const long long ntiles = (M + 31) / 32;
@@ -205,13 +167,13 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
   const int s_off = (tid >> 5) * SPL_ROWB + 8 * (tid & 31);         // 4 bf16 = 8 B per float4 and plane
   const auto rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(HAS_X2 ? X2 : X), 0,
                                                      (int)((long long)x2_period * ldx2 * 4), 0x00020000);
-  auto fetch = [&](const long long tile, spl_i32x4 (&g)[4]) {
+  auto fetch = [&](const long long tile, i32x4 (&g)[4]) {
     const auto rs = tile_rsrc(X, ldx, tile);
 #pragma unroll
     for (int q = 0; q < 4; ++q) g[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, g_voff, q * g_step, 0);
   };
   // the x2 rows (the positional term, shared by the batch: L2 hits) are fetched one tile ahead only: one register set
-  auto fetch2 = [&](const long long tile, spl_i32x4 (&g2)[4]) {
+  auto fetch2 = [&](const long long tile, i32x4 (&g2)[4]) {
     if constexpr (HAS_X2) {
       const int base = (int)((tile * 32) % x2_period);              // uniform
 #pragma unroll
@@ -222,20 +184,20 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
       }
     }
   };
-  auto stash_q = [&](unsigned char *dst, const int q, const spl_i32x4 (&g)[4], const spl_i32x4 (&g2)[4]) {
-    spl_f32x4 v = __builtin_bit_cast(spl_f32x4, g[q]);
+  auto stash_q = [&](unsigned char *dst, const int q, const i32x4 (&g)[4], const i32x4 (&g2)[4]) {
+    f32x4 v = __builtin_bit_cast(f32x4, g[q]);
     if constexpr (HAS_X2) {
-      if (add_x2) v += __builtin_bit_cast(spl_f32x4, g2[q]);
+      if (add_x2) v += __builtin_bit_cast(f32x4, g2[q]);
     }
     unsigned a0, b0, c0, a1, b1, c1;
-    spl_split(v[0], v[1], a0, b0, c0);
-    spl_split(v[2], v[3], a1, b1, c1);
+    split_bf16x3(v[0], v[1], a0, b0, c0);
+    split_bf16x3(v[2], v[3], a1, b1, c1);
     unsigned char *p = dst + s_off + q * 8 * SPL_ROWB;
     *reinterpret_cast<uint2 *>(p) = make_uint2(a0, a1);
     *reinterpret_cast<uint2 *>(p + SPL_PLANE) = make_uint2(b0, b1);
     *reinterpret_cast<uint2 *>(p + 2 * SPL_PLANE) = make_uint2(c0, c1);
   };
-  auto stash = [&](unsigned char *dst, const spl_i32x4 (&g)[4], const spl_i32x4 (&g2)[4]) {
+  auto stash = [&](unsigned char *dst, const i32x4 (&g)[4], const i32x4 (&g2)[4]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) stash_q(dst, q, g, g2);
   };
@@ -251,10 +213,10 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
   // tile whatever n).  Issue order inside an iteration is what the in-order vmcnt makes cheap: [residual rows of this
   // tile, x of tile+2] -> MFMAs -> split + stash of tile+1 (the oldest loads) -> epilogue (waits only for the residual,
   // which is older than the far fetch) -> stores.
-  spl_i32x4 ga[4], gb[4], g2[4] = {};
-  auto body = [&](const long long tile, const int buf, spl_i32x4 (&gn)[4], spl_i32x4 (&gf)[4]) {
+  i32x4 ga[4], gb[4], g2[4] = {};
+  auto body = [&](const long long tile, const int buf, i32x4 (&gn)[4], i32x4 (&gf)[4]) {
     const long long far = tile + 2 * (long long)nslots;
-    spl_i32x4 res[4];
+    i32x4 res[4];
     if constexpr (EPI == SPL_EPI_RES_LN) {
       const auto rr = tile_rsrc(R, ldr, tile);
 #pragma unroll
@@ -266,23 +228,23 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
 
     if constexpr (M16) {
       // sub-tile (cw, rx): output columns cbase + 16 cw .., x rows 16 rx ..; acc[t] = y[row 16 rx + lane % 16][col cbase + 16 cw + 4 (lane / 16) + t]
-      spl_f32x4acc ahi[2][2], alo[2][2];
+      f32x4 ahi[2][2], alo[2][2];
 #pragma unroll
       for (int cw = 0; cw < 2; ++cw)
 #pragma unroll
-        for (int rx = 0; rx < 2; ++rx) ahi[cw][rx] = alo[cw][rx] = spl_f32x4acc{0.f, 0.f, 0.f, 0.f};
+        for (int rx = 0; rx < 2; ++rx) ahi[cw][rx] = alo[cw][rx] = f32x4{0.f, 0.f, 0.f, 0.f};
       {
         const unsigned char *ap = abuf[buf] + (lane & 15) * SPL_ROWB + 16 * (lane >> 4);     // x row lane % 16 (+ 16 rx), k = 8 (lane / 16) ..
-        spl_bf16x8 n1[2], n2[2], n3[2];
+        bf16x8 n1[2], n2[2], n3[2];
 #pragma unroll
         for (int rx = 0; rx < 2; ++rx) {
-          n1[rx] = *reinterpret_cast<const spl_bf16x8 *>(ap + rx * 16 * SPL_ROWB);
-          n2[rx] = *reinterpret_cast<const spl_bf16x8 *>(ap + rx * 16 * SPL_ROWB + SPL_PLANE);
-          n3[rx] = *reinterpret_cast<const spl_bf16x8 *>(ap + rx * 16 * SPL_ROWB + 2 * SPL_PLANE);
+          n1[rx] = *reinterpret_cast<const bf16x8 *>(ap + rx * 16 * SPL_ROWB);
+          n2[rx] = *reinterpret_cast<const bf16x8 *>(ap + rx * 16 * SPL_ROWB + SPL_PLANE);
+          n3[rx] = *reinterpret_cast<const bf16x8 *>(ap + rx * 16 * SPL_ROWB + 2 * SPL_PLANE);
         }
 #pragma unroll
         for (int sk = 0; sk < 4; ++sk) {
-          spl_bf16x8 x1[2], x2p[2], x3[2];
+          bf16x8 x1[2], x2p[2], x3[2];
 #pragma unroll
           for (int rx = 0; rx < 2; ++rx) {
             x1[rx] = n1[rx];
@@ -292,9 +254,9 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
           if (sk < 3) {
 #pragma unroll
             for (int rx = 0; rx < 2; ++rx) {
-              n1[rx] = *reinterpret_cast<const spl_bf16x8 *>(ap + rx * 16 * SPL_ROWB + 64 * (sk + 1));
-              n2[rx] = *reinterpret_cast<const spl_bf16x8 *>(ap + rx * 16 * SPL_ROWB + 64 * (sk + 1) + SPL_PLANE);
-              n3[rx] = *reinterpret_cast<const spl_bf16x8 *>(ap + rx * 16 * SPL_ROWB + 64 * (sk + 1) + 2 * SPL_PLANE);
+              n1[rx] = *reinterpret_cast<const bf16x8 *>(ap + rx * 16 * SPL_ROWB + 64 * (sk + 1));
+              n2[rx] = *reinterpret_cast<const bf16x8 *>(ap + rx * 16 * SPL_ROWB + 64 * (sk + 1) + SPL_PLANE);
+              n3[rx] = *reinterpret_cast<const bf16x8 *>(ap + rx * 16 * SPL_ROWB + 64 * (sk + 1) + 2 * SPL_PLANE);
             }
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -307,18 +269,12 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
           if (sk >= (HAS_X2 ? SPL_IL_DELAY : 0)) stash_q(abuf[buf ^ 1], sk - (HAS_X2 ? SPL_IL_DELAY : 0), gn, g2);
 #pragma unroll
           for (int cw = 0; cw < 2; ++cw) {
-            const spl_bf16x8 b1 = __builtin_bit_cast(spl_bf16x8, w1[4 * cw + sk]);
-            const spl_bf16x8 b2 = __builtin_bit_cast(spl_bf16x8, w2[4 * cw + sk]);
-            const spl_bf16x8 b3 = __builtin_bit_cast(spl_bf16x8, w3[4 * cw + sk]);
+            const bf16x8 b1 = __builtin_bit_cast(bf16x8, w1[4 * cw + sk]);
+            const bf16x8 b2 = __builtin_bit_cast(bf16x8, w2[4 * cw + sk]);
+            const bf16x8 b3 = __builtin_bit_cast(bf16x8, w3[4 * cw + sk]);
 #pragma unroll
-            for (int rx = 0; rx < 2; ++rx) {
-              alo[cw][rx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, x3[rx], alo[cw][rx], 0, 0, 0);
-              ahi[cw][rx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, x1[rx], ahi[cw][rx], 0, 0, 0);
-              alo[cw][rx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b3, x1[rx], alo[cw][rx], 0, 0, 0);
-              alo[cw][rx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, x2p[rx], alo[cw][rx], 0, 0, 0);
-              alo[cw][rx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b1, x2p[rx], alo[cw][rx], 0, 0, 0);
-              alo[cw][rx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, x1[rx], alo[cw][rx], 0, 0, 0);
-            }
+            for (int rx = 0; rx < 2; ++rx)
+              split_mfma6(b1, b2, b3, x1[rx], x2p[rx], x3[rx], ahi[cw][rx], alo[cw][rx]);
           }
 #pragma unroll
           for (int i = 0; i < 24; ++i) {
@@ -336,49 +292,44 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
         for (int cw = 0; cw < 2; ++cw)
 #pragma unroll
           for (int rx = 0; rx < 2; ++rx) {
-            spl_f32x4 v;
+            f32x4 v;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
               v[t] = (ahi[cw][rx][t] + alo[cw][rx][t]) + bvec[cw][t];
               if constexpr (EPI == SPL_EPI_BIAS_RELU) v[t] = fmaxf(v[t], 0.f);
             }
-            *reinterpret_cast<spl_f32x4 *>(sw + (16 * rx + (lane & 15)) * SPL_OLD + 16 * cw + 4 * (lane >> 4)) = v;
+            *reinterpret_cast<f32x4 *>(sw + (16 * rx + (lane & 15)) * SPL_OLD + 16 * cw + 4 * (lane >> 4)) = v;
           }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const spl_f32x4 o = *reinterpret_cast<const spl_f32x4 *>(sw + ((lane >> 3) + 8 * i) * SPL_OLD + 4 * (lane & 7));
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(spl_i32x4, o), ry, y_voff, i * y_step, SPL_STORE_NT);
+          const f32x4 o = *reinterpret_cast<const f32x4 *>(sw + ((lane >> 3) + 8 * i) * SPL_OLD + 4 * (lane & 7));
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), ry, y_voff, i * y_step, SPL_STORE_NT);
         }
       }
     } else {
-    spl_f32x16 acc_hi, acc_lo;                                    // a1w1 | the five small terms
+    f32x16 acc_hi, acc_lo;                                    // a1w1 | the five small terms
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc_hi[j] = acc_lo[j] = 0.f;
     {                                                             // (a wave past n multiplies zeros: no branch, so
       const unsigned char *ap = abuf[buf] + a_off;                //  the compiler's vmcnt bookkeeping stays exact)
       // the three pieces of step t+1 are read while step t's MFMAs run (the wave issues in order: reads placed
       // after the MFMAs would leave the matrix pipe idle for an LDS round trip per step)
-      spl_bf16x8 n1 = *reinterpret_cast<const spl_bf16x8 *>(ap);
-      spl_bf16x8 n2 = *reinterpret_cast<const spl_bf16x8 *>(ap + SPL_PLANE);
-      spl_bf16x8 n3 = *reinterpret_cast<const spl_bf16x8 *>(ap + 2 * SPL_PLANE);
+      bf16x8 n1 = *reinterpret_cast<const bf16x8 *>(ap);
+      bf16x8 n2 = *reinterpret_cast<const bf16x8 *>(ap + SPL_PLANE);
+      bf16x8 n3 = *reinterpret_cast<const bf16x8 *>(ap + 2 * SPL_PLANE);
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
-        const spl_bf16x8 a1 = n1, a2 = n2, a3 = n3;
+        const bf16x8 a1 = n1, a2 = n2, a3 = n3;
         if (t < 7) {
-          n1 = *reinterpret_cast<const spl_bf16x8 *>(ap + 32 * (t + 1));
-          n2 = *reinterpret_cast<const spl_bf16x8 *>(ap + 32 * (t + 1) + SPL_PLANE);
-          n3 = *reinterpret_cast<const spl_bf16x8 *>(ap + 32 * (t + 1) + 2 * SPL_PLANE);
+          n1 = *reinterpret_cast<const bf16x8 *>(ap + 32 * (t + 1));
+          n2 = *reinterpret_cast<const bf16x8 *>(ap + 32 * (t + 1) + SPL_PLANE);
+          n3 = *reinterpret_cast<const bf16x8 *>(ap + 32 * (t + 1) + 2 * SPL_PLANE);
         }
         __builtin_amdgcn_sched_barrier(0);
-        const spl_bf16x8 b1 = __builtin_bit_cast(spl_bf16x8, w1[t]);
-        const spl_bf16x8 b2 = __builtin_bit_cast(spl_bf16x8, w2[t]);
-        const spl_bf16x8 b3 = __builtin_bit_cast(spl_bf16x8, w3[t]);
-        acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a3, acc_lo, 0, 0, 0);
-        acc_hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, acc_hi, 0, 0, 0);
-        acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b3, a1, acc_lo, 0, 0, 0);
-        acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a2, acc_lo, 0, 0, 0);
-        acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a2, acc_lo, 0, 0, 0);
-        acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a1, acc_lo, 0, 0, 0);
+        const bf16x8 b1 = __builtin_bit_cast(bf16x8, w1[t]);
+        const bf16x8 b2 = __builtin_bit_cast(bf16x8, w2[t]);
+        const bf16x8 b3 = __builtin_bit_cast(bf16x8, w3[t]);
+        split_mfma6(b1, b2, b3, a1, a2, a3, acc_hi, acc_lo);
       }
     }
     stash(abuf[buf ^ 1], gn, g2);
@@ -415,8 +366,8 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
         const float rstd = rsqrtf(((red[0][r] + red[1][r]) + (red[2][r] + red[3][r])) * (1.f / 128.f) + eps);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const spl_f32x4 gq = *reinterpret_cast<const spl_f32x4 *>(&gbuf[0][wave * 32 + 8 * q + 4 * h]);
-          const spl_f32x4 bq = *reinterpret_cast<const spl_f32x4 *>(&gbuf[1][wave * 32 + 8 * q + 4 * h]);
+          const f32x4 gq = *reinterpret_cast<const f32x4 *>(&gbuf[0][wave * 32 + 8 * q + 4 * h]);
+          const f32x4 bq = *reinterpret_cast<const f32x4 *>(&gbuf[1][wave * 32 + 8 * q + 4 * h]);
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[4 * q + i] = v[4 * q + i] * rstd * gq[i] + bq[i];
         }
@@ -431,11 +382,11 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
       float *sw = oscr[wave];
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<spl_f32x4 *>(sw + r * SPL_OLD + 8 * q + 4 * h) = spl_f32x4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+        *reinterpret_cast<f32x4 *>(sw + r * SPL_OLD + 8 * q + 4 * h) = f32x4{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const spl_f32x4 o = *reinterpret_cast<const spl_f32x4 *>(sw + ((lane >> 3) + 8 * i) * SPL_OLD + 4 * (lane & 7));
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(spl_i32x4, o), ry, y_voff, i * y_step, SPL_STORE_NT);
+        const f32x4 o = *reinterpret_cast<const f32x4 *>(sw + ((lane >> 3) + 8 * i) * SPL_OLD + 4 * (lane & 7));
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), ry, y_voff, i * y_step, SPL_STORE_NT);
       }
     }
     }
@@ -477,7 +428,7 @@ static int spl_launch(const float *x, long long ldx, const float *x2, long long 
   if (x2) {
     if (epi == SPL_EPI_BIAS) PCT_SPL(SPL_EPI_BIAS, true);
     else if (epi == SPL_EPI_BIAS_RELU) PCT_SPL(SPL_EPI_BIAS_RELU, true);
-    else return -100;                                              // not instantiated (nothing uses it; it would spill)
+    else return PCT_NOT_COVERED;                                              // not instantiated (nothing uses it; it would spill)
   } else {
     if (epi == SPL_EPI_BIAS) PCT_SPL(SPL_EPI_BIAS, false);
     else if (epi == SPL_EPI_BIAS_RELU) PCT_SPL(SPL_EPI_BIAS_RELU, false);
@@ -487,7 +438,7 @@ static int spl_launch(const float *x, long long ldx, const float *x2, long long 
   return (int)hipGetLastError();
 }
 
-// n must be a multiple of 32 (LayerNorm variant: exactly 128); x rows 16-byte aligned.  Returns -100 when the
+// n must be a multiple of 32 (LayerNorm variant: exactly 128); x rows 16-byte aligned.  Returns PCT_NOT_COVERED when the
 // operands do not allow the dwordx4 epilogue (caller uses the fp32-MFMA kernel).
 int launch_linear_k128_split(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period,
                              const float *w, const float *bias, long long rows, int n, int epi, float *y, long long ldy,
@@ -497,7 +448,7 @@ int launch_linear_k128_split(const float *x, long long ldx, const float *x2, lon
   if (rows <= 0) return 0;
   if ((((uintptr_t)y | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)gamma | (uintptr_t)beta) & 15u) || (ldy & 3) ||
       (ldr & 3))
-    return -100;
+    return PCT_NOT_COVERED;
   SplSegs segs = {};
   segs.w[0] = w;
   segs.bias[0] = bias;
@@ -510,19 +461,19 @@ int launch_linear_k128_split(const float *x, long long ldx, const float *x2, lon
 }
 
 // several Linear layers over the same rows (bias epilogue only); every n[s] a multiple of 32, 1 <= nseg <= SPL_MAXSEG;
-// use_add[s] != 0: segment s multiplies x + x2.  Returns -100 when an operand is not 16-byte aligned.
+// use_add[s] != 0: segment s multiplies x + x2.  Returns PCT_NOT_COVERED when an operand is not 16-byte aligned.
 int launch_linear_k128_split_multi(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period,
                                    int nseg, const float *const *w, const float *const *bias, const int *n,
                                    const int *use_add, float *const *y, const long long *ldy, long long rows,
                                    hipStream_t stream)
 {
   if (rows <= 0) return 0;
-  if (nseg < 1 || nseg > SPL_MAXSEG) return -4;
+  if (nseg < 1 || nseg > SPL_MAXSEG) return PCT_ERR_UNSUPPORTED;
   SplSegs segs = {};
   segs.nseg = nseg;
   bool any_add = false;
   for (int g = 0; g < nseg; ++g) {
-    if ((((uintptr_t)y[g] | (uintptr_t)bias[g] | (uintptr_t)w[g]) & 15u) || (ldy[g] & 3)) return -100;
+    if ((((uintptr_t)y[g] | (uintptr_t)bias[g] | (uintptr_t)w[g]) & 15u) || (ldy[g] & 3)) return PCT_NOT_COVERED;
     segs.w[g] = w[g];
     segs.bias[g] = bias[g];
     segs.y[g] = y[g];

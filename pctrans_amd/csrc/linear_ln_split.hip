@@ -16,17 +16,10 @@
 //   * the MFMA computes the transposed tile (W pieces as the A operand), so a lane holds 4-column groups of ONE row:
 //     bias / residual / LayerNorm / store are dwordx4, the row statistics are in-lane sums + one cross-half exchange +
 //     one LDS hop between the two column halves.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "launchers.hpp"
+#include "split_bf16.hpp"
 
 namespace pct {
-
-typedef float lls_f32x16 __attribute__((ext_vector_type(16)));
-typedef float lls_f32x4 __attribute__((ext_vector_type(4)));
-typedef float lls_f32x2 __attribute__((ext_vector_type(2)));
-typedef int lls_i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 lls_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 lls_bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int LLS_BLOCK = 256;
 constexpr int LLS_BM = 128;                       // rows per workgroup tile
@@ -36,15 +29,6 @@ constexpr int LLS_ROWB = 80;                      // bytes per row and plane in 
 constexpr int LLS_PLANE = 128 * LLS_ROWB;         // 10240
 constexpr int LLS_OPER = 3 * LLS_PLANE;           // one operand's three planes
 
-__device__ __forceinline__ void lls_split(const float x, const float y, unsigned &p1, unsigned &p2, unsigned &p3)
-{
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(lls_f32x2{x, y}, lls_bf16x2));
-  const float rx = x - __uint_as_float(p1 << 16), ry = y - __uint_as_float(p1 & 0xffff0000u);   // exact
-  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(lls_f32x2{rx, ry}, lls_bf16x2));
-  const float sx = rx - __uint_as_float(p2 << 16), sy = ry - __uint_as_float(p2 & 0xffff0000u); // exact
-  p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(lls_f32x2{sx, sy}, lls_bf16x2));
-}
-
 // out[p * count + i] = piece p of w[i]  (count even)
 __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float *__restrict__ w, const long long count,
                                                            unsigned short *__restrict__ out)
@@ -52,7 +36,7 @@ __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float *__restri
   const long long i = 2 * ((long long)blockIdx.x * 256 + threadIdx.x);
   if (i >= count) return;
   unsigned p1, p2, p3;
-  lls_split(w[i], w[i + 1], p1, p2, p3);
+  split_bf16x3(w[i], w[i + 1], p1, p2, p3);
   *reinterpret_cast<unsigned *>(out + i) = p1;
   *reinterpret_cast<unsigned *>(out + count + i) = p2;
   *reinterpret_cast<unsigned *>(out + 2 * count + i) = p3;
@@ -105,7 +89,7 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
   const int wg_voff = (int)((((long long)(tid >> 2)) * K + 8 * (tid & 3)) * 2);
   const int ws_off = (tid >> 2) * LLS_ROWB + 16 * (tid & 3);
 
-  lls_i32x4 gx[4], gw[6];
+  i32x4 gx[4], gw[6];
   auto fetch = [&](const long long tile, const int step) {
     const auto rs = tile_rsrc(X, ldx, tile);
 #pragma unroll
@@ -118,20 +102,20 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
     unsigned p1[8], p2[8], p3[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const lls_f32x4 v = __builtin_bit_cast(lls_f32x4, gx[q]);
-      lls_split(v[0], v[1], p1[2 * q], p2[2 * q], p3[2 * q]);
-      lls_split(v[2], v[3], p1[2 * q + 1], p2[2 * q + 1], p3[2 * q + 1]);
+      const f32x4 v = __builtin_bit_cast(f32x4, gx[q]);
+      split_bf16x3(v[0], v[1], p1[2 * q], p2[2 * q], p3[2 * q]);
+      split_bf16x3(v[2], v[3], p1[2 * q + 1], p2[2 * q + 1], p3[2 * q + 1]);
     }
     unsigned char *p = xs + xs_off;
-    *reinterpret_cast<lls_i32x4 *>(p) = lls_i32x4{(int)p1[0], (int)p1[1], (int)p1[2], (int)p1[3]};
-    *reinterpret_cast<lls_i32x4 *>(p + 16) = lls_i32x4{(int)p1[4], (int)p1[5], (int)p1[6], (int)p1[7]};
-    *reinterpret_cast<lls_i32x4 *>(p + LLS_PLANE) = lls_i32x4{(int)p2[0], (int)p2[1], (int)p2[2], (int)p2[3]};
-    *reinterpret_cast<lls_i32x4 *>(p + LLS_PLANE + 16) = lls_i32x4{(int)p2[4], (int)p2[5], (int)p2[6], (int)p2[7]};
-    *reinterpret_cast<lls_i32x4 *>(p + 2 * LLS_PLANE) = lls_i32x4{(int)p3[0], (int)p3[1], (int)p3[2], (int)p3[3]};
-    *reinterpret_cast<lls_i32x4 *>(p + 2 * LLS_PLANE + 16) = lls_i32x4{(int)p3[4], (int)p3[5], (int)p3[6], (int)p3[7]};
+    *reinterpret_cast<i32x4 *>(p) = i32x4{(int)p1[0], (int)p1[1], (int)p1[2], (int)p1[3]};
+    *reinterpret_cast<i32x4 *>(p + 16) = i32x4{(int)p1[4], (int)p1[5], (int)p1[6], (int)p1[7]};
+    *reinterpret_cast<i32x4 *>(p + LLS_PLANE) = i32x4{(int)p2[0], (int)p2[1], (int)p2[2], (int)p2[3]};
+    *reinterpret_cast<i32x4 *>(p + LLS_PLANE + 16) = i32x4{(int)p2[4], (int)p2[5], (int)p2[6], (int)p2[7]};
+    *reinterpret_cast<i32x4 *>(p + 2 * LLS_PLANE) = i32x4{(int)p3[0], (int)p3[1], (int)p3[2], (int)p3[3]};
+    *reinterpret_cast<i32x4 *>(p + 2 * LLS_PLANE + 16) = i32x4{(int)p3[4], (int)p3[5], (int)p3[6], (int)p3[7]};
 #pragma unroll
     for (int i = 0; i < 6; ++i)
-      *reinterpret_cast<lls_i32x4 *>(ws + ws_off + (i >> 1) * LLS_PLANE + (i & 1) * 64 * LLS_ROWB) = gw[i];
+      *reinterpret_cast<i32x4 *>(ws + ws_off + (i >> 1) * LLS_PLANE + (i & 1) * 64 * LLS_ROWB) = gw[i];
   };
 
   // operand reads: lane (r, h) takes 16 B = 8 k at 32*ks + 16*h of its row
@@ -141,7 +125,7 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
   long long tile = blockIdx.x;
   fetch(tile, 0);
   for (; tile < ntiles; tile += gridDim.x) {
-    lls_f32x16 acc_hi[2][2], acc_lo[2][2];                        // [row block][column block]
+    f32x16 acc_hi[2][2], acc_lo[2][2];                        // [row block][column block]
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -159,25 +143,19 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        lls_bf16x8 a[2][3], w[2][3];
+        bf16x8 a[2][3], w[2][3];
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
           for (int p = 0; p < 3; ++p) {
-            a[b][p] = *reinterpret_cast<const lls_bf16x8 *>(xs + xr_off + b * 32 * LLS_ROWB + p * LLS_PLANE + 32 * ks);
-            w[b][p] = *reinterpret_cast<const lls_bf16x8 *>(ws + wr_off + b * 32 * LLS_ROWB + p * LLS_PLANE + 32 * ks);
+            a[b][p] = *reinterpret_cast<const bf16x8 *>(xs + xr_off + b * 32 * LLS_ROWB + p * LLS_PLANE + 32 * ks);
+            w[b][p] = *reinterpret_cast<const bf16x8 *>(ws + wr_off + b * 32 * LLS_ROWB + p * LLS_PLANE + 32 * ks);
           }
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[cb][0], a[rb][2], acc_lo[rb][cb], 0, 0, 0);
-            acc_hi[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[cb][0], a[rb][0], acc_hi[rb][cb], 0, 0, 0);
-            acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[cb][2], a[rb][0], acc_lo[rb][cb], 0, 0, 0);
-            acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[cb][1], a[rb][1], acc_lo[rb][cb], 0, 0, 0);
-            acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[cb][0], a[rb][1], acc_lo[rb][cb], 0, 0, 0);
-            acc_lo[rb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[cb][1], a[rb][0], acc_lo[rb][cb], 0, 0, 0);
-          }
+          for (int cb = 0; cb < 2; ++cb)
+            split_mfma6(w[cb][0], w[cb][1], w[cb][2], a[rb][0], a[rb][1], a[rb][2], acc_hi[rb][cb], acc_lo[rb][cb]);
       }
     }
 
@@ -193,9 +171,9 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c0 = 64 * wc + 32 * cb + 8 * q + 4 * h;
-          const lls_f32x4 res = __builtin_bit_cast(
-              lls_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)((row * ldr + c0) * 4), 0, 0));
-          const lls_f32x4 bq = *reinterpret_cast<const lls_f32x4 *>(&gbuf[0][c0]);
+          const f32x4 res = __builtin_bit_cast(
+              f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, (int)((row * ldr + c0) * 4), 0, 0));
+          const f32x4 bq = *reinterpret_cast<const f32x4 *>(&gbuf[0][c0]);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             v[16 * cb + 4 * q + i] = ((acc_hi[rb][cb][4 * q + i] + acc_lo[rb][cb][4 * q + i]) + bq[i]) + res[i];
@@ -225,12 +203,12 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c0 = 64 * wc + 32 * cb + 8 * q + 4 * h;
-          const lls_f32x4 gq = *reinterpret_cast<const lls_f32x4 *>(&gbuf[1][c0]);
-          const lls_f32x4 eq = *reinterpret_cast<const lls_f32x4 *>(&gbuf[2][c0]);
-          lls_f32x4 o;
+          const f32x4 gq = *reinterpret_cast<const f32x4 *>(&gbuf[1][c0]);
+          const f32x4 eq = *reinterpret_cast<const f32x4 *>(&gbuf[2][c0]);
+          f32x4 o;
 #pragma unroll
           for (int i = 0; i < 4; ++i) o[i] = v[16 * cb + 4 * q + i] * rstd * gq[i] + eq[i];
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lls_i32x4, o), ry, (int)((row * ldy + c0) * 4), 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, o), ry, (int)((row * ldy + c0) * 4), 0, 0);
         }
     }
   }
@@ -242,8 +220,8 @@ int launch_linear_ln_split(const float *x, long long ldx, const float *w, unsign
                            long long rows, float *out, long long ldo, hipStream_t stream)
 {
   if (rows <= 0) return 0;
-  if (K <= 0 || K % LLS_BK) return -4;
-  if ((long long)LLS_BM * (ldx > ldr ? (ldx > ldo ? ldx : ldo) : (ldr > ldo ? ldr : ldo)) * 4 > 0x7fffffffLL) return -4;
+  if (K <= 0 || K % LLS_BK) return PCT_ERR_UNSUPPORTED;
+  if ((long long)LLS_BM * (ldx > ldr ? (ldx > ldo ? ldx : ldo) : (ldr > ldo ? ldr : ldo)) * 4 > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   const long long count = (long long)LLS_N * K;
   hipLaunchKernelGGL(split_bf16x3_kernel, dim3((unsigned)((count / 2 + 255) / 256)), dim3(256), 0, stream, w, count, w_pieces);
   const long long ntiles = (rows + LLS_BM - 1) / LLS_BM;

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "msda_win_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -186,7 +187,7 @@ int launch_lsap(const float *cost, int batch, int num_query, int ld_target, cons
                 int *status, hipStream_t stream)
 {
   if (batch == 0) return 0;
-  if (num_query > LSAP_MAXQ || ld_target > LSAP_MAXG) return -4;
+  if (num_query > LSAP_MAXQ || ld_target > LSAP_MAXG) return PCT_ERR_UNSUPPORTED;
   // (the transposed costs use ld_target columns at most: sized for the worst case the caller declares)
   const size_t ct_bytes = (size_t)num_query * (size_t)ld_target * sizeof(float);
   const int in_lds = ct_bytes <= (size_t)LSAP_COST_LDS;

@@ -20,6 +20,7 @@
 // Fully masked rows give NaN exactly like softmax over all -inf does in the reference (callers un-mask such rows
 // first, mask2former_transformer_decoder.py:561).
 #include "attn_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -123,11 +124,11 @@ int launch_masked_attention(const void *q, const void *k, const void *vT, const 
                             int Q, int S, int head_dim, int v_head_dim, float scale, int out_dtype, void *out,
                             hipStream_t stream)
 {
-  if (v_head_dim != 16 || (head_dim != 32 && head_dim != 16)) return -4;
+  if (v_head_dim != 16 || (head_dim != 32 && head_dim != 16)) return PCT_ERR_UNSUPPORTED;
   if (N == 0 || Q == 0) return 0;
-  if (S <= 0) return -1;
+  if (S <= 0) return PCT_ERR_BAD_ARG;
   const long long nblk = (long long)N * heads * ((Q + 15) / 16);
-  if (nblk > 0x7fffffffLL) return -4;
+  if (nblk > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)nblk), block(64);
   const __bf16 *qq = static_cast<const __bf16 *>(q), *kk = static_cast<const __bf16 *>(k);
   const __bf16 *vv = static_cast<const __bf16 *>(vT);
@@ -138,7 +139,7 @@ int launch_masked_attention(const void *q, const void *k, const void *vT, const 
   else if (head_dim == 32 && out_dtype == 0) PCT_MA(32, float);
   else if (head_dim == 16 && out_dtype == 2) PCT_MA(16, __bf16);
   else if (head_dim == 16 && out_dtype == 0) PCT_MA(16, float);
-  else return -1;
+  else return PCT_ERR_BAD_ARG;
 #undef PCT_MA
   return (int)hipGetLastError();
 }

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "msda_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -166,17 +167,6 @@ __global__ __launch_bounds__(BWD_BLOCK) void msda_backward_kernel(
   }
 }
 
-int launch_msda_backward_win(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
-                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
-                             int P, float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream);
-// msda_backward_col.hip: the pyramid-column kernel and the backward's kernel choice (0 = auto, 1 = windowed, 2 = generic,
-// 3 = pyramid-column) / record of the kernel launched last (1 = windowed, 2 = generic, 3 = pyramid-column)
-int launch_msda_backward_col(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
-                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
-                             int P, float *grad_value, float *grad_loc, float *grad_attn, bool forced, hipStream_t stream);
-int msda_bwd_kernel_choice();
-void note_msda_bwd_kernel(int k);
-
 // Zero-fill by a kernel of our own instead of hipMemsetAsync.  A memset recorded into a HIP graph by torch.cuda.graph does
 // not replay reliably on ROCm 7.2 (a stand-alone capture of the same memsets does: tools/micro/graph_memset_replay.hip): from the second replay on, the node wrote a garbage dword into every fourth / second element of
 // grad_value (tools/diag_bwd_graph2.py: the windowed and the column backward both came out 0.26 x max|grad_value| off in
@@ -234,34 +224,34 @@ int launch_msda_backward(const void *value, const int64_t *shapes, const int64_t
     // PCT_MSDA_BWD_KERNEL = auto (pyramid-column when the queries are the pyramid's own pixels and the problem fills the
     // chip, else windowed, else generic) | col | win | generic; pct_msda_set_bwd_kernel_choice overrides the environment
     const int mode = msda_bwd_kernel_choice();
-    if (shfl && (mode == 0 || mode == 3) && Lq == S) {
+    if (shfl && (mode == MSDA_BWD_AUTO || mode == MSDA_BWD_COL) && Lq == S) {
       const int rc = launch_msda_backward_col(
           static_cast<const float *>(value), shapes, starts, static_cast<const float *>(loc),
           static_cast<const float *>(attn), static_cast<const float *>(grad_out), N, S, M, D, L, Lq, P,
-          static_cast<float *>(grad_value), static_cast<float *>(grad_loc), static_cast<float *>(grad_attn), mode == 3, stream);
-      if (rc != -100) {
-        note_msda_bwd_kernel(3);
+          static_cast<float *>(grad_value), static_cast<float *>(grad_loc), static_cast<float *>(grad_attn), mode == MSDA_BWD_COL, stream);
+      if (rc != PCT_NOT_COVERED) {
+        note_msda_bwd_kernel(MSDA_BWD_COL);
         return rc;
       }
     }
-    if (shfl && mode != 2 && (mode == 1 || Lq == S)) {
+    if (shfl && mode != MSDA_BWD_GENERIC && (mode == MSDA_BWD_WIN || Lq == S)) {
       const int rc = launch_msda_backward_win(
           static_cast<const float *>(value), shapes, starts, static_cast<const float *>(loc),
           static_cast<const float *>(attn), static_cast<const float *>(grad_out), N, S, M, D, L, Lq, P,
           static_cast<float *>(grad_value), static_cast<float *>(grad_loc), static_cast<float *>(grad_attn), stream);
-      if (rc != -100) {
-        note_msda_bwd_kernel(1);
+      if (rc != PCT_NOT_COVERED) {
+        note_msda_bwd_kernel(MSDA_BWD_WIN);
         return rc;
       }
     }
   }
-  note_msda_bwd_kernel(2);
+  note_msda_bwd_kernel(MSDA_BWD_GENERIC);
   const long long nblk = (total_lanes + BWD_BLOCK - 1) / BWD_BLOCK;
-  if (nblk > 0x7fffffffLL) return -4;
+  if (nblk > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   const int rec_stride = sizeof(A) == 4 ? padded_record_stride(LP * 3) : LP * 3 + 1;
   const int nrec_max = (BWD_BLOCK + CV - 2) / CV + 1;
   const size_t lds_bytes = (size_t)nrec_max * rec_stride * sizeof(A);
-  if (lds_bytes > 64 * 1024) return -4;
+  if (lds_bytes > 64 * 1024) return PCT_ERR_UNSUPPORTED;
 
   const dim3 grid((unsigned)nblk), block(BWD_BLOCK);
   const A *go = static_cast<const A *>(grad_out), *v = static_cast<const A *>(value);

@@ -40,6 +40,7 @@
 #include <utility>
 
 #include "msda_col_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -650,7 +651,8 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
       // a window dword receives at most BLOCK * P = 1024 contributions w_corner * attn * grad_out, each below C < 2^e:
       // rounded to multiples of 2^(e - 21) every contribution is below 2^21 in magnitude and the int32 sums stay inside
       // (-2^31, 2^31) (a contribution also has to stay below 2^22 for the magic-constant rounding)
-      const int shift = max(min(21 - e, 100), -100);
+      constexpr int SHIFT_MAX = 100;
+      const int shift = max(min(21 - e, SHIFT_MAX), -SHIFT_MAX);
       scale = uni(ldexpf(1.f, shift));
       inv_scale = uni(ldexpf(1.f, -shift));
     }
@@ -877,7 +879,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
 // ---- kernel choice for the backward (diagnostics; see include/pctrans_hip.h) ---------------------------------------------
 static std::atomic<int> g_bwd_choice{-1};                                    // -1: follow PCT_MSDA_BWD_KERNEL
 static std::atomic<int> g_bwd_last{0};
-void set_msda_bwd_kernel_choice(int c) { g_bwd_choice.store((c >= 0 && c <= 3) ? c : -1); }
+void set_msda_bwd_kernel_choice(int c) { g_bwd_choice.store((c >= MSDA_BWD_AUTO && c <= MSDA_BWD_COL) ? c : -1); }
 int msda_bwd_last_kernel() { return g_bwd_last.load(); }
 void note_msda_bwd_kernel(int k) { g_bwd_last.store(k); }
 int msda_bwd_kernel_choice()
@@ -886,7 +888,8 @@ int msda_bwd_kernel_choice()
   if (c >= 0) return c;
   static const int env = [] {
     const char *e = getenv("PCT_MSDA_BWD_KERNEL");
-    return !e ? 0 : (!strcmp(e, "win") ? 1 : (!strcmp(e, "generic") ? 2 : (!strcmp(e, "col") ? 3 : 0)));
+    if (!e) return MSDA_BWD_AUTO;
+    return !strcmp(e, "win") ? MSDA_BWD_WIN : (!strcmp(e, "generic") ? MSDA_BWD_GENERIC : (!strcmp(e, "col") ? MSDA_BWD_COL : MSDA_BWD_AUTO));
   }();
   return env;
 }
@@ -982,25 +985,25 @@ int prepare_msda_backward_col_device()
   return bcol_flag_buffer(nullptr, &slot, true) ? 0 : (int)hipErrorOutOfMemory;
 }
 
-// returns -100 when this geometry is not covered (caller uses another kernel)
+// returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel)
 int launch_msda_backward_col(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
                              const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
                              int P, float *grad_value, float *grad_loc, float *grad_attn, bool forced, hipStream_t stream)
 {
   if ((((uintptr_t)value | (uintptr_t)grad_out | (uintptr_t)loc | (uintptr_t)attn | (uintptr_t)grad_loc |
         (uintptr_t)grad_attn) & 15u) || ((uintptr_t)grad_value & 3u))
-    return -100;
-  if (D != 16 || P != 4 || L < 3 || L > 5 || Lq != S || M < 1) return -100;
-  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return -100;   // item / record arithmetic headroom
-  if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return -100;               // 32-bit byte offsets inside an image, all tensors
-  if ((long long)S * M * D * 4 >= 0x7fffffffLL) return -100;                   // (0x80000000 is the out-of-range sentinel)
-  if (S >= (1 << 24) || M >= (1 << 16)) return -100;                           // 24-bit multiplies in the record index
+    return PCT_NOT_COVERED;
+  if (D != 16 || P != 4 || L < 3 || L > 5 || Lq != S || M < 1) return PCT_NOT_COVERED;
+  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;   // item / record arithmetic headroom
+  if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return PCT_NOT_COVERED;               // 32-bit byte offsets inside an image, all tensors
+  if ((long long)S * M * D * 4 >= 0x7fffffffLL) return PCT_NOT_COVERED;                   // (0x80000000 is the out-of-range sentinel)
+  if (S >= (1 << 24) || M >= (1 << 16)) return PCT_NOT_COVERED;                           // 24-bit multiplies in the record index
   // (measured against the windowed kernel down to one 256^2-image pyramid, 43 k (query, head) pairs: 0.042 vs 0.055 ms;
   // profiles/r03_bwd_small_sizes.txt)
-  if (!forced && (long long)N * S * M < 32768) return -100;
+  if (!forced && (long long)N * S * M < 32768) return PCT_NOT_COVERED;
   int flag_slot = -1;
   unsigned char *flags = bcol_flag_buffer(stream, &flag_slot);
-  if (!flags) return -100;
+  if (!flags) return PCT_NOT_COVERED;
   // (PCT_BCOL_FLAG_CAP: a smaller capacity, so that a test can reach the overflow route with an oracle-sized case)
   static const int cap_env = [] { const char *e = getenv("PCT_BCOL_FLAG_CAP"); return e ? atoi(e) : 0; }();
   const int flag_cap = (cap_env > 0 && cap_env < (int)BCOL_FLAG_BYTES) ? cap_env : (int)BCOL_FLAG_BYTES;

@@ -29,6 +29,7 @@
 #include <utility>
 
 #include "msda_win_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -542,16 +543,16 @@ __global__ __launch_bounds__(WIN_BLOCK, 2) void msda_backward_win_kernel(
   }
 }
 
-// returns -100 when this geometry is not covered (caller uses msda_backward.hip)
+// returns PCT_NOT_COVERED when this geometry is not covered (caller uses msda_backward.hip)
 int launch_msda_backward_win(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
                              const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
                              int P, float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream)
 {
-  if ((((uintptr_t)value | (uintptr_t)grad_out) & 15u) || (((uintptr_t)loc | (uintptr_t)grad_loc) & 7u)) return -100;
-  if (D != 16 || P != 4 || L < 3 || L > 5) return -100;
-  if ((long long)N * Lq * M < 32768) return -100;
-  if ((long long)N * ((long long)S + 64 * L) * M >= 0x7fffffffLL) return -100;
-  if ((long long)S * M * D >= 0x7fffffffLL) return -100;            // per-image element offsets are 32-bit
+  if ((((uintptr_t)value | (uintptr_t)grad_out) & 15u) || (((uintptr_t)loc | (uintptr_t)grad_loc) & 7u)) return PCT_NOT_COVERED;
+  if (D != 16 || P != 4 || L < 3 || L > 5) return PCT_NOT_COVERED;
+  if ((long long)N * Lq * M < 32768) return PCT_NOT_COVERED;
+  if ((long long)N * ((long long)S + 64 * L) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;
+  if ((long long)S * M * D >= 0x7fffffffLL) return PCT_NOT_COVERED;            // per-image element offsets are 32-bit
   const int pool_px = BWD_WIN_POOL_PX;                               // value pool + grad pool + boxes per workgroup
   const size_t lds = 2 * (size_t)pool_px * 64 + (WIN_BLOCK / 64) * (WIN_MAXL + 1) * 2 * sizeof(unsigned) + 16;
   const int wg_fit = (int)((160 * 1024) / lds);

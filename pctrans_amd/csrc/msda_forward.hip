@@ -20,6 +20,7 @@
 #include <atomic>
 
 #include "msda_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -192,27 +193,13 @@ __global__ __launch_bounds__(FWD_BLOCK) void msda_forward_kernel(
   }
 }
 
-// specialised kernels for PCTrans' geometry; each returns -100 when it does not cover the call
-template <typename T>
-int launch_msda_forward_win(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int, int,
-                            int, int, int, int, void *, hipStream_t, const float *, long long);   // msda_forward_win.hip
-template <typename T>
-int launch_msda_forward_dpp(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int, int,
-                            int, int, int, int, void *, hipStream_t, const float *, long long);   // msda_forward_dpp.hip
-
-int launch_msda_forward_col(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int, int,
-                            int, int, int, int, void *, hipStream_t, const float *, long long, bool);   // msda_forward_col.hip
-template <typename T>
-int launch_msda_forward_col16(const void *, const int64_t *, const int64_t *, const void *, const void *, int, int, int,
-                              int, int, int, int, void *, hipStream_t, const float *, long long);  // msda_forward_col16.hip
-
 // Kernel choice for PCTrans' geometry.  Default "auto": the windowed-LDS kernel when the queries are the pyramid's
 // own pixels (Lq == S: neighbouring queries sample neighbouring texels, the case it is built for) and the problem fills
 // its persistent grid (except where it was measured slower, see below), else the quad-owner kernel.
 // PCT_MSDA_KERNEL = auto | win | dpp | generic | col (development A/B).
 static std::atomic<int> g_kernel_override{-1};     // pct_msda_set_kernel_choice (diagnostic): -1 = follow the environment
 static std::atomic<int> g_last_kernel{0};          // pct_msda_last_kernel (diagnostic): what the last forward call launched
-void set_msda_kernel_choice(int v) { g_kernel_override.store((v >= 0 && v <= 4) ? v : -1, std::memory_order_relaxed); }
+void set_msda_kernel_choice(int v) { g_kernel_override.store((v >= MSDA_FWD_AUTO && v <= MSDA_FWD_COL) ? v : -1, std::memory_order_relaxed); }
 int msda_last_kernel() { return g_last_kernel.load(std::memory_order_relaxed); }
 void note_msda_kernel(int k) { g_last_kernel.store(k, std::memory_order_relaxed); }
 
@@ -222,25 +209,25 @@ int msda_kernel_choice()
   if (ov >= 0) return ov;
   static const int v = [] {
     const char *e = getenv("PCT_MSDA_KERNEL");
-    if (!e) return 0;
-    if (e[0] == 'w') return 1;
-    if (e[0] == 'd') return 3;
-    if (e[0] == 'g') return 2;
-    if (e[0] == 'c') return 4;
-    return 0;
+    if (!e) return MSDA_FWD_AUTO;
+    if (e[0] == 'w') return MSDA_FWD_WIN;
+    if (e[0] == 'd') return MSDA_FWD_QUAD;
+    if (e[0] == 'g') return MSDA_FWD_GENERIC;
+    if (e[0] == 'c') return MSDA_FWD_COL;
+    return MSDA_FWD_AUTO;
   }();
   return v;
 }
 
-// shared by the plain and the fused entry points: -100 = geometry not covered by the specialised kernels
+// shared by the plain and the fused entry points: PCT_NOT_COVERED = geometry not covered by the specialised kernels
 template <typename T>
 int launch_msda_forward_special(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
                                 const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
                                 hipStream_t stream, const float *ref, long long ref_batch_stride)
 {
   const int choice = msda_kernel_choice();
-  if (choice == 2) return -100;
-  int rc = -100;
+  if (choice == MSDA_FWD_GENERIC) return PCT_NOT_COVERED;
+  int rc = PCT_NOT_COVERED;
   // 16-bit values with 8 points per level (SURVEY config 5): the windowed variant (2 lanes per head-pixel, 4 points per
   // lane and level, 20-40 spilled VGPRs) loses to the quad-owner kernel (P3, N = 1: 0.49 vs 0.34 ms) -- measured, so
   // "auto" skips it there; fp32 with 8 points and 16-bit with 4 points stay on the windowed kernel (faster)
@@ -254,40 +241,40 @@ int launch_msda_forward_special(const void *value, const int64_t *shapes, const 
   // levels it wins from one 512^2 image on (N * S * M = 174 k); with 3 levels from about 450 k (quad-owner before that)
   if constexpr (sizeof(typename Traits<T>::store_t) == 4) {
     const bool col_big = (long long)N * S * M >= (L >= 4 ? 160000LL : 450000LL);
-    if (choice == 4 || (choice == 0 && Lq == S && P == 4 && col_big)) {
+    if (choice == MSDA_FWD_COL || (choice == MSDA_FWD_AUTO && Lq == S && P == 4 && col_big)) {
       rc = launch_msda_forward_col(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref, ref_batch_stride, false);
-      if (rc != -100) note_msda_kernel(4);
+      if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_COL);
     }
   }
   if constexpr (sizeof(typename Traits<T>::store_t) == 2) {
     // 16-bit values: the column kernel's 16-bit variant (4 or 8 points; two lanes per (query, head) with 8 points)
     const bool col_big = (long long)N * S * M * (P / 4) >= (L >= 4 ? 160000LL : 450000LL);
-    if (choice == 4 || (choice == 0 && Lq == S && (P == 4 || P == 8) && col_big)) {
+    if (choice == MSDA_FWD_COL || (choice == MSDA_FWD_AUTO && Lq == S && (P == 4 || P == 8) && col_big)) {
       rc = launch_msda_forward_col16<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
                                         ref_batch_stride);
-      if (rc != -100) note_msda_kernel(4);
+      if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_COL);
     }
   }
-  if (rc == -100 && (choice == 1 || (choice == 0 && Lq == S && !win_loses && !win_small))) {
+  if (rc == PCT_NOT_COVERED && (choice == MSDA_FWD_WIN || (choice == MSDA_FWD_AUTO && Lq == S && !win_loses && !win_small))) {
     rc = launch_msda_forward_win<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
                                     ref_batch_stride);
-    if (rc != -100) note_msda_kernel(1);
+    if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_WIN);
   }
-  if (rc == -100) {
+  if (rc == PCT_NOT_COVERED) {
     rc = launch_msda_forward_dpp<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
                                     ref_batch_stride);
-    if (rc != -100) note_msda_kernel(3);
+    if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_QUAD);
   }
   return rc;
 }
-// piece-plane operands (pct_ms_deform_attn_forward_planes_f32): the pyramid-column kernel or nothing (-100)
+// piece-plane operands (pct_ms_deform_attn_forward_planes_f32): the pyramid-column kernel or nothing (PCT_NOT_COVERED)
 int launch_msda_forward_planes(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
                                const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
                                hipStream_t stream, const float *ref, long long ref_batch_stride)
 {
   const int rc = launch_msda_forward_col(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
                                          ref_batch_stride, true);
-  if (rc != -100) note_msda_kernel(4);
+  if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_COL);
   return rc;
 }
 
@@ -306,9 +293,9 @@ int launch_msda_forward(const void *value, const int64_t *shapes, const int64_t 
   if constexpr (sizeof(A) == 4) {
     const int rc = launch_msda_forward_special<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream,
                                                   nullptr, 0);
-    if (rc != -100) return rc;
+    if (rc != PCT_NOT_COVERED) return rc;
   }
-  note_msda_kernel(2);
+  note_msda_kernel(MSDA_FWD_GENERIC);
   constexpr int VECW = 16 / (int)sizeof(ST);                    // channels in one 16-byte lane load
   const bool aligned16 = (((uintptr_t)value | (uintptr_t)out) & 15u) == 0 &&
                          (((uintptr_t)loc | (uintptr_t)attn) & 15u) == 0;
@@ -318,12 +305,12 @@ int launch_msda_forward(const void *value, const int64_t *shapes, const int64_t 
   const long long total_lanes = (long long)N * Lq * M * CV;
   if (total_lanes == 0) return 0;
   const long long nblk = (total_lanes + FWD_BLOCK - 1) / FWD_BLOCK;
-  if (nblk > 0x7fffffffLL) return -4;
+  if (nblk > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   const int LP = L * P;
   const int rec_stride = sizeof(A) == 4 ? padded_record_stride(LP * 3) : LP * 3 + 1;
   const int nrec_max = (FWD_BLOCK + CV - 2) / CV + 1;
   const size_t lds_bytes = (size_t)nrec_max * rec_stride * sizeof(A);
-  if (lds_bytes > 64 * 1024) return -4;
+  if (lds_bytes > 64 * 1024) return PCT_ERR_UNSUPPORTED;
 
   const dim3 grid((unsigned)nblk), block(FWD_BLOCK);
   const ST *v = static_cast<const ST *>(value);

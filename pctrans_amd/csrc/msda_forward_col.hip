@@ -30,6 +30,7 @@
 #include <utility>
 
 #include "msda_col_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -945,20 +946,20 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
   }
 }
 
-// ---- launcher: returns -100 when this geometry is not covered (caller uses another kernel) ----------------------------
+// ---- launcher: returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel) ----------------------------
 // ref == nullptr: plain op; ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits).
 int launch_msda_forward_col(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
                             const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
                             hipStream_t stream, const float *ref, long long ref_batch_stride, bool planes)
 {
-  if ((((uintptr_t)value | (uintptr_t)out | (uintptr_t)loc | (uintptr_t)attn) & 15u)) return -100;
-  if (ref && (((uintptr_t)ref) & ((L % 2 == 0) ? 15u : 7u))) return -100;
-  if (ref && (L % 2 == 0) && (ref_batch_stride & 3)) return -100;
-  if (D != 16 || P != 4 || L < 3 || L > 5 || Lq != S || M < 1) return -100;
-  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return -100;   // item / record arithmetic headroom
-  if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return -100;               // 32-bit byte offsets inside an image, all tensors
-  if ((long long)S * M * D * 4 >= 0x7fffffffLL) return -100;                   // (0x80000000 is the out-of-range sentinel)
-  if (S >= (1 << 24) || M >= (1 << 16)) return -100;                           // 24-bit multiplies in the record index
+  if ((((uintptr_t)value | (uintptr_t)out | (uintptr_t)loc | (uintptr_t)attn) & 15u)) return PCT_NOT_COVERED;
+  if (ref && (((uintptr_t)ref) & ((L % 2 == 0) ? 15u : 7u))) return PCT_NOT_COVERED;
+  if (ref && (L % 2 == 0) && (ref_batch_stride & 3)) return PCT_NOT_COVERED;
+  if (D != 16 || P != 4 || L < 3 || L > 5 || Lq != S || M < 1) return PCT_NOT_COVERED;
+  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;   // item / record arithmetic headroom
+  if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return PCT_NOT_COVERED;               // 32-bit byte offsets inside an image, all tensors
+  if ((long long)S * M * D * 4 >= 0x7fffffffLL) return PCT_NOT_COVERED;                   // (0x80000000 is the out-of-range sentinel)
+  if (S >= (1 << 24) || M >= (1 << 16)) return PCT_NOT_COVERED;                           // 24-bit multiplies in the record index
   const int pool_px = COL_POOL_KB * 1024 / 64;
   const size_t lds = (size_t)pool_px * 64 + ((size_t)(COL_BLOCK / 64) * L * 2 + 4) * sizeof(unsigned);   // pool, boxes, queue words
   const dim3 grid(256 * COL_WG_PER_CU), block(COL_BLOCK);

@@ -19,6 +19,7 @@
 #include <utility>
 
 #include "msda_col_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -638,18 +639,18 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
   }
 }
 
-// ---- launcher: returns -100 when this geometry is not covered (caller uses another kernel) ----------------------------
+// ---- launcher: returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel) ----------------------------
 template <typename T>
 int launch_msda_forward_col16(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
                               const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
                               hipStream_t stream, const float *ref, long long ref_batch_stride)
 {
   using ST = typename Traits<T>::store_t;
-  if ((((uintptr_t)value | (uintptr_t)out | (uintptr_t)loc | (uintptr_t)attn) & 15u)) return -100;
-  if (ref && (((uintptr_t)ref) & 7u)) return -100;
-  if (D != 16 || (P != 4 && P != 8) || L < 3 || L > 5 || Lq != S || M < 1) return -100;
-  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return -100;
-  if ((long long)S * M * L * P * 8 >= 0xffffffffLL) return -100;               // 32-bit byte offsets inside an image
+  if ((((uintptr_t)value | (uintptr_t)out | (uintptr_t)loc | (uintptr_t)attn) & 15u)) return PCT_NOT_COVERED;
+  if (ref && (((uintptr_t)ref) & 7u)) return PCT_NOT_COVERED;
+  if (D != 16 || (P != 4 && P != 8) || L < 3 || L > 5 || Lq != S || M < 1) return PCT_NOT_COVERED;
+  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;
+  if ((long long)S * M * L * P * 8 >= 0xffffffffLL) return PCT_NOT_COVERED;               // 32-bit byte offsets inside an image
   constexpr int BLOCK = 256;
   const int pool_px = 50 * 1024 / 32;                                          // ~50 KB of LDS per workgroup, 3 per CU
   const size_t lds = (size_t)pool_px * 32 + ((size_t)(BLOCK / 64) * L * 2 + 4) * sizeof(unsigned);

@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "msda_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(1024) void msda_forward_dpp_kernel(
   }
 }
 
-// returns -100 when this geometry is not covered (caller falls through to the generic kernel).
+// returns PCT_NOT_COVERED when this geometry is not covered (caller falls through to the generic kernel).
 // ref == nullptr: plain op (loc = sampling locations, attn = attention weights);
 // ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits, ref = [N or 1, Lq, L, 2] reference points).
 template <typename T>
@@ -228,17 +229,17 @@ int launch_msda_forward_dpp(const void *value, const int64_t *shapes, const int6
 {
   using ST = typename Traits<T>::store_t;
   constexpr int VEC = 16 / (int)sizeof(ST);
-  if (D != 16 || (P != 4 && P != 8)) return -100;
-  if ((((uintptr_t)value | (uintptr_t)out) & 15u) || (((uintptr_t)loc) & 7u) || (((uintptr_t)attn) & 3u)) return -100;
+  if (D != 16 || (P != 4 && P != 8)) return PCT_NOT_COVERED;
+  if ((((uintptr_t)value | (uintptr_t)out) & 15u) || (((uintptr_t)loc) & 7u) || (((uintptr_t)attn) & 3u)) return PCT_NOT_COVERED;
   const long long vbytes = (long long)N * S * M * D * (long long)sizeof(ST);
-  if (vbytes >= 0x7fffffffLL) return -100;                          // 32-bit buffer offsets, OOB sentinel at 2^31
+  if (vbytes >= 0x7fffffffLL) return PCT_NOT_COVERED;                          // 32-bit buffer offsets, OOB sentinel at 2^31
   constexpr int QL = 16 / VEC;
   const long long total_recs = (long long)N * Lq * M;
   if (total_recs == 0) return 0;
   const bool qmajor = M <= 16;
   const long long per_blk = qmajor ? (long long)(64 / QL) * M : DPP_BLOCK / QL;    // records per block
   const long long nblk = qmajor ? ((long long)N * Lq + 64 / QL - 1) / (64 / QL) : (total_recs + per_blk - 1) / per_blk;
-  if (nblk > 0x7fffffffLL) return -100;
+  if (nblk > 0x7fffffffLL) return PCT_NOT_COVERED;
   const dim3 grid((unsigned)nblk), block(qmajor ? 64 * M : DPP_BLOCK);
   const ST *v = static_cast<const ST *>(value);
   const float *lc = static_cast<const float *>(loc), *at = static_cast<const float *>(attn);

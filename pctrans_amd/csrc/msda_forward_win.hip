@@ -28,6 +28,7 @@
 #include <utility>
 
 #include "msda_win_common.hpp"
+#include "launchers.hpp"
 
 namespace pct {
 
@@ -566,7 +567,7 @@ int prepare_win_queue_device()
   return win_queue_slot(null_stream) ? 0 : 0;      // (nullptr = queues disabled or no memory: launches then use the static stride)
 }
 
-// ---- launcher: returns -100 when this geometry is not covered (caller uses another kernel) ----------------------
+// ---- launcher: returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel) ----------------------
 // ref == nullptr: plain op; ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits).
 template <typename T>
 int launch_msda_forward_win(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
@@ -575,11 +576,11 @@ int launch_msda_forward_win(const void *value, const int64_t *shapes, const int6
 {
   using ST = typename Traits<T>::store_t;
   constexpr int VEC = 16 / (int)sizeof(ST);
-  if ((((uintptr_t)value | (uintptr_t)out) & 15u) || (((uintptr_t)loc) & 7u) || (((uintptr_t)attn) & 3u)) return -100;
-  if (ref && (((uintptr_t)ref) & 7u)) return -100;
-  if (D != 16 || (P != 4 && P != 8) || L < 3 || L > 5) return -100;
-  if ((long long)N * Lq * M < 32768) return -100;                  // too small to fill a persistent grid
-  if ((long long)N * ((long long)S + 64 * L) * M >= 0x7fffffffLL) return -100;   // item counter is 32-bit
+  if ((((uintptr_t)value | (uintptr_t)out) & 15u) || (((uintptr_t)loc) & 7u) || (((uintptr_t)attn) & 3u)) return PCT_NOT_COVERED;
+  if (ref && (((uintptr_t)ref) & 7u)) return PCT_NOT_COVERED;
+  if (D != 16 || (P != 4 && P != 8) || L < 3 || L > 5) return PCT_NOT_COVERED;
+  if ((long long)N * Lq * M < 32768) return PCT_NOT_COVERED;                  // too small to fill a persistent grid
+  if ((long long)N * ((long long)S + 64 * L) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;   // item counter is 32-bit
   constexpr int QL = 16 / VEC;
   // a 50 KB pool, 3 workgroups per CU; P = 4: NS = 4 query slots per lane.  P = 8 (config 5): twice the points per lane
   // -> 2 slots per lane (16-bit: 1, 128 queries per slot)

@@ -115,8 +115,6 @@ inline hipError_t func_attr_per_device(const void *fn, const int bytes = 160 * 1
 // skeleton" -- and 0.34 ms with the counters apart (profiles/r04_forward_structural_ab.txt).  The product kernels draw
 // ~40 items per microsecond and hide the fetch two items ahead, so they did not get faster; the cap is gone.
 constexpr int WIN_QUEUE_STRIDE = 64;
-unsigned *win_queue_slot(hipStream_t stream);
-int prepare_win_queue_device();     // allocate the ring now (outside any capture)
 
 // One level's window, derived identically by every lane from the 4 per-wave boxes in LDS.
 struct LevelWindow {

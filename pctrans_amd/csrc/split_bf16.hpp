@@ -1,0 +1,70 @@
+// The split-bf16 arithmetic of the encoder's GEMMs (linear_k128_split.hip, linear_ln_split.hip, ffn_fused_split.hip,
+// conv1x1_split.hip), stated once.  Every fp32 number is EXACTLY the sum of three bf16 numbers
+//     a = a1 + a2 + a3,   a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)
+// and a product a.w is evaluated from its six leading partial products on the bf16 matrix cores with fp32 accumulation
+// (linear_k128_split.hip has the error analysis).  Tiling, staging and epilogues stay with the kernels; what they share is
+// the split, the order of the six products and the vector types -- the GEMMs agree bit for bit only while these agree.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace pct {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// (x, y) -> three packed bf16 pairs (low half = x's piece), x = x1 + x2 + x3 exactly
+__device__ __forceinline__ void split_bf16x3(const float x, const float y, unsigned &p1, unsigned &p2, unsigned &p3)
+{
+  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x, y}, bf16x2));               // v_cvt_pk_bf16_f32 (RNE)
+  const float rx = x - __uint_as_float(p1 << 16), ry = y - __uint_as_float(p1 & 0xffff0000u);   // exact
+  p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{rx, ry}, bf16x2));
+  const float sx = rx - __uint_as_float(p2 << 16), sy = ry - __uint_as_float(p2 & 0xffff0000u); // exact
+  p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{sx, sy}, bf16x2));
+}
+
+// One k-step of the product of w = w1 + w2 + w3 (A operand) and a = a1 + a2 + a3 (B operand): the six leading terms
+//     w1a1 | w1a2 + w2a1 | w2a2 + w1a3 + w3a1          (relative size 1 | 2^-9 | 2^-18)
+// Two accumulators: the w1a1 chain alone in `hi`, the five small terms in `lo`, so that the small terms are rounded at their
+// own magnitude and not at the product's; the caller adds hi + lo once at the end.  The order below is the order everywhere:
+// fp32 accumulation does not commute, and the kernels' results (tests/test_ffn_bitwise_gpu.py) are pinned to it.
+// The accumulator type selects the instruction: f32x16 v_mfma_f32_32x32x16_bf16, f32x4 v_mfma_f32_16x16x32_bf16.
+__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 w, bf16x8 a, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma_bf16(bf16x8 w, bf16x8 a, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, a, c, 0, 0, 0); }
+template <typename Acc>
+__device__ __forceinline__ void split_mfma6(const bf16x8 w1, const bf16x8 w2, const bf16x8 w3, const bf16x8 a1, const bf16x8 a2,
+                                            const bf16x8 a3, Acc &hi, Acc &lo)
+{
+  lo = mfma_bf16(w1, a3, lo);
+  hi = mfma_bf16(w1, a1, hi);
+  lo = mfma_bf16(w3, a1, lo);
+  lo = mfma_bf16(w2, a2, lo);
+  lo = mfma_bf16(w1, a2, lo);
+  lo = mfma_bf16(w2, a1, lo);
+}
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v)
+{
+  const int i = __float_as_int(v);
+  return __int_as_float(__builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, true));
+}
+
+// sum over the 32 lanes of each wave half (lanes 0-31 / 32-63); result valid in every lane of the half
+__device__ __forceinline__ float half_wave_sum(float v)
+{
+  v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+  v += dpp_mov<0x141>(v);   // row_half_mirror
+  v += dpp_mov<0x140>(v);   // row_mirror  -> every lane of a 16-lane row holds the row's sum
+  const int vi = __float_as_int(v);                                 // (readlane takes and returns the bit pattern)
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(vi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(vi, 16));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(vi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(vi, 48));
+  return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
+}
+
+}  // namespace pct

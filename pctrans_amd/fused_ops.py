@@ -68,18 +68,23 @@ def _x_add_ok(x, x_add):
             and x.numel() // x.shape[0] // 128 >= 32)
 
 
+def _x_add_rows(x_add):
+    """x_add -> (its rows as a 2-d tensor, their count = the period they repeat with over the rows of x); (None, 0) without."""
+    if x_add is None:
+        return None, 0
+    if x_add.shape[0] != 1 and x_add.stride(0) == 0:              # an expanded batch-1 tensor
+        x_add = x_add[:1]
+    a2 = _rows_2d(x_add)
+    return a2, a2.shape[0]
+
+
 def linear_k128(x, weight, bias=None, relu=False, x_add=None):
     """act((x + x_add) @ weight.T + bias) for in_features = 128 on the hand-written fp32 MFMA kernel
     (csrc/linear_k128.hip); x_add (shape of x, or batch 1 = shared by the images, or None) is summed on the way into
     the kernel's LDS tiles."""
     x2 = _rows_2d(x)
     rows, n = x2.shape[0], weight.shape[0]
-    a2, period = None, 0
-    if x_add is not None:
-        if x_add.shape[0] != 1 and x_add.stride(0) == 0:          # an expanded batch-1 tensor
-            x_add = x_add[:1]
-        a2 = _rows_2d(x_add)
-        period = a2.shape[0]
+    a2, period = _x_add_rows(x_add)
     out = torch.empty((rows, n), dtype=torch.float32, device=x.device)
     timed = _timing.timed("linear_k128 n=1024 relu", x2) if (n == 1024 and relu) else contextlib.nullcontext()
     with torch.cuda.device(x.device), timed:
@@ -147,12 +152,7 @@ def linear_k128_multi(x, layers, x_add=None):
     import ctypes
     x2 = _rows_2d(x)
     rows = x2.shape[0]
-    a2, period = None, 0
-    if x_add is not None:
-        if x_add.shape[0] != 1 and x_add.stride(0) == 0:
-            x_add = x_add[:1]
-        a2 = _rows_2d(x_add)
-        period = a2.shape[0]
+    a2, period = _x_add_rows(x_add)
     k = len(layers)
     outs = [torch.empty((rows, lin.out_features), dtype=torch.float32, device=x.device) for lin, _ in layers]
     vp, ll, ci = ctypes.c_void_p * k, ctypes.c_longlong * k, ctypes.c_int * k

@@ -35,9 +35,12 @@ def test_library_exports_every_declared_symbol():
 def test_kernel_sources_carry_no_build_switches_or_launch_overrides():
     """The shipped kernels are the only kernels: no compile-time switch can select another variant (the knock-out timing
     builds, which gave wrong results by design, are gone with them), and the environment selects nothing but the
-    documented kernel choices and the two test hooks."""
+    documented kernel choices and the two test hooks.  The glue between them is declared once: launchers.hpp alone holds the
+    prototypes of the launch_* / prepare_* functions and the value of the internal "not covered" status."""
     csrc = os.path.join(ROOT, "pctrans_amd", "csrc")
     names = set()
+    # a launch_* / prepare_* function declared at file scope and not defined (an explicit instantiation starts with `template`)
+    proto = re.compile(r"^(?!template\b)(?=\S)[\w:<>\*&, ]*?\b((?:launch|prepare)_\w+)\s*\([^;{}]*\)\s*;", re.M)
     for f in sorted(os.listdir(csrc)):
         if not f.endswith((".hip", ".hpp", ".h")):
             continue
@@ -45,6 +48,13 @@ def test_kernel_sources_carry_no_build_switches_or_launch_overrides():
         assert "PCT_EXPERIMENT_BUILD" not in src, f
         assert not re.search(r"#\s*ifn?def\s+(PCT|FZ)_", src), f
         names.update(re.findall(r"getenv\(\s*\"(\w+)\"", src))
+        if f == "launchers.hpp":
+            assert len(proto.findall(src)) >= 25 and re.search(r"PCT_NOT_COVERED = -100;", src), f
+            continue
+        assert not re.search(r"-\s*100\b", src), f
+        if f.endswith(".hip"):
+            assert not proto.findall(src), (f, proto.findall(src))
+            assert '#include "launchers.hpp"' in src, f
     assert names == {"PCT_MSDA_KERNEL", "PCT_MSDA_BWD_KERNEL", "PCT_WIN_QUEUE", "PCT_BCOL_FLAG_CAP", "PCT_LIN_KERNEL"}, names
     from pctrans_amd import _lib
     assert _lib.lib().pct_build_info() == b"target=gfx950"
