@@ -186,6 +186,10 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
                                                      void *workspace, void *up_logits, unsigned char *attn_mask,
                                                      void *stream);
 
+/* ---- opt-in entry points (no default call site of the head or of a training step reaches them): the backward of the fp32
+ * dynamic mask head.  Declared in a header of their own, which needs the definitions above -------------------------------- */
+#include "pctrans_hip_train.h"
+
 /* ---- fused residual add + LayerNorm:  out = LayerNorm(x + y) * gamma + beta  over the last dimension ----------
  * Replaces the `x + dropout(y)` / `nn.LayerNorm` pairs of the encoder and decoder layers in eval mode
  * (pixel_decoder/msdeformattn.py:116-131; transformer_decoder/mask2former_transformer_decoder.py:97-99, 179-181,

@@ -53,6 +53,14 @@ SYMBOLS = {
     "pct_dynamic_mask_head_forward": ([_vp, _vp, _vp] + [_i] * 10 + [_vp, _vp, _vp], _i),
 }
 
+# Entry points of opt-in paths: no default call site of the head or of a training step reaches them, so they are bound here and
+# not in SYMBOLS (whose compute entries are each checked at a default call site).  name -> (argtypes, restype, the test module
+# that checks the entry against float64)
+OPT_IN_SYMBOLS = {
+    "pct_dynamic_mask_head_backward_f32": ([_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _vp, _vp, _vp, _vp], _i,
+                                           "tests/test_dmh_train_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -69,7 +77,7 @@ def lib():
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).  "
             "pctrans_amd has no CPU / eager fallback for device tensors." % LIB_PATH)
     l = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in SYMBOLS.items():
+    for name, (argtypes, restype) in list(SYMBOLS.items()) + [(k, v[:2]) for k, v in OPT_IN_SYMBOLS.items()]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

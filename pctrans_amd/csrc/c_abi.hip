@@ -275,6 +275,31 @@ int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, const float
                                                     static_cast<hipStream_t>(stream)));
 }
 
+int pct_dynamic_mask_head_backward_f32(const float *mask_feat, const float *ref_points, const float *params,
+                                       const float *grad_up, int batch, int channels, int num_query, int height, int width,
+                                       int stride, int rel_coord, void *workspace, float *grad_feat, float *grad_ref,
+                                       float *grad_params, void *stream)
+{
+  if (batch < 0 || num_query < 0 || channels <= 0 || height <= 0 || width <= 0 || stride <= 0) return PCT_ERR_BAD_ARG;
+  if (!grad_feat && batch > 0) return PCT_ERR_BAD_ARG;
+  if (channels != 16) return PCT_ERR_UNSUPPORTED;
+  if (batch > 65535 || (long long)height * width >= 0x7fffffffLL / 64) return PCT_ERR_UNSUPPORTED;
+  if (batch == 0) return PCT_OK;
+  if (num_query == 0)        // no query: the feature gradient is zero, the other outputs are empty
+    return pct::launch_dyn_mask_head_bwd(mask_feat, ref_points, params, grad_up, batch, channels, 0, height, width, stride,
+                                         rel_coord, workspace, grad_feat, grad_ref, grad_params,
+                                         static_cast<hipStream_t>(stream));
+  if (!mask_feat || !params || !grad_up || !workspace || !grad_params || (rel_coord && (!ref_points || !grad_ref)))
+    return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)mask_feat | (uintptr_t)params | (uintptr_t)ref_points | (uintptr_t)grad_feat | (uintptr_t)grad_ref |
+       (uintptr_t)grad_params) & 3u)
+    return PCT_ERR_ALIGNMENT;
+  if (((uintptr_t)grad_up & 7u) || ((uintptr_t)workspace & 15u)) return PCT_ERR_ALIGNMENT;     // grad_up: 8-byte loads
+  return pct::launch_dyn_mask_head_bwd(mask_feat, ref_points, params, grad_up, batch, channels, num_query, height, width, stride,
+                                       rel_coord, workspace, grad_feat, grad_ref, grad_params,
+                                       static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

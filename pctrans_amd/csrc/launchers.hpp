@@ -85,6 +85,10 @@ int launch_dyn_mask_head_mfma(const float *feat, const float *ref, const float *
 int launch_dyn_mask_head_fused(const float *feat, const float *ref, const float *params, int N, int C, int Q, int H, int W,
                                int stride, int rel_coord, int th, int tw, void *workspace, void *up, unsigned char *amask,
                                hipStream_t stream);
+// backward of the fp32 forward (dyn_mask_head_bwd.hip): two or three launches, deterministic, partial sums in `workspace`
+int launch_dyn_mask_head_bwd(const float *feat, const float *ref, const float *params, const float *grad_up, int N, int C, int Q,
+                             int H, int W, int stride, int rel_coord, void *workspace, float *grad_feat, float *grad_ref,
+                             float *grad_params, hipStream_t stream);
 
 // ---- the encoder's GEMMs and norms.  epi: 0 = bias, 1 = bias + ReLU, 2 = residual + LayerNorm -------------------------
 int launch_linear_k128(const float *x, long long ldx, const float *x2, long long ldx2, long long x2_period, const float *w,

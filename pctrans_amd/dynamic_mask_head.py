@@ -1,6 +1,10 @@
 """Python entry of the fused dynamic mask head kernel (C ABI `pct_dynamic_mask_head_forward`,
-include/pctrans_hip.h; kernel pctrans_amd/csrc/dyn_mask_head.hip).  Forward only: when gradients are needed the
-decoder uses its differentiable batched formulation instead (mask2former_transformer_decoder.py in this package)."""
+include/pctrans_hip.h; kernel pctrans_amd/csrc/dyn_mask_head.hip) and of its backward
+(`pct_dynamic_mask_head_backward_f32`, include/pctrans_hip_train.h; csrc/dyn_mask_head_bwd.hip).  `dynamic_mask_head_forward` is forward only;
+`dynamic_mask_head_train` is the differentiable fp32 head: the same forward kernel, nothing saved but the three inputs, the
+MLP recomputed inside the backward kernel.  The decoder takes it when gradients are needed and its `dmh_train` switch is
+"hip" (PCT_DMH_TRAIN); otherwise it uses its differentiable batched torch formulation
+(mask2former_transformer_decoder.py in this package)."""
 import os
 
 import torch
@@ -12,6 +16,14 @@ _OUT = {torch.float32: 0, torch.bfloat16: 2}
 
 def supported(mask_feats, rel_coord=True):
     return mask_feats.is_cuda and mask_feats.dim() == 4 and mask_feats.shape[1] == 16
+
+
+def train_default():
+    """Process default of the decoder's `dmh_train` switch: PCT_DMH_TRAIN = hip | torch (default torch)."""
+    v = os.environ.get("PCT_DMH_TRAIN") or "torch"
+    if v not in ("hip", "torch"):
+        raise RuntimeError("PCT_DMH_TRAIN must be 'hip' or 'torch', got %r" % v)
+    return v
 
 
 def fused_geometry(H, W, target_size):
@@ -79,3 +91,76 @@ def dynamic_mask_head_forward(mask_feats, ref_xy, params, stride, rel_coord, tar
             torch.cuda.current_stream(mask_feats.device).cuda_stream)
     _lib.check(rc, "dynamic_mask_head_forward")
     return up, amask
+
+
+def backward_workspace_bytes(N, Q, H, W, G):
+    """include/pctrans_hip_train.h, pct_dynamic_mask_head_backward_f32: per-tile parameter partials + per-group feature partials."""
+    return 4 * N * (((H * W + 127) // 128) * Q * G + 8 * 16 * H * W)
+
+
+def dynamic_mask_head_backward(mask_feats, ref_xy, params, grad_up, stride, rel_coord):
+    """Backward of the fp32 `dynamic_mask_head_forward`.  mask_feats [N, 16, H, W]; ref_xy [N, Q, 2] (ignored without
+    rel_coord); params [N, Q, G]; grad_up [N, Q, 2H, 2W], the gradient of the upsampled logits.
+    -> (grad_feat [N, 16, H, W], grad_ref [N, Q, 2] or None without rel_coord, grad_params [N, Q, G]), fp32, contiguous.
+    Deterministic: two calls on the same operands give the same bits.  The C entry allocates nothing; this wrapper allocates
+    the outputs and the partial-sum workspace (up to 72 MB at 2 x 300 queries, 128 x 128) from torch's caching allocator per
+    call, which also works inside a graph capture (the capture's private pool)."""
+    if not mask_feats.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    N, C, H, W = mask_feats.shape
+    Q = params.shape[1]
+    G = (C + (2 if rel_coord else 0)) * 8 + 64 + 8 + 8 + 8 + 1
+    if params.shape != (N, Q, G):
+        raise RuntimeError("params must be [N, Q, %d], got %s" % (G, tuple(params.shape)))
+    if tuple(grad_up.shape) != (N, Q, 2 * H, 2 * W):
+        raise RuntimeError("grad_up must be [N, Q, 2H, 2W] = %s, got %s" % ((N, Q, 2 * H, 2 * W), tuple(grad_up.shape)))
+    feats = mask_feats.detach().float().contiguous()
+    prm = params.detach().float().contiguous()
+    gup = grad_up.detach().float().contiguous()
+    ref = ref_xy.detach().float().contiguous() if rel_coord else None
+    if rel_coord and tuple(ref.shape) != (N, Q, 2):
+        raise RuntimeError("ref_xy must be [N, Q, 2]")
+    dev = mask_feats.device
+    grad_feat = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
+    grad_params = torch.empty((N, Q, G), dtype=torch.float32, device=dev)
+    grad_ref = torch.empty((N, Q, 2), dtype=torch.float32, device=dev) if rel_coord else None
+    ws = torch.empty((max(backward_workspace_bytes(N, Q, H, W, G) // 4, 4),), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timing.timed("mask_head backward", feats):
+        rc = _lib.lib().pct_dynamic_mask_head_backward_f32(
+            feats.data_ptr(), ref.data_ptr() if rel_coord else None, prm.data_ptr(), gup.data_ptr(), N, C, Q, H, W,
+            int(stride), 1 if rel_coord else 0, ws.data_ptr(), grad_feat.data_ptr(),
+            grad_ref.data_ptr() if rel_coord else None, grad_params.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "dynamic_mask_head_backward")
+    return grad_feat, grad_ref, grad_params
+
+
+class DynamicMaskHeadFunction(torch.autograd.Function):
+    """fp32 dynamic mask head with a HIP backward: (mask_feats, ref_xy, params) -> (up_logits, attn_mask).  Saves its three
+    inputs and nothing else; the attention mask carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, mask_feats, ref_xy, params, stride, rel_coord, target_size):
+        up, amask = dynamic_mask_head_forward(mask_feats, ref_xy, params, stride, rel_coord, target_size,
+                                              out_dtype=torch.float32)
+        ctx.save_for_backward(mask_feats, ref_xy, params)
+        ctx.stride, ctx.rel_coord = int(stride), bool(rel_coord)
+        ctx.mark_non_differentiable(amask)
+        return up, amask
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_up, _grad_mask):
+        mask_feats, ref_xy, params = ctx.saved_tensors
+        grad_feat, grad_ref, grad_params = dynamic_mask_head_backward(mask_feats, ref_xy, params, grad_up, ctx.stride,
+                                                                      ctx.rel_coord)
+        need = ctx.needs_input_grad
+        return (grad_feat.to(mask_feats.dtype) if need[0] else None,
+                grad_ref.to(ref_xy.dtype) if need[1] and grad_ref is not None else None,
+                grad_params.to(params.dtype) if need[2] else None, None, None, None)
+
+
+def dynamic_mask_head_train(mask_feats, ref_xy, params, stride, rel_coord, target_size):
+    """Differentiable fp32 head: -> (up_logits fp32 [N, Q, 2H, 2W], attn_mask bool [N, Q, th*tw], no gradient).  Inputs may
+    be views (the decoder's transposed [Q, N, ...] tensors): autograd maps the contiguous gradients back."""
+    return DynamicMaskHeadFunction.apply(mask_feats, ref_xy, params, stride, rel_coord, target_size)

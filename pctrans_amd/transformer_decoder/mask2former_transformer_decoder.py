@@ -361,6 +361,9 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         self.in_channels = mask_dim
         self.dynamic_mask_channels = 8
         self.controller_layers = 3
+        # training path of the dynamic mask head: "torch" (differentiable batched formulation) or "hip" (the fp32 forward
+        # kernel with its HIP backward, where its conditions hold).  A plain attribute; process default from PCT_DMH_TRAIN
+        self.dmh_train = dmh.train_default()
         self.mask_out_stride = 4
         self.rel_coord = rel_coord
         ch = self.dynamic_mask_channels
@@ -535,6 +538,13 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             mask_logits, amask = dmh.dynamic_mask_head_forward(
                 mask_feats, reference_points.transpose(0, 1), params, mask_feat_stride, rel_coord,
                 attn_mask_target_size, out_dtype=out_dtype, feats_f32=_feats_f32)
+            return mask_logits, amask.unsqueeze(1)
+        if (needs_grad and self.dmh_train == "hip" and mask_feats.is_cuda and dmh.supported(mask_feats)
+                and self.controller_layers == 3 and mask_feats.dtype == torch.float32 and params.dtype == torch.float32
+                and reference_points.dtype == torch.float32 and not torch.is_autocast_enabled()):
+            # opt-in training path: the fp32 forward kernel + its HIP backward (saves the three inputs only)
+            mask_logits, amask = dmh.dynamic_mask_head_train(
+                mask_feats, reference_points.transpose(0, 1), params, mask_feat_stride, rel_coord, attn_mask_target_size)
             return mask_logits, amask.unsqueeze(1)
         mask_logits = self.mask_heads_forward_batched(
             mask_feats, reference_points.transpose(0, 1), params, mask_feat_stride, rel_coord)   # [N, Q, H, W]

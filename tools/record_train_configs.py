@@ -53,6 +53,10 @@ def build(c):
         targets.append({"masks": masks, "labels": torch.ones(G, dtype=torch.long, device="cuda"),
                         "fg_masks": (masks.sum(0) > 0).float(), "center_points": centers})
     opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=0.05)
+    if c.get("hip_mask_head"):
+        for m in model.modules():
+            if hasattr(m, "dmh_train"):
+                m.dmh_train = "hip"
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -70,57 +74,89 @@ def build(c):
     return model, step
 
 
-def main():
-    out = {"device": torch.cuda.get_device_name(0), "note": __doc__.split("\n\n")[0], "configs": {}}
+def selected_configs(argv):
     configs = dict(CONFIGS)
-    if "--graph-front" in sys.argv:
+    if "--graph-front" in argv:
         configs.update({k + " + graphed backbone / pixel decoder": dict(v, graph_front=True) for k, v in CONFIGS.items()})
-    if "--graph-decoder" in sys.argv:
+    if "--graph-decoder" in argv:
         configs.update({k + " + graphed decoder core": dict(v, graph_decoder=True) for k, v in CONFIGS.items()})
-    for name, c in configs.items():
-        model, step = build(c)
-        for _ in range(3):
-            step()
+    if "--hip-mask-head" in argv:           # every selected config again with the mask head's HIP training path
+        configs.update({k + " + HIP mask head": dict(v, hip_mask_head=True) for k, v in list(configs.items())})
+    return configs
+
+
+def record_one(name, c):
+    model, step = build(c)
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    steps = 10
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(steps):
+        total = step()
+    e1.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / steps * 1e3
+    ev = e0.elapsed_time(e1) / steps
+    peak_mib = round(torch.cuda.max_memory_allocated() / 2 ** 20)
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        step()
         torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        steps = 10
-        t0 = time.perf_counter()
-        e0.record()
-        for _ in range(steps):
-            total = step()
-        e1.record()
-        torch.cuda.synchronize()
-        wall = (time.perf_counter() - t0) / steps * 1e3
-        ev = e0.elapsed_time(e1) / steps
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            step()
-            torch.cuda.synchronize()
-        launches, dev_us, d2h = 0, 0.0, 0
-        top = {}
-        for e in prof.events():
-            if e.device_type == torch.autograd.DeviceType.CUDA:
-                launches += 1
-                dev_us += e.device_time if hasattr(e, "device_time") else e.cuda_time
-                key = e.name[:60]
-                top[key] = top.get(key, 0.0) + (e.device_time if hasattr(e, "device_time") else e.cuda_time)
-                if "Memcpy DtoH" in e.name or "DtoH" in e.name:
-                    d2h += 1
-        rec = dict(c, step_ms_wall=round(wall, 2), step_ms_hip_events=round(ev, 2), kernel_launches_per_step=launches,
-                   device_to_host_copies_per_step=d2h, device_ms_sum_of_kernels=round(dev_us / 1e3, 2),
-                   loss=float(total.detach()), samples_per_s_per_gpu=round(c["N"] / (wall / 1e3), 1),
-                   top_device_time_ms={k: round(v / 1e3, 2) for k, v in sorted(top.items(), key=lambda kv: -kv[1])[:12]})
-        out["configs"][name] = rec
-        print(name, json.dumps(rec), flush=True)
-        if c.get("graph_front") or c.get("graph_decoder"):
-            from pctrans_amd.graph import release_training_graphs
-            release_training_graphs(model)                # graphs destroyed now, not by a later collector pass inside a replay
-        del model, step, prof
-        import gc
-        gc.collect()
-        torch.cuda.empty_cache()
+    launches, dev_us, d2h = 0, 0.0, 0
+    top = {}
+    for e in prof.events():
+        if e.device_type == torch.autograd.DeviceType.CUDA:
+            launches += 1
+            dev_us += e.device_time if hasattr(e, "device_time") else e.cuda_time
+            key = e.name[:60]
+            top[key] = top.get(key, 0.0) + (e.device_time if hasattr(e, "device_time") else e.cuda_time)
+            if "Memcpy DtoH" in e.name or "DtoH" in e.name:
+                d2h += 1
+    rec = dict(c, max_memory_allocated_mib=peak_mib, step_ms_wall=round(wall, 2), step_ms_hip_events=round(ev, 2), kernel_launches_per_step=launches,
+               device_to_host_copies_per_step=d2h, device_ms_sum_of_kernels=round(dev_us / 1e3, 2),
+               loss=float(total.detach()), samples_per_s_per_gpu=round(c["N"] / (wall / 1e3), 1),
+               top_device_time_ms={k: round(v / 1e3, 2) for k, v in sorted(top.items(), key=lambda kv: -kv[1])[:12]})
+    if c.get("graph_front") or c.get("graph_decoder"):
+        from pctrans_amd.graph import release_training_graphs
+        release_training_graphs(model)                # graphs destroyed now, not by a later collector pass inside a replay
+    return rec
+
+
+def main():
+    """Every configuration is recorded in a child process of its own: a step's peak memory and the HIP runtime's graph
+    bookkeeping then owe nothing to the configurations recorded before it (one process that captured, released and captured
+    again across configurations ended in a segmentation fault at its third capture; graph.release_training_graphs documents
+    the same fragility).  `--rounds R` repeats the whole list R times, so that flag-off and flag-on steps alternate on one
+    machine; a child that fails ends the recording there with its exit status."""
+    import subprocess
+    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head")]
+    configs = selected_configs(flags)
+    if "--only" in sys.argv:
+        name = sys.argv[sys.argv.index("--only") + 1]
+        rec = record_one(name, configs[name])
+        rec["device"] = torch.cuda.get_device_name(0)
+        print("REC " + json.dumps(rec), flush=True)
+        return 0
+    rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 1
+    out = {"note": __doc__.split("\n\n")[0], "rounds": rounds, "configs": {name: [] for name in configs}}
+    for rnd in range(rounds):
+        for name in configs:
+            child = subprocess.run([sys.executable, "-X", "faulthandler", os.path.abspath(__file__), "--only", name] + flags,
+                                   stdout=subprocess.PIPE, text=True, timeout=600)
+            recs = [ln[4:] for ln in child.stdout.splitlines() if ln.startswith("REC ")]
+            if child.returncode != 0 or not recs:
+                print("round %d, %s: child ended with status %d" % (rnd, name, child.returncode), flush=True)
+                print("JSON " + json.dumps(out))
+                return child.returncode or 1
+            out["configs"][name].append(json.loads(recs[-1]))
+            print(rnd, name, recs[-1], flush=True)
     print("JSON " + json.dumps(out))
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
