@@ -189,6 +189,8 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 /* ---- opt-in entry points (no default call site of the head or of a training step reaches them): the backward of the fp32
  * dynamic mask head.  Declared in a header of their own, which needs the definitions above -------------------------------- */
 #include "pctrans_hip_train.h"
+/* ... and the instance post-processing of eval mode (logits -> label maps), behind MaskFormer.postprocess = "hip" */
+#include "pctrans_hip_post.h"
 
 /* ---- fused residual add + LayerNorm:  out = LayerNorm(x + y) * gamma + beta  over the last dimension ----------
  * Replaces the `x + dropout(y)` / `nn.LayerNorm` pairs of the encoder and decoder layers in eval mode

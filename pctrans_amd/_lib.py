@@ -61,6 +61,19 @@ OPT_IN_SYMBOLS = {
                                            "tests/test_dmh_train_gpu.py"),
 }
 
+# Entry points of the opt-in instance post-processing (include/pctrans_hip_post.h; pctrans_amd/postprocess.py, reached with
+# MaskFormer.postprocess = "hip").  A table of its own: SYMBOLS entries each have a default call site, OPT_IN_SYMBOLS is the
+# training header's.  name -> (argtypes, restype, the test module that checks the entry)
+_POST_MASKS = [_vp] + [_i] * 7 + [_vp, _vp, _vp]
+_POST_LABELS = [_vp] + [_i] * 7 + [_vp, _vp, _vp]
+POST_SYMBOLS = {
+    "pct_instance_masks_f32": (_POST_MASKS, _i, "tests/test_postprocess_gpu.py"),
+    "pct_instance_masks_bf16": (_POST_MASKS, _i, "tests/test_postprocess_gpu.py"),
+    "pct_instance_labels_from_bits": ([_vp, _vp] + [_i] * 5 + [_vp, _vp, _vp], _i, "tests/test_postprocess_gpu.py"),
+    "pct_instance_labels_f32": (_POST_LABELS, _i, "tests/test_postprocess_gpu.py"),
+    "pct_instance_labels_bf16": (_POST_LABELS, _i, "tests/test_postprocess_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -77,7 +90,8 @@ def lib():
             "(or `python -c 'import __graft_entry__ as g; g.build()'`).  "
             "pctrans_amd has no CPU / eager fallback for device tensors." % LIB_PATH)
     l = ctypes.CDLL(LIB_PATH)
-    for name, (argtypes, restype) in list(SYMBOLS.items()) + [(k, v[:2]) for k, v in OPT_IN_SYMBOLS.items()]:
+    for name, (argtypes, restype) in list(SYMBOLS.items()) + [
+            (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

@@ -11,6 +11,10 @@ Same results, different execution for the post-processing: per-
 O(Q^2) Python loops over mask pairs are replaced by one [Q, HW] x [HW, Q] GEMM (pairwise intersections / dice) and a
 greedy pass over that small matrix; the reference's debugging leftovers in the CVPPP branch (`io.imsave`,
 `pdb.set_trace()`, :305-306) are not reproduced.
+
+Opt-in (`MaskFormer.postprocess = "hip"`, process default PCT_POSTPROCESS): in eval mode the whole batch's post-processing runs
+on the device in one sequence of launches (pctrans_amd/postprocess.py, csrc/instance_post.hip); `instance_inference` below is
+the default and what that path is tested against.
 """
 from typing import List
 
@@ -18,6 +22,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from .. import postprocess as post
 from ..loss import Point_HungarianMatcher, SetCriterion
 from ..meta_arch.mask_former_head import MaskFormerHead
 
@@ -105,6 +110,9 @@ class MaskFormer(nn.Module):
         if not self.semantic_on:
             assert self.sem_seg_postprocess_before_inference
         self.dataset_name = dataset_name
+        # "torch": the formulation below; "hip": eval-mode post-processing on the device in one sequence of launches
+        # (pctrans_amd/postprocess.py) for device tensors and covered geometry.  Process default: PCT_POSTPROCESS.
+        self.postprocess = post.default()
 
     @classmethod
     def from_config(cls, cfg, backbone):
@@ -156,6 +164,11 @@ class MaskFormer(nn.Module):
             return losses
 
         outputs, _ = self.sem_seg_head(features)
+        if self.postprocess not in ("torch", "hip"):
+            raise ValueError("MaskFormer.postprocess must be 'torch' or 'hip', got %r" % (self.postprocess,))
+        if (self.postprocess == "hip" and self.instance_on
+                and post.supported(outputs["pred_masks"], volume.shape[-2:], self.dataset_name)):
+            return post.instance_labels(outputs["pred_masks"], volume.shape[-2:], self.dataset_name), None
         mask_pred_results = F.interpolate(outputs["pred_masks"], size=(volume.shape[-2], volume.shape[-1]),
                                           mode="bilinear", align_corners=False)
         del outputs

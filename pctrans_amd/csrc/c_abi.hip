@@ -110,9 +110,85 @@ int check_x_add(const float *x_add, long long ld_add, long long add_period)
   return PCT_OK;
 }
 
+// The arguments the instance post-processing entries share.  PCT_OK also for an empty call (batch == 0): the caller returns then.
+int check_instance_post(int batch, int num_query, int h, int w, int height, int width, int dataset)
+{
+  if (batch < 0 || num_query < 0 || h <= 0 || w <= 0 || height <= 0 || width <= 0 || (dataset != 0 && dataset != 1))
+    return PCT_ERR_BAD_ARG;
+  if ((long long)h * w >= 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
+  return pct::instance_geometry_status(batch, num_query, height, width);
+}
+
+int instance_masks_impl(const void *logits, int bf16, int batch, int num_query, int h, int w, int height, int width, int dataset,
+                        uint32_t *bits, int32_t *areas, void *stream)
+{
+  const int rc = check_instance_post(batch, num_query, h, w, height, width, dataset);
+  if (rc != PCT_OK || batch == 0 || num_query == 0) return rc;
+  if (!logits || !bits || !areas) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)logits & (bf16 ? 1u : 3u)) || ((uintptr_t)bits & 15u) || ((uintptr_t)areas & 3u)) return PCT_ERR_ALIGNMENT;
+  return pct::launch_instance_masks(logits, bf16, batch, num_query, h, w, height, width, dataset, bits, areas,
+                                    static_cast<hipStream_t>(stream));
+}
+
+// no query: every label is background
+int instance_labels_empty(int batch, int height, int width, int16_t *labels, void *stream)
+{
+  if (!labels) return PCT_ERR_BAD_ARG;
+  return (int)hipMemsetAsync(labels, 0, (size_t)batch * height * width * sizeof(int16_t), static_cast<hipStream_t>(stream));
+}
+
+int instance_labels_impl(const void *logits, int bf16, int batch, int num_query, int h, int w, int height, int width, int dataset,
+                         void *workspace, int16_t *labels, void *stream)
+{
+  const int rc = check_instance_post(batch, num_query, h, w, height, width, dataset);
+  if (rc != PCT_OK || batch == 0) return rc;
+  if (num_query == 0) return instance_labels_empty(batch, height, width, labels, stream);
+  if (!logits || !workspace || !labels) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)logits & (bf16 ? 1u : 3u)) || ((uintptr_t)workspace & 15u) || ((uintptr_t)labels & 1u)) return PCT_ERR_ALIGNMENT;
+  return pct::launch_instance_labels(logits, bf16, batch, num_query, h, w, height, width, dataset, workspace, labels,
+                                     static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" {
+
+int pct_instance_masks_f32(const float *logits, int batch, int num_query, int h, int w, int height, int width, int dataset,
+                           uint32_t *bits, int32_t *areas, void *stream)
+{
+  return instance_masks_impl(logits, 0, batch, num_query, h, w, height, width, dataset, bits, areas, stream);
+}
+
+int pct_instance_masks_bf16(const void *logits, int batch, int num_query, int h, int w, int height, int width, int dataset,
+                            uint32_t *bits, int32_t *areas, void *stream)
+{
+  return instance_masks_impl(logits, 1, batch, num_query, h, w, height, width, dataset, bits, areas, stream);
+}
+
+int pct_instance_labels_from_bits(const uint32_t *bits, const int32_t *areas, int batch, int num_query, int height, int width,
+                                  int dataset, void *workspace, int16_t *labels, void *stream)
+{
+  const int rc = check_instance_post(batch, num_query, 1, 1, height, width, dataset);
+  if (rc != PCT_OK || batch == 0) return rc;
+  if (num_query == 0) return instance_labels_empty(batch, height, width, labels, stream);
+  if (!bits || !areas || !workspace || !labels) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)bits & 15u) || ((uintptr_t)areas & 3u) || ((uintptr_t)workspace & 15u) || ((uintptr_t)labels & 1u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_instance_labels_from_bits(bits, areas, batch, num_query, height, width, dataset, workspace, labels,
+                                               static_cast<hipStream_t>(stream));
+}
+
+int pct_instance_labels_f32(const float *logits, int batch, int num_query, int h, int w, int height, int width, int dataset,
+                            void *workspace, int16_t *labels, void *stream)
+{
+  return instance_labels_impl(logits, 0, batch, num_query, h, w, height, width, dataset, workspace, labels, stream);
+}
+
+int pct_instance_labels_bf16(const void *logits, int batch, int num_query, int h, int w, int height, int width, int dataset,
+                             void *workspace, int16_t *labels, void *stream)
+{
+  return instance_labels_impl(logits, 1, batch, num_query, h, w, height, width, dataset, workspace, labels, stream);
+}
 
 int pct_abi_version(void) { return PCT_ABI_VERSION; }
 

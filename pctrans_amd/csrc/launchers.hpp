@@ -127,4 +127,13 @@ int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, co
 int launch_lsap(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
                 int *status, hipStream_t stream);
 
+// ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
+int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
+int launch_instance_masks(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, unsigned *bits,
+                          int *areas, hipStream_t stream);
+int launch_instance_labels_from_bits(const unsigned *bits, const int *areas, int N, int Q, int H, int W, int dataset,
+                                     void *workspace, short *labels, hipStream_t stream);
+int launch_instance_labels(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, void *workspace,
+                           short *labels, hipStream_t stream);
+
 }  // namespace pct
