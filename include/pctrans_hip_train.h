@@ -32,6 +32,62 @@ PCT_API int pct_dynamic_mask_head_backward_f32(const float *mask_feat, const flo
                                                int width, int stride, int rel_coord, void *workspace, float *grad_feat,
                                                float *grad_ref, float *grad_params, void *stream);
 
+/* ---- point-sampled mask losses (the matcher's and the criterion's point_sample + BCE + dice) --------------------------
+ * What the reference computes with detectron2's point_sample and its sigmoid_ce_loss / dice_loss
+ * (loss/matcher.py:70-222, loss/maskformer_criterion.py:23-116 and its loss_masks).  Sampling is
+ * F.grid_sample(input, 2c - 1, mode="bilinear", padding_mode="zeros", align_corners=False) on fp32 planes in fp32:
+ * x = c_x * width - 0.5, y = c_y * height - 0.5, taps at floor and floor + 1, a tap outside the plane contributes zero; a
+ * coordinate of any value (outside [0, 1], NaN) reads nothing outside its plane.  Planes are contiguous [n, height, width];
+ * coordinates are (x, y) pairs, 8-byte aligned; every other pointer is 4-byte aligned.  An index array is int32 on the device
+ * and may be NULL (identity: entry k is plane k); an index outside its planes gives NaN for that row and reads nothing.
+ * Each call is one launch on `stream`, no workspace, no host synchronisation, no floating-point atomic; every sum runs in a
+ * fixed order: results are bit-identical from call to call.  Calls may be recorded into a HIP graph.
+ * Status: a negative count, non-positive size or missing pointer PCT_ERR_BAD_ARG; misaligned pointer PCT_ERR_ALIGNMENT;
+ * geometry outside what is covered PCT_ERR_UNSUPPORTED (callers keep their torch formulation); num_out / num_pairs == 0 or
+ * num_points == 0: PCT_OK, nothing is launched and nothing is written.
+ *
+ * Gather.  out[k, p] = sample of plane plane_index[k] of planes [num_planes, height, width] at
+ * coords[k / planes_per_coord_row, p, :];  coords [coord_rows, num_points, 2], out [num_out, num_points].
+ * planes_per_coord_row >= 1: the matcher passes its query (target) count, one coordinate row serving a whole image; the
+ * criterion passes 1.  Covered: height * width < 2^31 - 1 and num_out * ceil(num_points / 256) < 2^31 - 1. */
+PCT_API int pct_point_sample_f32(const float *planes, const int32_t *plane_index, const float *coords, int num_planes, int height,
+                                 int width, int num_out, int num_points, int coord_rows, int planes_per_coord_row, float *out,
+                                 void *stream);
+
+/* Loss forward.  For pair k: x[k, p] = sample of plane src_index[k] of pred [num_pred_planes, height, width] and
+ * t[k, p] = sample of plane tgt_index[k] of tgt [num_tgt_planes, tgt_height, tgt_width], both at coords[k, p, :]
+ * (coords [num_pairs, num_points, 2]; x, t [num_pairs, num_points], kept by the caller for the backward), and
+ *   sums[k, 0..3] = sum_p bce(x, t),  sum_p sigma(x) t,  sum_p sigma(x),  sum_p t
+ * with bce(x, t) = max(x, 0) - x t + log1p(exp(-|x|)), torch's binary_cross_entropy_with_logits.  One workgroup per pair:
+ * each thread sums its points in ascending order, the threads are summed by a fixed tree.
+ * Covered: what the backward covers for (height, width), and tgt_height * tgt_width < 2^31 - 1. */
+PCT_API int pct_point_mask_loss_forward_f32(const float *pred, const int32_t *src_index, int num_pred_planes, int height,
+                                            int width, const float *tgt, const int32_t *tgt_index, int num_tgt_planes,
+                                            int tgt_height, int tgt_width, const float *coords, int num_pairs, int num_points,
+                                            float *x, float *t, float *sums, void *stream);
+
+/* Loss backward.  From x, t, coords of the forward and three per-pair coefficient vectors on the device, alpha, beta,
+ * gamma [num_pairs] (for loss_mask = sum_k sums[k,0] / P / M and loss_dice = sum_k (1 - N_k / D_k) / M with
+ * N_k = 2 sums[k,1] + 1, D_k = sums[k,2] + sums[k,3] + 1 and incoming gradients g_m, g_d:  alpha = g_m / (P M),
+ * beta_k = g_d N_k / (D_k^2 M), gamma_k = 2 g_d / (D_k M)):
+ *   grad_x[k, p] = alpha_k (sigma(x) - t) + sigma(x) (1 - sigma(x)) (beta_k - gamma_k t)
+ * scattered to the four taps of point p with its bilinear weights into grad_planes [num_pairs, height, width]: compact (plane
+ * k belongs to pair k), fully overwritten, so no zero-fill is needed before the call.
+ * Fixed point instead of floating-point atomics: one workgroup per (pair, band of 32 rows) holds a signed 64-bit accumulator
+ * per band pixel in LDS, adds round(w * grad_x * s) with workgroup-scope integer adds -- independent of their order -- and
+ * stores float(sum) / s.  The scale is a power of two taken per pair on the device from
+ *   bound_k = |alpha_k| + (|beta_k| + |gamma_k|) / 4  >=  |grad_x[k, p]|     (labels in [0, 1])
+ *   bound_k = m 2^e, m in [0.5, 1):  s = 2^(30 - e), the exponent clamped to [-126, 126]
+ * so that one contribution is below 2^30 (1 + 2^-20) in magnitude and the at most 2^31 - 1 contributions one pixel can receive
+ * cannot overflow 63 bits.  Quantisation: a contribution moves by at most half a quantum, 1 / (2 s) <= bound_k 2^-30 (or 2^-127
+ * where the clamp holds); a pixel that receives n contributions differs from the exact sum of its fp32 products by at most
+ * n bound_k 2^-30, plus the one rounding of the conversion back to fp32.  Non-finite coefficients give a NaN plane.
+ * Covered: width <= 256 (32 rows of 64-bit accumulators in 64 KiB of LDS), height * width < 2^31 - 1,
+ * num_pairs * ceil(height / 32) < 2^31 - 1. */
+PCT_API int pct_point_mask_loss_backward_f32(const float *x, const float *t, const float *coords, const float *alpha,
+                                             const float *beta, const float *gamma, int num_pairs, int num_points, int height,
+                                             int width, float *grad_planes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,10 @@ SYMBOLS = {
 OPT_IN_SYMBOLS = {
     "pct_dynamic_mask_head_backward_f32": ([_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _vp, _vp, _vp, _vp], _i,
                                            "tests/test_dmh_train_gpu.py"),
+    "pct_point_sample_f32": ([_vp, _vp, _vp] + [_i] * 7 + [_vp, _vp], _i, "tests/test_point_loss_gpu.py"),
+    "pct_point_mask_loss_forward_f32": ([_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp], _i,
+                                        "tests/test_point_loss_gpu.py"),
+    "pct_point_mask_loss_backward_f32": ([_vp] * 6 + [_i] * 4 + [_vp, _vp], _i, "tests/test_point_loss_gpu.py"),
 }
 
 # Entry points of the opt-in instance post-processing (include/pctrans_hip_post.h; pctrans_amd/postprocess.py, reached with

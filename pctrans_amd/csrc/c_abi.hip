@@ -376,6 +376,53 @@ int pct_dynamic_mask_head_backward_f32(const float *mask_feat, const float *ref_
                                        static_cast<hipStream_t>(stream));
 }
 
+int pct_point_sample_f32(const float *planes, const int32_t *plane_index, const float *coords, int num_planes, int height,
+                         int width, int num_out, int num_points, int coord_rows, int planes_per_coord_row, float *out,
+                         void *stream)
+{
+  if (num_planes < 0 || height <= 0 || width <= 0 || num_out < 0 || num_points < 0 || coord_rows < 0 || planes_per_coord_row < 1)
+    return PCT_ERR_BAD_ARG;
+  if (num_out == 0 || num_points == 0) return PCT_OK;
+  if (!planes || !coords || !out || num_planes == 0 || (num_out - 1) / planes_per_coord_row >= coord_rows) return PCT_ERR_BAD_ARG;
+  if (!plane_index && num_out > num_planes) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)planes | (uintptr_t)plane_index | (uintptr_t)out) & 3u) || ((uintptr_t)coords & 7u)) return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_sample(planes, plane_index, coords, num_planes, height, width, num_out, num_points,
+                                  planes_per_coord_row, out, static_cast<hipStream_t>(stream));
+}
+
+int pct_point_mask_loss_forward_f32(const float *pred, const int32_t *src_index, int num_pred_planes, int height, int width,
+                                    const float *tgt, const int32_t *tgt_index, int num_tgt_planes, int tgt_height,
+                                    int tgt_width, const float *coords, int num_pairs, int num_points, float *x, float *t,
+                                    float *sums, void *stream)
+{
+  if (num_pred_planes < 0 || num_tgt_planes < 0 || height <= 0 || width <= 0 || tgt_height <= 0 || tgt_width <= 0 ||
+      num_pairs < 0 || num_points < 0)
+    return PCT_ERR_BAD_ARG;
+  if (num_pairs == 0 || num_points == 0) return PCT_OK;
+  if (!pred || !tgt || !coords || !x || !t || !sums || num_pred_planes == 0 || num_tgt_planes == 0) return PCT_ERR_BAD_ARG;
+  if ((!src_index && num_pairs > num_pred_planes) || (!tgt_index && num_pairs > num_tgt_planes)) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)pred | (uintptr_t)src_index | (uintptr_t)tgt | (uintptr_t)tgt_index | (uintptr_t)x | (uintptr_t)t |
+        (uintptr_t)sums) & 3u) || ((uintptr_t)coords & 7u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_loss_forward(pred, src_index, num_pred_planes, height, width, tgt, tgt_index, num_tgt_planes,
+                                        tgt_height, tgt_width, coords, num_pairs, num_points, x, t, sums,
+                                        static_cast<hipStream_t>(stream));
+}
+
+int pct_point_mask_loss_backward_f32(const float *x, const float *t, const float *coords, const float *alpha, const float *beta,
+                                     const float *gamma, int num_pairs, int num_points, int height, int width,
+                                     float *grad_planes, void *stream)
+{
+  if (num_pairs < 0 || num_points < 0 || height <= 0 || width <= 0) return PCT_ERR_BAD_ARG;
+  if (num_pairs == 0 || num_points == 0) return PCT_OK;
+  if (!x || !t || !coords || !alpha || !beta || !gamma || !grad_planes) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)x | (uintptr_t)t | (uintptr_t)alpha | (uintptr_t)beta | (uintptr_t)gamma | (uintptr_t)grad_planes) & 3u) ||
+      ((uintptr_t)coords & 7u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_loss_backward(x, t, coords, alpha, beta, gamma, num_pairs, num_points, height, width, grad_planes,
+                                         static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

@@ -127,6 +127,16 @@ int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, co
 int launch_lsap(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
                 int *status, hipStream_t stream);
 
+// ---- point-sampled mask losses (point_loss.hip; include/pctrans_hip_train.h).  An index array may be nullptr (identity);
+// PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover -----------------------------------------
+int launch_point_sample(const float *planes, const int *plane_index, const float *coords, int num_planes, int H, int W, int K,
+                        int P, int per_row, float *out, hipStream_t stream);
+int launch_point_loss_forward(const float *pred, const int *src_index, int num_pred, int H, int W, const float *tgt,
+                              const int *tgt_index, int num_tgt, int Ht, int Wt, const float *coords, int K, int P, float *x,
+                              float *t, float *sums, hipStream_t stream);
+int launch_point_loss_backward(const float *x, const float *t, const float *coords, const float *alpha, const float *beta,
+                               const float *gamma, int K, int P, int H, int W, float *grad_planes, hipStream_t stream);
+
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
 int launch_instance_masks(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, unsigned *bits,

@@ -12,6 +12,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
+from .. import point_loss as _point_loss
 from .point_features import get_uncertain_point_coords_with_randomness, point_sample
 
 
@@ -138,9 +139,61 @@ class SetCriterion(nn.Module):
         self.num_points = num_points
         self.oversample_ratio = oversample_ratio
         self.importance_sample_ratio = importance_sample_ratio
+        # "torch": loss_masks as the reference writes it.  "hip": the point-sampled losses on the device kernels of
+        # pctrans_amd/point_loss.py where their conditions hold (CUDA fp32 predictions, target masks of one size, covered
+        # geometry), the code below otherwise.  A plain attribute; process default from PCT_POINT_LOSS
+        self.point_loss = _point_loss.default()
+        self._target_planes = None
+
+    def _hip_target_planes(self, targets, like):
+        """The images' target masks as one fp32 [sum G, Ht, Wt] tensor and each image's first plane, or None when the masks
+        differ in size.  Kept for the calls that follow with the same masks (the ten predictions of a step)."""
+        masks = [t["masks"] for t in targets]
+        if not masks or len({tuple(m.shape[-2:]) for m in masks}) != 1 or any(m.dim() != 3 or m.device != like.device for m in masks):
+            return None
+        key = tuple((m.data_ptr(), m._version, tuple(m.shape), m.dtype) for m in masks)
+        if self._target_planes is None or self._target_planes[0] != key:
+            planes = torch.cat(masks).to(torch.float32).contiguous()
+            starts = [0]
+            for m in masks[:-1]:
+                starts.append(starts[-1] + m.shape[0])
+            self._target_planes = (key, planes, starts, masks)            # (the masks: their addresses stay theirs while kept)
+        return self._target_planes[1], self._target_planes[2]
+
+    def _loss_masks_hip(self, pred, targets, indices, num_masks):
+        """loss_masks on the device kernels: the same torch.rand calls in the same order, the 3 P oversampled logits from the
+        gather, torch's topk, then BCE + dice and their backward in one kernel each.  None when the conditions do not hold."""
+        if not (torch.is_tensor(pred) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 4 and pred.is_contiguous()):
+            return None
+        got = self._hip_target_planes(targets, pred)
+        if got is None or not _point_loss.loss_supported(pred, got[0]):
+            return None
+        planes, starts = got
+        Q = pred.shape[1]
+        src = torch.cat([s.to(pred.device) + b * Q for b, (s, _) in enumerate(indices)])
+        tgt = torch.cat([t.to(pred.device) + starts[b] for b, (_, t) in enumerate(indices)])
+        K = int(src.shape[0])
+        if K == 0:
+            return None
+        num_sampled = int(self.num_points * self.oversample_ratio)
+        num_uncertain = int(self.importance_sample_ratio * self.num_points)
+        num_random = self.num_points - num_uncertain
+        with torch.no_grad():
+            coords = torch.rand(K, num_sampled, 2, device=pred.device)
+            logits = _point_loss.point_sample_planes(pred, src, coords, 1)
+            idx = torch.topk(calculate_uncertainty(logits[:, None])[:, 0, :], k=num_uncertain, dim=1)[1]
+            coords = torch.gather(coords, 1, idx[:, :, None].expand(-1, -1, 2))
+            if num_random > 0:
+                coords = torch.cat([coords, torch.rand(K, num_random, 2, device=pred.device)], dim=1)
+        loss_mask, loss_dice = _point_loss.point_mask_losses(pred, src, planes, tgt, coords, num_masks)
+        return {"loss_mask": loss_mask, "loss_dice": loss_dice}
 
     def loss_masks(self, outputs, targets, indices, num_masks):
         assert "pred_masks" in outputs
+        if self.point_loss == "hip":
+            got = self._loss_masks_hip(outputs["pred_masks"], targets, indices, num_masks)
+            if got is not None:
+                return got
         src_idx = self._get_src_permutation_idx(indices)
         tgt_idx = self._get_tgt_permutation_idx(indices)
         src_masks = outputs["pred_masks"][src_idx]

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 from scipy.optimize import linear_sum_assignment
 from torch import nn
 
+from .. import point_loss as _point_loss
 from .point_features import point_sample
 
 
@@ -39,6 +40,9 @@ class Point_HungarianMatcher(nn.Module):
         self.device_lsap = True            # CUDA inputs: assign on the device; False = scipy on the host (reference)
         self.batch_images = True           # one cost pass for the whole batch when the target masks share a size
         self.pending_status = []
+        # "torch": point_sample as the reference calls it.  "hip": the batched costs gather their points with the device
+        # kernel where it applies (CUDA fp32 contiguous masks).  A plain attribute; process default from PCT_POINT_LOSS
+        self.point_sample = _point_loss.default()
 
     def _batched_costs(self, outputs, targets):
         """All images of the batch in one pass -- when their target masks share one size: the predicted masks are the
@@ -59,8 +63,14 @@ class Point_HungarianMatcher(nn.Module):
             tgt = pred.new_zeros((bs, gmax) + next(iter(sizes)))
             for b, t in enumerate(targets):
                 tgt[b, :counts[b]] = t["masks"]
-        tgt_pts = point_sample(tgt, coords, align_corners=False)                # [B, Gmax, P]
-        out_pts = point_sample(pred, coords, align_corners=False)               # [B, Q, P]
+        if (self.point_sample == "hip" and pred.dtype == torch.float32 and _point_loss.sample_supported(pred)
+                and _point_loss.sample_supported(tgt)):
+            # the device gather (pctrans_amd/point_loss.py): one coordinate row serves an image's Gmax / Q planes
+            tgt_pts = _point_loss.point_sample_planes(tgt, None, coords, gmax).view(bs, gmax, -1)
+            out_pts = _point_loss.point_sample_planes(pred, None, coords, num_queries).view(bs, num_queries, -1)
+        else:
+            tgt_pts = point_sample(tgt, coords, align_corners=False)                # [B, Gmax, P]
+            out_pts = point_sample(pred, coords, align_corners=False)               # [B, Q, P]
         with torch.autocast(device_type=pred.device.type, enabled=False):
             out_pts, tgt_pts = out_pts.float(), tgt_pts.float()
             hw = out_pts.shape[2]

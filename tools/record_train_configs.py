@@ -57,6 +57,8 @@ def build(c):
         for m in model.modules():
             if hasattr(m, "dmh_train"):
                 m.dmh_train = "hip"
+    if c.get("hip_point_loss"):
+        model.criterion.point_loss = model.criterion.matcher.point_sample = "hip"
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -82,6 +84,8 @@ def selected_configs(argv):
         configs.update({k + " + graphed decoder core": dict(v, graph_decoder=True) for k, v in CONFIGS.items()})
     if "--hip-mask-head" in argv:           # every selected config again with the mask head's HIP training path
         configs.update({k + " + HIP mask head": dict(v, hip_mask_head=True) for k, v in list(configs.items())})
+    if "--hip-point-loss" in argv:          # and again with the point-sampled losses and the matcher's gather on the device
+        configs.update({k + " + HIP point loss": dict(v, hip_point_loss=True) for k, v in list(configs.items())})
     return configs
 
 
@@ -133,7 +137,7 @@ def main():
     the same fragility).  `--rounds R` repeats the whole list R times, so that flag-off and flag-on steps alternate on one
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
-    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head")]
+    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss")]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
