@@ -88,6 +88,28 @@ PCT_API int pct_point_mask_loss_backward_f32(const float *x, const float *t, con
                                              const float *beta, const float *gamma, int num_pairs, int num_points, int height,
                                              int width, float *grad_planes, void *stream);
 
+/* Uncertain-point selection (the criterion's get_uncertain_point_coords_with_randomness without its gather, topk, gather and
+ * cat).  For pair k and candidate s, x = sample of plane src_index[k] of pred [num_pred_planes, height, width] at
+ * cand_coords[k, s, :] (cand_coords [num_pairs, num_cand, 2]), computed by the gather's code: bit-identical to what
+ * pct_point_sample_f32 returns for that plane and coordinate.  It is never written to memory.  The uncertainty is -|x|
+ * (calculate_uncertainty); the key of a candidate is the bit pattern of |x| as an unsigned 32-bit integer (+0 and -0 tie), and
+ * 0 for a NaN x (torch.topk ranks a NaN above every number: NaN counts as most uncertain).
+ * The num_keep candidates with the smallest keys are selected; among the candidates whose key equals the num_keep-th smallest
+ * the ones with the lowest candidate numbers are taken.  The selected candidates are written in ascending candidate number:
+ * their coordinates, copied bit for bit, to out_coords[k, 0 .. num_keep), row k starting at out_coords + k * out_row_points * 2
+ * (out_row_points >= num_keep; the points num_keep .. out_row_points of a row are not touched: the caller's fresh uniform
+ * points live there), and their numbers to out_index [num_pairs, num_keep] unless it is NULL.  A row whose src_index is outside
+ * the planes gets NaN coordinates and numbers -1.  cand_coords and out_coords are 8-byte aligned.
+ * One workgroup of 1024 threads per pair: the keys stay in registers, a radix select (four 8-bit passes over LDS histograms,
+ * integer adds) finds the num_keep-th smallest key and how many of its equals are admitted, one scan in candidate order
+ * places the selected ones.  No sort, no workspace; everything is a function of the inputs alone.
+ * Status, beyond the common rules: num_keep > num_cand or out_row_points < num_keep PCT_ERR_BAD_ARG; num_pairs == 0 or
+ * num_keep == 0 PCT_OK with nothing launched.
+ * Covered: num_cand <= 65536 (64 keys per thread) and height * width < 2^31 - 1. */
+PCT_API int pct_point_select_uncertain_f32(const float *pred, const int32_t *src_index, int num_pred_planes, int height,
+                                           int width, const float *cand_coords, int num_pairs, int num_cand, int num_keep,
+                                           float *out_coords, int out_row_points, int32_t *out_index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

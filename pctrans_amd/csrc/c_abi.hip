@@ -423,6 +423,23 @@ int pct_point_mask_loss_backward_f32(const float *x, const float *t, const float
                                          static_cast<hipStream_t>(stream));
 }
 
+int pct_point_select_uncertain_f32(const float *pred, const int32_t *src_index, int num_pred_planes, int height, int width,
+                                   const float *cand_coords, int num_pairs, int num_cand, int num_keep, float *out_coords,
+                                   int out_row_points, int32_t *out_index, void *stream)
+{
+  if (num_pred_planes < 0 || height <= 0 || width <= 0 || num_pairs < 0 || num_cand < 0 || num_keep < 0 || num_keep > num_cand ||
+      out_row_points < num_keep)
+    return PCT_ERR_BAD_ARG;
+  if (num_pairs == 0 || num_keep == 0) return PCT_OK;
+  if (!pred || !cand_coords || !out_coords || num_pred_planes == 0) return PCT_ERR_BAD_ARG;
+  if (!src_index && num_pairs > num_pred_planes) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)pred | (uintptr_t)src_index | (uintptr_t)out_index) & 3u) ||
+      (((uintptr_t)cand_coords | (uintptr_t)out_coords) & 7u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_select(pred, src_index, num_pred_planes, height, width, cand_coords, num_pairs, num_cand, num_keep,
+                                  out_coords, out_row_points, out_index, static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

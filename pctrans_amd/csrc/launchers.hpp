@@ -136,6 +136,8 @@ int launch_point_loss_forward(const float *pred, const int *src_index, int num_p
                               float *t, float *sums, hipStream_t stream);
 int launch_point_loss_backward(const float *x, const float *t, const float *coords, const float *alpha, const float *beta,
                                const float *gamma, int K, int P, int H, int W, float *grad_planes, hipStream_t stream);
+int launch_point_select(const float *pred, const int *src_index, int num_pred, int H, int W, const float *cand_coords, int K, int S,
+                        int num_keep, float *out_coords, int out_row_points, int *out_index, hipStream_t stream);
 
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED

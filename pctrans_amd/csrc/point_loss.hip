@@ -1,7 +1,8 @@
 // Point-sampled mask losses (include/pctrans_hip_train.h: pct_point_sample_f32, pct_point_mask_loss_forward_f32,
-// pct_point_mask_loss_backward_f32): the gather, the fused BCE + dice sums and the scatter of their gradient that
-// loss/matcher.py and loss/maskformer_criterion.py otherwise run as grid_sample forward / backward plus elementwise and reduce
-// launches.
+// pct_point_mask_loss_backward_f32, pct_point_select_uncertain_f32): the gather, the fused BCE + dice sums and the scatter of
+// their gradient that loss/matcher.py and loss/maskformer_criterion.py otherwise run as grid_sample forward / backward plus
+// elementwise and reduce launches, and the choice of the most uncertain of the oversampled candidates that the criterion
+// otherwise makes with a gather, topk, gather and cat.
 //
 // Sampling is F.grid_sample(input, 2c - 1, "bilinear", "zeros", align_corners=False): x = c_x * W - 0.5 (one fma),
 // y = c_y * H - 0.5, taps at floor and floor + 1, weights (1 - tx)(1 - ty) .. tx ty, a tap outside the plane adds nothing.
@@ -32,6 +33,9 @@ constexpr int PL_MAX_WIDTH = 256;     // 32 rows x 256 pixels x 8 B = 64 KiB of 
 constexpr int PL_GATHER_BLOCK = 256;
 constexpr int PL_FWD_BLOCK = 1024;
 constexpr int PL_BWD_BLOCK = 512;
+constexpr int PL_SELECT_BLOCK = 1024;
+constexpr int PL_SELECT_MAX_CAND = 65536;   // 64 keys per thread in registers (pctrans_amd/point_loss.py: MAX_CANDIDATES)
+constexpr int PL_SELECT_COPIES = 32;        // copies of the digit histogram: one per LDS bank
 
 struct Taps {
   int x0, y0;
@@ -196,6 +200,178 @@ __global__ __launch_bounds__(PL_BWD_BLOCK) void point_loss_backward_kernel(
   for (int i = threadIdx.x; i < cells; i += PL_BWD_BLOCK) out[i] = (float)(long long)acc[i] * inv_scale;
 }
 
+// Selection of the num_keep most uncertain (smallest |logit|) of S candidates, one workgroup per pair, no sort and the logits
+// never in memory.  key = bits of |x| (NaN: 0); unsigned order of the keys is the order of |x|.
+//
+// Candidates are dealt to the threads strided: round i, thread t holds candidate i * 1024 + t, so a wave's coordinate loads
+// and stores are contiguous.  A blocked deal (thread t holds IPT consecutive candidates) would give each thread one run of
+// candidate order and so one scan of per-thread counts, but 8-byte loads IPT * 8 bytes apart.  The strided deal keeps one scan
+// as well: in round i the 64 candidates of a wave are consecutive, their order inside the wave is the lane order (a ballot
+// and a population count of the lanes below), and the (round, wave) cells in ascending order are the candidate order.  So
+// one workgroup-wide exclusive scan over the IPT * 16 <= 1024 cell counts, one cell per thread, places every candidate.
+//
+// 1. Every thread samples its IPT candidates (make_taps / sample_plane: the gather's code, the gather's bits) and keeps the
+//    keys in registers; every loop over them is fully unrolled.  A thread's samples run one after the other (the taps sit
+//    behind their bounds tests): this, not a throughput limit, is what the kernel's time is made of.
+// 2. Radix select, most significant byte first, four passes.  A pass counts the byte of the keys that agree with the bytes
+//    chosen so far in a 256-bin LDS histogram, finds the bin that holds rank `rank` and descends into it.  The histogram has
+//    PL_SELECT_COPIES = 32 copies laid out [bin][copy] with copy = lane & 31: the 32 lanes the LDS serves together hit 32
+//    different banks whatever their bins, so the adds (integer, workgroup scope, order-free) never conflict, also when every
+//    key falls in one bin (an all-zero plane; logits of one exponent).  The copies are summed by all threads (bin t / 4, eight
+//    copies each, rotated by the bin so that the 32 lanes again read 32 banks) and cleared for the next pass; wave 0 scans the
+//    256 totals.  After the last pass `key_t` is the num_keep-th smallest key and `rank` the number of candidates equal to
+//    it that are admitted: the first `rank` of them in candidate order.
+// 3. Ballots of key < key_t and key == key_t per round and wave, the scan of their counts, and for candidate s with `lb` lower
+//    and `eb` equal keys before it:  selected = lower or (equal and eb < rank),  position = lb + min(eb, rank).
+template <int IPT>
+__global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_kernel(const float *__restrict__ pred,
+                                                                       const int *__restrict__ src_index, const int num_pred,
+                                                                       const int H, const int W, const float2 *__restrict__ cand,
+                                                                       const int S, const int num_keep, float2 *__restrict__ out,
+                                                                       const int out_row_points, int *__restrict__ out_index)
+{
+  constexpr int WAVES = PL_SELECT_BLOCK / 64, CELLS = IPT * WAVES;
+  static_assert(CELLS <= PL_SELECT_BLOCK && IPT * PL_SELECT_BLOCK <= PL_SELECT_MAX_CAND, "one scan cell per thread");
+  __shared__ unsigned hist[256 * PL_SELECT_COPIES];
+  __shared__ unsigned total[256];
+  __shared__ unsigned cell[2][PL_SELECT_BLOCK];                            // lower / equal keys per (round, wave), then before it
+  __shared__ unsigned wave_sum[2][WAVES];
+  __shared__ unsigned pick[2];                                             // the chosen bin and the rank inside it
+  const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int plane = src_index ? src_index[k] : k;
+  float2 *orow = out + (size_t)k * out_row_points;
+  int *irow = out_index ? out_index + (size_t)k * num_keep : nullptr;
+  if (!((unsigned)plane < (unsigned)num_pred)) {                           // an index outside the planes: loud, and no access
+    const float nan = __builtin_nanf("");
+    for (int p = tid; p < num_keep; p += PL_SELECT_BLOCK) {
+      orow[p] = make_float2(nan, nan);
+      if (irow) irow[p] = -1;
+    }
+    return;
+  }
+  const float *pp = pred + (size_t)plane * H * W;
+  const float2 *crow = cand + (size_t)k * S;
+
+  for (int i = tid; i < 256 * PL_SELECT_COPIES; i += PL_SELECT_BLOCK) hist[i] = 0u;
+  unsigned key[IPT];                                                       // 0xffffffff past S: above every key, in no later pass
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    key[i] = 0xffffffffu;
+    if (tid < S - i * PL_SELECT_BLOCK) {
+      const float2 c = (crow + i * PL_SELECT_BLOCK)[threadIdx.x];          // a uniform base and one 32-bit lane offset
+      const unsigned bits = __float_as_uint(sample_plane(pp, make_taps(c.x, c.y, H, W), H, W)) & 0x7fffffffu;
+      key[i] = bits > 0x7f800000u ? 0u : bits;
+    }
+  }
+  __syncthreads();
+
+  unsigned key_t = 0u, rank = (unsigned)num_keep;                          // rank counts from 1 among the keys that agree with key_t
+#pragma unroll
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    const unsigned above = shift == 24 ? 0u : 0xffffffffu << (shift + 8);
+#pragma unroll
+    for (int i = 0; i < IPT; ++i)
+      if (((key[i] ^ key_t) & above) == 0u)
+        __hip_atomic_fetch_add(&hist[((key[i] >> shift) & 255u) * PL_SELECT_COPIES + (lane & 31)], 1u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+    __syncthreads();
+    {
+      const int bin = tid >> 2, quarter = tid & 3;
+      unsigned a = 0u;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int at = bin * PL_SELECT_COPIES + quarter * 8 + ((j + bin) & 7);
+        a += hist[at];
+        hist[at] = 0u;
+      }
+      a += __shfl_xor(a, 1, 64);
+      a += __shfl_xor(a, 2, 64);
+      if (quarter == 0) total[bin] = a;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      unsigned c[4], sum = 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sum += c[j] = total[4 * lane + j];
+      unsigned incl = sum;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const unsigned up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+      }
+      unsigned before = incl - sum;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {                                        // one bin of one lane holds the rank: an empty one cannot
+        if (before < rank && rank <= before + c[j]) {
+          pick[0] = (unsigned)(4 * lane + j);
+          pick[1] = rank - before;
+        }
+        before += c[j];
+      }
+    }
+    __syncthreads();
+    key_t |= pick[0] << shift;
+    rank = pick[1];
+  }
+
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int i = 0; i < IPT; ++i) {
+    const unsigned long long lower = __ballot(key[i] < key_t), equal = __ballot(key[i] == key_t);
+    if (lane == 0) {
+      cell[0][i * WAVES + wave] = (unsigned)__popcll(lower);
+      cell[1][i * WAVES + wave] = (unsigned)__popcll(equal);
+    }
+  }
+  __syncthreads();
+  {
+    unsigned v[2], incl[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      incl[h] = v[h] = tid < CELLS ? cell[h][tid] : 0u;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const unsigned up = __shfl_up(incl[h], d, 64);
+        if (lane >= d) incl[h] += up;
+      }
+      if (lane == 63) wave_sum[h][wave] = incl[h];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      unsigned before = incl[h] - v[h];
+      for (int w = 0; w < wave; ++w) before += wave_sum[h][w];
+      if (tid < CELLS) cell[h][tid] = before;
+    }
+  }
+  __syncthreads();
+  // The compiler would otherwise keep IPT coordinate addresses and 2 IPT ballots of the loops above alive for the loop below
+  // (common subexpressions: hundreds of registers, spilled); through these two it forms them again, a few instructions each.
+  unsigned tid2 = threadIdx.x;
+  asm volatile("" : "+v"(tid2), "+v"(key_t));
+  constexpr int BATCH = 8;                                                 // coordinate pairs loaded together, then stored
+  static_assert(IPT % BATCH == 0, "whole batches");
+#pragma unroll
+  for (int i0 = 0; i0 < IPT; i0 += BATCH) {
+    float2 c[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) c[j] = crow[min((i0 + j) * PL_SELECT_BLOCK + (int)tid2, S - 1)];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int i = i0 + j;
+      const bool is_lower = key[i] < key_t, is_equal = key[i] == key_t;
+      const unsigned long long lower = __ballot(is_lower), equal = __ballot(is_equal);
+      const unsigned lb = cell[0][i * WAVES + wave] + (unsigned)__popcll(lower & below);
+      const unsigned eb = cell[1][i * WAVES + wave] + (unsigned)__popcll(equal & below);
+      const unsigned at = lb + min(eb, rank);
+      if ((is_lower || (is_equal && eb < rank)) && at < (unsigned)num_keep) {   // (at < num_keep always holds: the store's own guard)
+        orow[at] = c[j];
+        if (irow) irow[at] = i * PL_SELECT_BLOCK + (int)tid2;
+      }
+    }
+  }
+}
+
 // what the kernels cover: 32-bit offsets inside a plane, a one-dimensional grid, and for the losses a band that fits LDS
 int point_sample_geometry_status(int H, int W, long long K, int P, int block)
 {
@@ -243,6 +419,22 @@ int launch_point_loss_backward(const float *x, const float *t, const float *coor
   const size_t lds = (size_t)(H < PL_BAND_ROWS ? H : PL_BAND_ROWS) * W * sizeof(unsigned long long);
   point_loss_backward_kernel<<<dim3((unsigned)(K * bands)), dim3(PL_BWD_BLOCK), lds, stream>>>(
       x, t, reinterpret_cast<const float2 *>(coords), alpha, beta, gamma, P, H, W, bands, grad_planes);
+  return (int)hipGetLastError();
+}
+
+int launch_point_select(const float *pred, const int *src_index, int num_pred, int H, int W, const float *cand_coords, int K, int S,
+                        int num_keep, float *out_coords, int out_row_points, int *out_index, hipStream_t stream)
+{
+  if ((long long)H * W >= 0x7fffffffLL || S > PL_SELECT_MAX_CAND) return PCT_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)K), block(PL_SELECT_BLOCK);
+  const float2 *cand = reinterpret_cast<const float2 *>(cand_coords);
+  float2 *out = reinterpret_cast<float2 *>(out_coords);
+  if (S <= 16 * PL_SELECT_BLOCK)
+    point_select_kernel<16><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
+  else if (S <= 40 * PL_SELECT_BLOCK)
+    point_select_kernel<40><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
+  else
+    point_select_kernel<64><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
   return (int)hipGetLastError();
 }
 

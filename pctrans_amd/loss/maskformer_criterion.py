@@ -143,6 +143,10 @@ class SetCriterion(nn.Module):
         # pctrans_amd/point_loss.py where their conditions hold (CUDA fp32 predictions, target masks of one size, covered
         # geometry), the code below otherwise.  A plain attribute; process default from PCT_POINT_LOSS
         self.point_loss = _point_loss.default()
+        # acts only inside the "hip" loss path.  "torch": the candidates' logits from the gather, torch.topk, gather, cat.
+        # "hip": one selection kernel instead (point_loss.select_uncertain_points), where it covers the shape.  A plain
+        # attribute; process default from PCT_POINT_SELECT
+        self.point_select = _point_loss.select_default()
         self._target_planes = None
 
     def _hip_target_planes(self, targets, like):
@@ -162,7 +166,8 @@ class SetCriterion(nn.Module):
 
     def _loss_masks_hip(self, pred, targets, indices, num_masks):
         """loss_masks on the device kernels: the same torch.rand calls in the same order, the 3 P oversampled logits from the
-        gather, torch's topk, then BCE + dice and their backward in one kernel each.  None when the conditions do not hold."""
+        gather and torch's topk (or, with point_select = "hip", the selection kernel in their place), then BCE + dice and
+        their backward in one kernel each.  None when the conditions do not hold."""
         if not (torch.is_tensor(pred) and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 4 and pred.is_contiguous()):
             return None
         got = self._hip_target_planes(targets, pred)
@@ -180,11 +185,19 @@ class SetCriterion(nn.Module):
         num_random = self.num_points - num_uncertain
         with torch.no_grad():
             coords = torch.rand(K, num_sampled, 2, device=pred.device)
-            logits = _point_loss.point_sample_planes(pred, src, coords, 1)
-            idx = torch.topk(calculate_uncertainty(logits[:, None])[:, 0, :], k=num_uncertain, dim=1)[1]
-            coords = torch.gather(coords, 1, idx[:, :, None].expand(-1, -1, 2))
-            if num_random > 0:
-                coords = torch.cat([coords, torch.rand(K, num_random, 2, device=pred.device)], dim=1)
+            if (self.point_select == "hip" and num_uncertain > 0
+                    and _point_loss.select_supported(pred, coords, num_uncertain)):
+                # the same two torch.rand calls in the same order; the selected candidates come in candidate order
+                candidates, coords = coords, torch.empty(K, self.num_points, 2, device=pred.device)
+                _point_loss.select_uncertain_points(pred, src, candidates, num_uncertain, out=coords, with_index=False)
+                if num_random > 0:
+                    coords[:, num_uncertain:] = torch.rand(K, num_random, 2, device=pred.device)
+            else:
+                logits = _point_loss.point_sample_planes(pred, src, coords, 1)
+                idx = torch.topk(calculate_uncertainty(logits[:, None])[:, 0, :], k=num_uncertain, dim=1)[1]
+                coords = torch.gather(coords, 1, idx[:, :, None].expand(-1, -1, 2))
+                if num_random > 0:
+                    coords = torch.cat([coords, torch.rand(K, num_random, 2, device=pred.device)], dim=1)
         loss_mask, loss_dice = _point_loss.point_mask_losses(pred, src, planes, tgt, coords, num_masks)
         return {"loss_mask": loss_mask, "loss_dice": loss_dice}
 

@@ -1,10 +1,13 @@
 """Python entry of the point-sampled mask losses (C ABI `pct_point_sample_f32`, `pct_point_mask_loss_forward_f32`,
-`pct_point_mask_loss_backward_f32`, include/pctrans_hip_train.h; kernels pctrans_amd/csrc/point_loss.hip).
+`pct_point_mask_loss_backward_f32`, `pct_point_select_uncertain_f32`, include/pctrans_hip_train.h; kernels
+pctrans_amd/csrc/point_loss.hip).
 
 `point_sample_planes` is the gather (detectron2's point_sample on planes picked through an index); `point_mask_losses` is the
 criterion's sigmoid_ce_loss + dice_loss on point samples of matched (prediction, target) planes with a HIP backward that
 scatters with fixed-point LDS accumulators (deterministic: two calls give the same bits).  Opt-in: `SetCriterion.point_loss`
-and `Point_HungarianMatcher.point_sample` are "torch" unless set to "hip" (process default: PCT_POINT_LOSS)."""
+and `Point_HungarianMatcher.point_sample` are "torch" unless set to "hip" (process default: PCT_POINT_LOSS).
+`select_uncertain_points` picks the most uncertain of the criterion's oversampled candidates in one launch (no logits in memory,
+no topk); it acts inside the "hip" loss path when `SetCriterion.point_select` is "hip" (process default: PCT_POINT_SELECT)."""
 import os
 
 import torch
@@ -13,6 +16,7 @@ from . import _lib, _timing
 
 BAND_ROWS = 32        # rows of one backward workgroup's band (csrc/point_loss.hip: PL_BAND_ROWS)
 MAX_WIDTH = 256       # widest prediction plane the loss kernels cover (PL_MAX_WIDTH)
+MAX_CANDIDATES = 65536  # most candidates per pair the selection covers (PL_SELECT_MAX_CAND)
 UNSUPPORTED = -4      # PCT_ERR_UNSUPPORTED
 
 
@@ -22,6 +26,14 @@ def default():
     v = os.environ.get("PCT_POINT_LOSS") or "torch"
     if v not in ("hip", "torch"):
         raise RuntimeError("PCT_POINT_LOSS must be 'hip' or 'torch', got %r" % v)
+    return v
+
+
+def select_default():
+    """Process default of `SetCriterion.point_select`: PCT_POINT_SELECT = hip | torch (default torch)."""
+    v = os.environ.get("PCT_POINT_SELECT") or "torch"
+    if v not in ("hip", "torch"):
+        raise RuntimeError("PCT_POINT_SELECT must be 'hip' or 'torch', got %r" % v)
     return v
 
 
@@ -79,6 +91,47 @@ def point_sample_planes(planes, plane_index, coords, planes_per_coord_row=1):
                                              per_row, out.data_ptr(), torch.cuda.current_stream(planes.device).cuda_stream)
     _lib.check(rc, "point_sample")
     return out
+
+
+def select_supported(pred_masks, cand_coords, num_keep):
+    """What the selection covers: planes as the gather's, fp32 contiguous candidates [K, S, 2] on the planes' device with
+    0 < S <= MAX_CANDIDATES, and 0 <= num_keep <= S."""
+    return (sample_supported(pred_masks) and torch.is_tensor(cand_coords) and cand_coords.is_cuda
+            and cand_coords.device == pred_masks.device and cand_coords.dtype == torch.float32 and cand_coords.dim() == 3
+            and cand_coords.shape[2] == 2 and cand_coords.is_contiguous() and 0 < cand_coords.shape[1] <= MAX_CANDIDATES
+            and 0 <= int(num_keep) <= cand_coords.shape[1])
+
+
+def select_uncertain_points(pred_masks, src_index, cand_coords, num_keep, out=None, with_index=True):
+    """The num_keep most uncertain (smallest |logit|) of each pair's candidates, in ascending candidate number
+    (pct_point_select_uncertain_f32: ties at the threshold go to the lowest candidate numbers, NaN logits first).
+    pred_masks [..., H, W] fp32 on the device; src_index int [K] plane numbers or None (identity); cand_coords [K, S, 2] (x, y).
+    out: None, or fp32 contiguous [K, P, 2] with P >= num_keep whose rows' first num_keep points are written in place, the rest
+    left as they are.  -> (coords, index): coords is `out`, or a new [K, num_keep, 2]; index int32 [K, num_keep] candidate
+    numbers, or None with with_index=False.  No gradient."""
+    if not pred_masks.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    num_keep = int(num_keep)
+    cand_coords = cand_coords.detach()
+    if not select_supported(pred_masks, cand_coords, num_keep):
+        raise RuntimeError("select_uncertain_points needs contiguous fp32 device planes and candidates [K, S <= %d, 2], "
+                           "0 <= num_keep <= S" % MAX_CANDIDATES)
+    dev = pred_masks.device
+    H, W = pred_masks.shape[-2:]
+    K, S = int(cand_coords.shape[0]), int(cand_coords.shape[1])
+    src = _index(src_index, K, dev)
+    if out is None:
+        out = torch.empty((K, num_keep, 2), dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.float32 and out.dim() == 3 and out.is_contiguous()
+              and out.shape[0] == K and out.shape[1] >= num_keep and out.shape[2] == 2):
+        raise RuntimeError("out must be contiguous fp32 [%d, >= %d, 2] on the planes' device" % (K, num_keep))
+    index = torch.empty((K, num_keep), dtype=torch.int32, device=dev) if with_index else None
+    with torch.cuda.device(dev), _timing.timed("point_select", out):
+        rc = _lib.lib().pct_point_select_uncertain_f32(
+            pred_masks.data_ptr(), _ptr(src), pred_masks.numel() // (H * W), H, W, cand_coords.data_ptr(), K, S, num_keep,
+            out.data_ptr(), int(out.shape[1]), _ptr(index), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "point_select_uncertain")
+    return out, index
 
 
 def point_mask_loss_forward(pred_planes, src_index, tgt_planes, tgt_index, coords):

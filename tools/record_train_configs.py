@@ -59,6 +59,8 @@ def build(c):
                 m.dmh_train = "hip"
     if c.get("hip_point_loss"):
         model.criterion.point_loss = model.criterion.matcher.point_sample = "hip"
+    if c.get("hip_point_select"):
+        model.criterion.point_select = "hip"
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -86,6 +88,9 @@ def selected_configs(argv):
         configs.update({k + " + HIP mask head": dict(v, hip_mask_head=True) for k, v in list(configs.items())})
     if "--hip-point-loss" in argv:          # and again with the point-sampled losses and the matcher's gather on the device
         configs.update({k + " + HIP point loss": dict(v, hip_point_loss=True) for k, v in list(configs.items())})
+    if "--hip-point-select" in argv:        # and the point-loss configs again with the uncertain points chosen by the kernel
+        configs.update({k + " + HIP point select": dict(v, hip_point_select=True) for k, v in list(configs.items())
+                        if v.get("hip_point_loss")})
     return configs
 
 
@@ -137,7 +142,7 @@ def main():
     the same fragility).  `--rounds R` repeats the whole list R times, so that flag-off and flag-on steps alternate on one
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
-    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss")]
+    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select")]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
