@@ -110,6 +110,36 @@ PCT_API int pct_point_select_uncertain_f32(const float *pred, const int32_t *src
                                            int width, const float *cand_coords, int num_pairs, int num_cand, int num_keep,
                                            float *out_coords, int out_row_points, int32_t *out_index, void *stream);
 
+/* Matcher cost matrices (Point_HungarianMatcher._batched_costs without its two gathers and its chain of elementwise, einsum
+ * and reduce launches).  pred [batch * num_query, height, width] and tgt [num_tgt_planes, tgt_height, tgt_width] are fp32 planes,
+ * the targets of the images concatenated: image b owns the planes tgt_start[b] .. tgt_start[b] + tgt_count[b] (int32 arrays
+ * [batch] on the device).  coords [batch, num_points, 2]: one row of points per image, serving all its planes.  With
+ * x = sample of pred[b, q] and t = sample of target g of image b at the image's P = num_points points -- computed by the gather's
+ * code: the bits pct_point_sample_f32 returns, never written to memory --
+ *   ce[q, g]   = ( sum_p softplus(-x) t  +  sum_p softplus(x) (1 - t) ) / P
+ *   dice[q, g] = 1 - (2 sum_p sigma(x) t + 1) / (sum_p sigma(x) + sum_p t + 1)
+ *   cost[b, q, g] = cost_mask ce + cost_dice dice                      cost [batch, num_query, max_targets] fp32
+ * softplus(-x) = max(-x, 0) + log1p(e), softplus(x) = max(x, 0) + log1p(e), sigma(x) from the same e = exp(-|x|): torch's
+ * binary_cross_entropy_with_logits against ones and zeros.  The cross-entropy is the sum of two products of non-negative
+ * factors, as the reference forms it: nothing cancels where a confident prediction meets its target.  The products over the
+ * points run on v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 accumulation).
+ * cost is fully overwritten; columns g >= tgt_count[b] are written as exactly 0 (a negative count is 0, a count above
+ * max_targets is max_targets).  A target plane outside 0 .. num_tgt_planes gives NaN in its column and reads nothing.
+ * Two launches on `stream`: workgroups (chunk of the points, 128 queries x 64 targets, image) write partial sums to the
+ * workspace, a second kernel adds the chunks in ascending order and forms the cost.  No floating-point atomic, no host
+ * synchronisation, nothing allocated; every sum runs in a fixed order: results are bit-identical from call to call.  The call
+ * may be recorded into a HIP graph.
+ * `workspace`: caller-owned, 16-byte aligned, at least
+ *   4 * batch * chunks * (2 Qp Gp + Qp + Gp) bytes,   Qp = 128 ceil(num_query / 128),  Gp = 64 ceil(max_targets / 64),
+ *   chunks = max(1, min(32, ceil(num_points / 128), ceil(512 / (batch * (Qp / 128) * (Gp / 64)))))
+ * Status: the common rules; batch, num_query, max_targets or num_points == 0: PCT_OK, nothing is launched and nothing is written
+ * (for num_points == 0 the reference's 0 / 0 is left to the caller).  Covered: both planes below 2^31 - 1 pixels, batch <= 65535,
+ * num_points <= 2^30, (Qp / 128) * (Gp / 64) <= 65535 -- the assignment's limits (1024 queries, 512 targets) included. */
+PCT_API int pct_point_match_cost_f32(const float *pred, int batch, int num_query, int height, int width, const float *tgt,
+                                     int num_tgt_planes, int tgt_height, int tgt_width, const int32_t *tgt_start,
+                                     const int32_t *tgt_count, int max_targets, const float *coords, int num_points,
+                                     float cost_mask, float cost_dice, void *workspace, float *cost, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

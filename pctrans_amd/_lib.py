@@ -65,6 +65,8 @@ OPT_IN_SYMBOLS = {
     "pct_point_mask_loss_backward_f32": ([_vp] * 6 + [_i] * 4 + [_vp, _vp], _i, "tests/test_point_loss_gpu.py"),
     "pct_point_select_uncertain_f32": ([_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp], _i,
                                        "tests/test_point_select_gpu.py"),
+    "pct_point_match_cost_f32": ([_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, ctypes.c_float,
+                                  _vp, _vp, _vp], _i, "tests/test_match_cost_gpu.py"),
 }
 
 # Entry points of the opt-in instance post-processing (include/pctrans_hip_post.h; pctrans_amd/postprocess.py, reached with

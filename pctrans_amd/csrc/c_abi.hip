@@ -440,6 +440,24 @@ int pct_point_select_uncertain_f32(const float *pred, const int32_t *src_index, 
                                   out_coords, out_row_points, out_index, static_cast<hipStream_t>(stream));
 }
 
+int pct_point_match_cost_f32(const float *pred, int batch, int num_query, int height, int width, const float *tgt,
+                             int num_tgt_planes, int tgt_height, int tgt_width, const int32_t *tgt_start, const int32_t *tgt_count,
+                             int max_targets, const float *coords, int num_points, float cost_mask, float cost_dice,
+                             void *workspace, float *cost, void *stream)
+{
+  if (batch < 0 || num_query < 0 || height <= 0 || width <= 0 || num_tgt_planes < 0 || tgt_height <= 0 || tgt_width <= 0 ||
+      max_targets < 0 || num_points < 0)
+    return PCT_ERR_BAD_ARG;
+  if (batch == 0 || num_query == 0 || max_targets == 0 || num_points == 0) return PCT_OK;
+  if (!pred || (!tgt && num_tgt_planes > 0) || !tgt_start || !tgt_count || !coords || !workspace || !cost) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)pred | (uintptr_t)tgt | (uintptr_t)tgt_start | (uintptr_t)tgt_count | (uintptr_t)cost) & 3u) ||
+      ((uintptr_t)coords & 7u) || ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_match_cost(pred, batch, num_query, height, width, tgt, num_tgt_planes, tgt_height, tgt_width, tgt_start,
+                                      tgt_count, max_targets, coords, num_points, cost_mask, cost_dice, workspace, cost,
+                                      static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

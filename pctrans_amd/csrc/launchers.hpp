@@ -138,6 +138,9 @@ int launch_point_loss_backward(const float *x, const float *t, const float *coor
                                const float *gamma, int K, int P, int H, int W, float *grad_planes, hipStream_t stream);
 int launch_point_select(const float *pred, const int *src_index, int num_pred, int H, int W, const float *cand_coords, int K, int S,
                         int num_keep, float *out_coords, int out_row_points, int *out_index, hipStream_t stream);
+int launch_point_match_cost(const float *pred, int B, int Q, int H, int W, const float *tgt, int num_tgt, int Ht, int Wt,
+                            const int *tgt_start, const int *tgt_count, int Gmax, const float *coords, int P, float cost_mask,
+                            float cost_dice, void *workspace, float *cost, hipStream_t stream);
 
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED

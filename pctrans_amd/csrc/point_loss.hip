@@ -1,8 +1,9 @@
 // Point-sampled mask losses (include/pctrans_hip_train.h: pct_point_sample_f32, pct_point_mask_loss_forward_f32,
-// pct_point_mask_loss_backward_f32, pct_point_select_uncertain_f32): the gather, the fused BCE + dice sums and the scatter of
-// their gradient that loss/matcher.py and loss/maskformer_criterion.py otherwise run as grid_sample forward / backward plus
-// elementwise and reduce launches, and the choice of the most uncertain of the oversampled candidates that the criterion
-// otherwise makes with a gather, topk, gather and cat.
+// pct_point_mask_loss_backward_f32, pct_point_select_uncertain_f32, pct_point_match_cost_f32): the gather, the fused BCE + dice
+// sums and the scatter of their gradient that loss/matcher.py and loss/maskformer_criterion.py otherwise run as grid_sample
+// forward / backward plus elementwise and reduce launches, the choice of the most uncertain of the oversampled candidates that
+// the criterion otherwise makes with a gather, topk, gather and cat, and the matcher's cost matrices that it otherwise forms
+// from two gathers with a chain of elementwise launches and three einsum.
 //
 // Sampling is F.grid_sample(input, 2c - 1, "bilinear", "zeros", align_corners=False): x = c_x * W - 0.5 (one fma),
 // y = c_y * H - 0.5, taps at floor and floor + 1, weights (1 - tx)(1 - ty) .. tx ty, a tap outside the plane adds nothing.
@@ -372,6 +373,180 @@ __global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_kernel(const flo
   }
 }
 
+// Matcher cost matrices (pct_point_match_cost_f32): cost[b, q, g] of Point_HungarianMatcher._batched_costs from the planes, the
+// point samples never in memory.  Three P-long contractions per (q, g) on v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 sums):
+//     ce  = sum_p softplus(-x) t + sum_p softplus(x) (1 - t)      (two non-negative products into ONE accumulator: nothing cancels)
+//     st  = sum_p sigma(x) t
+// plus the vectors sum_p sigma(x) per query and sum_p t per target.
+//
+// Workgroup (chunk of P, group of 128 queries x group of 64 targets, image), 4 waves, wave w the query tile 32 w .. 32 w + 31.
+// The chunk is walked in passes of MC_SUB = 128 points:
+//   1. every thread forms the taps of one point of the pass from the image's coordinate row, once for the prediction's geometry
+//      (kept in LDS for pass 2) and once for the targets' (kept in registers), and samples its share of the group's target planes
+//      into LDS as ts[point][target] (row stride 65 words: the writes, lanes along the points, and the reads, lanes along the
+//      targets, both touch 32 different banks);
+//   2. a wave's lane (i, kh) = (lane % 32, lane / 32) IS the A operand's element (row i, k = kh) of the matrix instruction: for step s
+//      it samples query i at point 2 s + kh with the staged taps (make_taps / sample_plane: the gather's code and the gather's bits),
+//      forms softplus(-x), softplus(x), sigma(x) from one e = exp(-|x|) and feeds them straight from registers; the B operand
+//      (k = kh, column i) is ts[2 s + kh][i], and 1 - that.  No operand shuffle, no A tile in LDS.
+// The accumulators (2 products x 2 target tiles x 16 registers) stay in registers over all passes of the chunk and go to the
+// workspace once; sum sigma is a per-lane running sum (ascending points), sum t likewise from the B operands the lane reads anyway.
+// Points past P: A operands and t are 0 (0 * (1 - 0) = 0).  Queries past Q: x = 0, nothing is read, the rows are not used.
+// Targets past the image's count: t = 0, nothing is read; target tiles wholly past the count are skipped.
+// match_cost_finish_kernel adds the chunks in ascending order and forms the cost; columns past the count are written as 0.
+constexpr int MC_BLOCK = 256;
+constexpr int MC_SUB = 128;                // points per pass
+constexpr int MC_QGROUP = 128;             // queries per workgroup: 4 waves x 32
+constexpr int MC_GTILES = 2;               // target tiles of 32 per workgroup
+constexpr int MC_GGROUP = 32 * MC_GTILES;
+constexpr int MC_TS = MC_GGROUP + 1;       // row stride of ts in words
+constexpr int MC_MAX_CHUNKS = 32;          // of P: bounds the workspace
+constexpr int MC_WANT_GROUPS = 512;        // workgroups the P split aims for (two per compute unit)
+
+typedef float mc_f16 __attribute__((ext_vector_type(16)));
+
+struct MatchCostPlan {
+  int qgroups, ggroups, passes, chunks;    // passes of MC_SUB points per chunk
+  long long per_chunk;                     // floats of one (image, chunk): 2 Qp Gp + Qp + Gp
+};
+
+__host__ __device__ inline MatchCostPlan match_cost_plan(const int B, const int Q, const int Gmax, const int P)
+{
+  MatchCostPlan m;
+  m.qgroups = (Q + MC_QGROUP - 1) / MC_QGROUP;
+  m.ggroups = (Gmax + MC_GGROUP - 1) / MC_GGROUP;
+  const long long groups = (long long)B * m.qgroups * m.ggroups;
+  const int subs = (P + MC_SUB - 1) / MC_SUB;
+  long long want = (MC_WANT_GROUPS + groups - 1) / groups;
+  if (want > MC_MAX_CHUNKS) want = MC_MAX_CHUNKS;
+  if (want > subs) want = subs;
+  if (want < 1) want = 1;
+  m.passes = (int)((subs + want - 1) / want);
+  m.chunks = (subs + m.passes - 1) / m.passes;                             // <= want
+  const long long Qp = (long long)m.qgroups * MC_QGROUP, Gp = (long long)m.ggroups * MC_GGROUP;
+  m.per_chunk = 2 * Qp * Gp + Qp + Gp;
+  return m;
+}
+
+__global__ __launch_bounds__(MC_BLOCK, 2) void match_cost_partial_kernel(
+    const float *__restrict__ pred, const float *__restrict__ tgt, const int *__restrict__ tgt_start,
+    const int *__restrict__ tgt_count, const float2 *__restrict__ coords, const int Q, const int H, const int W, const int num_tgt,
+    const int Ht, const int Wt, const int Gmax, const int P, const MatchCostPlan plan, float *__restrict__ ws)
+{
+  __shared__ Taps taps[MC_SUB];
+  __shared__ float ts[MC_SUB * MC_TS];
+  const int chunk = blockIdx.x, qgrp = blockIdx.y / plan.ggroups, ggrp = blockIdx.y - qgrp * plan.ggroups, b = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, kh = lane >> 5;
+  const int start = tgt_start[b];
+  const int count = max(0, min(tgt_count[b], Gmax)) - ggrp * MC_GGROUP;    // targets of this group that the image has
+  const int ntiles = max(0, min(MC_GTILES, (count + 31) / 32));
+  const int q = qgrp * MC_QGROUP + wave * 32 + col;
+  const bool q_ok = q < Q;
+  const float *pp = pred + ((size_t)b * Q + (q_ok ? q : 0)) * H * W;
+  const float2 *crow = coords + (size_t)b * P;
+
+  mc_f16 acc_ce[MC_GTILES], acc_st[MC_GTILES];
+  float tsum[MC_GTILES], ssig = 0.f;
+#pragma unroll
+  for (int gt = 0; gt < MC_GTILES; ++gt) {
+    tsum[gt] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc_ce[gt][r] = acc_st[gt][r] = 0.f;
+  }
+
+  for (int pass = 0; pass < plan.passes; ++pass) {
+    const int p0 = (chunk * plan.passes + pass) * MC_SUB;
+    if (p0 >= P) break;                                                     // (uniform)
+    __syncthreads();                                                        // the previous pass has read taps and ts
+    {
+      const int pt = tid & (MC_SUB - 1), half = tid >> 7;
+      const bool in = p0 + pt < P;
+      const float2 c = in ? crow[p0 + pt] : make_float2(0.f, 0.f);
+      if (half == 0) taps[pt] = make_taps(c.x, c.y, H, W);
+      const Taps tt = make_taps(c.x, c.y, Ht, Wt);
+      for (int j = half; j < ntiles * 32; j += MC_BLOCK / MC_SUB) {
+        float v = 0.f;
+        if (in && j < count) {
+          const int plane = start + ggrp * MC_GGROUP + j;                   // outside the planes: loud, and no access
+          v = (unsigned)plane < (unsigned)num_tgt ? sample_plane(tgt + (size_t)plane * Ht * Wt, tt, Ht, Wt) : __builtin_nanf("");
+        }
+        ts[pt * MC_TS + j] = v;
+      }
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int s = 0; s < MC_SUB / 2; ++s) {
+      const int pt = 2 * s + kh;
+      const Taps tp = taps[pt];
+      const float x = q_ok ? sample_plane(pp, tp, H, W) : 0.f;
+      const float e = expf(-fabsf(x));
+      const float l = log1pf(e), r = 1.f / (1.f + e);
+      const bool in = p0 + pt < P;
+      const float pos = in ? fmaxf(-x, 0.f) + l : 0.f;                      // softplus(-x) = bce_with_logits(x, 1)
+      const float neg = in ? fmaxf(x, 0.f) + l : 0.f;                       // softplus(x)  = bce_with_logits(x, 0)
+      const float sg = in ? (x >= 0.f ? r : e * r) : 0.f;
+      ssig += sg;
+#pragma unroll
+      for (int gt = 0; gt < MC_GTILES; ++gt) {
+        if (gt < ntiles) {
+          const float t = ts[pt * MC_TS + gt * 32 + col];
+          tsum[gt] += t;
+          acc_ce[gt] = __builtin_amdgcn_mfma_f32_32x32x2f32(pos, t, acc_ce[gt], 0, 0, 0);
+          acc_ce[gt] = __builtin_amdgcn_mfma_f32_32x32x2f32(neg, 1.f - t, acc_ce[gt], 0, 0, 0);
+          acc_st[gt] = __builtin_amdgcn_mfma_f32_32x32x2f32(sg, t, acc_st[gt], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  // acc[r] = D[row 8 (r / 4) + 4 kh + r % 4][column col]: row = query of the wave's tile, column = target of the tile
+  const long long Qp = (long long)plan.qgroups * MC_QGROUP, Gp = (long long)plan.ggroups * MC_GGROUP;
+  float *wsb = ws + ((size_t)b * plan.chunks + chunk) * plan.per_chunk;
+#pragma unroll
+  for (int gt = 0; gt < MC_GTILES; ++gt) {
+    if (gt < ntiles) {
+      const long long g = (long long)ggrp * MC_GGROUP + gt * 32 + col;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const long long row = (long long)qgrp * MC_QGROUP + wave * 32 + 8 * (r / 4) + 4 * kh + r % 4;
+        wsb[row * Gp + g] = acc_ce[gt][r];
+        wsb[Qp * Gp + row * Gp + g] = acc_st[gt][r];
+      }
+      const float t2 = tsum[gt] + __shfl_xor(tsum[gt], 32, 64);             // even points + odd points
+      if (qgrp == 0 && wave == 0 && kh == 0) wsb[2 * Qp * Gp + Qp + g] = t2;
+    }
+  }
+  const float s2 = ssig + __shfl_xor(ssig, 32, 64);
+  if (ggrp == 0 && kh == 0) wsb[2 * Qp * Gp + (long long)qgrp * MC_QGROUP + wave * 32 + col] = s2;
+}
+
+__global__ __launch_bounds__(256) void match_cost_finish_kernel(const float *__restrict__ ws, const int *__restrict__ tgt_count,
+                                                                const int Q, const int Gmax, const int P, const long long total,
+                                                                const MatchCostPlan plan, const float cost_mask,
+                                                                const float cost_dice, float *__restrict__ cost)
+{
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int g = (int)(i % Gmax);
+  const long long bq = i / Gmax;
+  const int q = (int)(bq % Q), b = (int)(bq / Q);
+  float c = 0.f;
+  if (g < tgt_count[b]) {
+    const long long Qp = (long long)plan.qgroups * MC_QGROUP, Gp = (long long)plan.ggroups * MC_GGROUP;
+    const float *w = ws + (size_t)b * plan.chunks * plan.per_chunk;
+    float ce = 0.f, st = 0.f, sg = 0.f, t = 0.f;
+    for (int k = 0; k < plan.chunks; ++k, w += plan.per_chunk) {
+      ce += w[q * Gp + g];
+      st += w[Qp * Gp + q * Gp + g];
+      sg += w[2 * Qp * Gp + q];
+      t += w[2 * Qp * Gp + Qp + g];
+    }
+    const float dice = 1.f - (2.f * st + 1.f) / (sg + t + 1.f);
+    c = cost_mask * (ce / (float)P) + cost_dice * dice;
+  }
+  cost[i] = c;
+}
+
 // what the kernels cover: 32-bit offsets inside a plane, a one-dimensional grid, and for the losses a band that fits LDS
 int point_sample_geometry_status(int H, int W, long long K, int P, int block)
 {
@@ -389,7 +564,35 @@ int point_loss_geometry_status(int H, int W, int Ht, int Wt, int K)
   return PCT_OK;
 }
 
+// the P split above bounds the grid's x; y and z hold the query / target groups and the images
+int match_cost_geometry_status(int B, int Q, int H, int W, int Ht, int Wt, int Gmax, int P)
+{
+  if ((long long)H * W >= 0x7fffffffLL || (long long)Ht * Wt >= 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
+  if (B > 65535 || P > 0x40000000) return PCT_ERR_UNSUPPORTED;
+  const long long qg = (Q + MC_QGROUP - 1) / MC_QGROUP, gg = (Gmax + MC_GGROUP - 1) / MC_GGROUP;
+  if (qg * gg > 65535) return PCT_ERR_UNSUPPORTED;
+  if ((long long)B * Q * Gmax >= 0x7fffffffLL * 256) return PCT_ERR_UNSUPPORTED;
+  return PCT_OK;
+}
+
 }  // namespace
+
+int launch_point_match_cost(const float *pred, int B, int Q, int H, int W, const float *tgt, int num_tgt, int Ht, int Wt,
+                            const int *tgt_start, const int *tgt_count, int Gmax, const float *coords, int P, float cost_mask,
+                            float cost_dice, void *workspace, float *cost, hipStream_t stream)
+{
+  if (const int rc = match_cost_geometry_status(B, Q, H, W, Ht, Wt, Gmax, P); rc != PCT_OK) return rc;
+  const MatchCostPlan plan = match_cost_plan(B, Q, Gmax, P);
+  float *ws = static_cast<float *>(workspace);
+  match_cost_partial_kernel<<<dim3((unsigned)plan.chunks, (unsigned)(plan.qgroups * plan.ggroups), (unsigned)B), dim3(MC_BLOCK), 0,
+                              stream>>>(pred, tgt, tgt_start, tgt_count, reinterpret_cast<const float2 *>(coords), Q, H, W, num_tgt,
+                                        Ht, Wt, Gmax, P, plan, ws);
+  if (const int rc = (int)hipGetLastError(); rc != 0) return rc;
+  const long long total = (long long)B * Q * Gmax;
+  match_cost_finish_kernel<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream>>>(ws, tgt_count, Q, Gmax, P, total, plan,
+                                                                                           cost_mask, cost_dice, cost);
+  return (int)hipGetLastError();
+}
 
 int launch_point_sample(const float *planes, const int *plane_index, const float *coords, int num_planes, int H, int W, int K,
                         int P, int per_row, float *out, hipStream_t stream)

@@ -43,6 +43,27 @@ class Point_HungarianMatcher(nn.Module):
         # "torch": point_sample as the reference calls it.  "hip": the batched costs gather their points with the device
         # kernel where it applies (CUDA fp32 contiguous masks).  A plain attribute; process default from PCT_POINT_LOSS
         self.point_sample = _point_loss.default()
+        # "hip": the batched costs come from ONE kernel that samples both mask sets and contracts them (point_loss.match_costs),
+        # where it applies (CUDA fp32 contiguous pred_masks, target masks of one size on the same device); no point samples, no
+        # einsum.  A plain attribute; process default from PCT_MATCH_COST
+        self.match_cost = _point_loss.match_cost_default()
+        self._target_planes = None         # (key, fp32 planes [sum G, Ht, Wt], device starts, device counts, the masks)
+
+    def _match_target_planes(self, targets, like):
+        """The images' target masks as one fp32 [sum G, Ht, Wt] tensor with each image's first plane and count as int32 device
+        vectors, or None when the masks differ in size or device.  Kept for the calls that follow with the same masks (the ten
+        predictions of a step): keyed as SetCriterion._hip_target_planes."""
+        masks = [t["masks"] for t in targets]
+        if not masks or len({tuple(m.shape[-2:]) for m in masks}) != 1 or any(m.dim() != 3 or m.device != like.device for m in masks):
+            return None
+        key = tuple((m.data_ptr(), m._version, tuple(m.shape), m.dtype) for m in masks)
+        if self._target_planes is None or self._target_planes[0] != key:
+            planes = torch.cat(masks).to(torch.float32).contiguous()
+            counts = [int(m.shape[0]) for m in masks]
+            starts = [sum(counts[:b]) for b in range(len(counts))]
+            vec = torch.tensor([starts, counts], dtype=torch.int32).to(like.device, non_blocking=True)
+            self._target_planes = (key, planes, vec[0], vec[1], masks)    # (the masks: their addresses stay theirs while kept)
+        return self._target_planes[1:4]
 
     def _batched_costs(self, outputs, targets):
         """All images of the batch in one pass -- when their target masks share one size: the predicted masks are the
@@ -57,6 +78,11 @@ class Point_HungarianMatcher(nn.Module):
             return None
         gmax = max(counts)
         coords = torch.cat([torch.rand(1, self.num_points, 2, device=pred.device) for _ in range(bs)])
+        if (self.match_cost == "hip" and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 4
+                and pred.is_contiguous()):
+            got = self._match_target_planes(targets, pred)
+            if got is not None and _point_loss.match_cost_supported(pred, got[0], self.num_points, gmax):
+                return _point_loss.match_costs(pred, got[0], got[1], got[2], coords, self.cost_mask, self.cost_dice, gmax), counts
         if min(counts) == gmax:
             tgt = torch.stack([t["masks"] for t in targets]).to(pred)
         else:

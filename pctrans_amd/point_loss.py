@@ -7,7 +7,10 @@ criterion's sigmoid_ce_loss + dice_loss on point samples of matched (prediction,
 scatters with fixed-point LDS accumulators (deterministic: two calls give the same bits).  Opt-in: `SetCriterion.point_loss`
 and `Point_HungarianMatcher.point_sample` are "torch" unless set to "hip" (process default: PCT_POINT_LOSS).
 `select_uncertain_points` picks the most uncertain of the criterion's oversampled candidates in one launch (no logits in memory,
-no topk); it acts inside the "hip" loss path when `SetCriterion.point_select` is "hip" (process default: PCT_POINT_SELECT)."""
+no topk); it acts inside the "hip" loss path when `SetCriterion.point_select` is "hip" (process default: PCT_POINT_SELECT).
+`match_costs` is the matcher's whole cost pass (`pct_point_match_cost_f32`: both gathers, BCE, dice and the three contractions
+in one kernel plus a small finishing one); `Point_HungarianMatcher.match_cost` is "torch" unless set to "hip" (process default:
+PCT_MATCH_COST)."""
 import os
 
 import torch
@@ -18,6 +21,12 @@ BAND_ROWS = 32        # rows of one backward workgroup's band (csrc/point_loss.h
 MAX_WIDTH = 256       # widest prediction plane the loss kernels cover (PL_MAX_WIDTH)
 MAX_CANDIDATES = 65536  # most candidates per pair the selection covers (PL_SELECT_MAX_CAND)
 UNSUPPORTED = -4      # PCT_ERR_UNSUPPORTED
+MATCH_QUERY_GROUP = 128   # queries / targets of one workgroup of the cost kernel, points of one pass, most chunks of the points
+MATCH_TARGET_GROUP = 64   # and the workgroups the split aims for (csrc/point_loss.hip: MC_QGROUP, MC_GGROUP, MC_SUB,
+MATCH_POINTS_PER_PASS = 128   # MC_MAX_CHUNKS, MC_WANT_GROUPS): the workspace formula of the header
+MATCH_MAX_CHUNKS = 32
+MATCH_WANT_GROUPS = 512
+MATCH_MAX_BATCH = 65535
 
 
 def default():
@@ -34,6 +43,14 @@ def select_default():
     v = os.environ.get("PCT_POINT_SELECT") or "torch"
     if v not in ("hip", "torch"):
         raise RuntimeError("PCT_POINT_SELECT must be 'hip' or 'torch', got %r" % v)
+    return v
+
+
+def match_cost_default():
+    """Process default of `Point_HungarianMatcher.match_cost`: PCT_MATCH_COST = hip | torch (default torch)."""
+    v = os.environ.get("PCT_MATCH_COST") or "torch"
+    if v not in ("hip", "torch"):
+        raise RuntimeError("PCT_MATCH_COST must be 'hip' or 'torch', got %r" % v)
     return v
 
 
@@ -132,6 +149,56 @@ def select_uncertain_points(pred_masks, src_index, cand_coords, num_keep, out=No
             out.data_ptr(), int(out.shape[1]), _ptr(index), torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "point_select_uncertain")
     return out, index
+
+
+def match_cost_supported(pred, tgt_planes, num_points=1, max_targets=1):
+    """What `match_costs` covers: pred [B, Q, H, W] and tgt_planes [n, Ht, Wt] CUDA fp32 contiguous on one device with planes as
+    the gather's, B <= MATCH_MAX_BATCH, at least one query, point and target column."""
+    return (sample_supported(pred) and pred.dim() == 4 and _planes_ok(tgt_planes) and tgt_planes.dim() == 3
+            and 0 < tgt_planes.shape[-1] * tgt_planes.shape[-2] < 2 ** 31 - 1 and pred.device == tgt_planes.device
+            and 0 < pred.shape[0] <= MATCH_MAX_BATCH and pred.shape[1] > 0 and 0 < int(num_points) <= 2 ** 30
+            and int(max_targets) > 0
+            and -(-pred.shape[1] // MATCH_QUERY_GROUP) * -(-int(max_targets) // MATCH_TARGET_GROUP) <= 65535)
+
+
+def match_cost_workspace_bytes(batch, num_query, max_targets, num_points):
+    """The workspace formula of include/pctrans_hip_train.h."""
+    qg, gg = -(-num_query // MATCH_QUERY_GROUP), -(-max_targets // MATCH_TARGET_GROUP)
+    chunks = max(1, min(MATCH_MAX_CHUNKS, -(-num_points // MATCH_POINTS_PER_PASS), -(-MATCH_WANT_GROUPS // (batch * qg * gg))))
+    Qp, Gp = qg * MATCH_QUERY_GROUP, gg * MATCH_TARGET_GROUP
+    return 4 * batch * chunks * (2 * Qp * Gp + Qp + Gp)
+
+
+def match_costs(pred, tgt_planes, starts, counts, coords, cost_mask, cost_dice, max_targets=None):
+    """The matcher's cost matrices in one call (pct_point_match_cost_f32).  pred [B, Q, H, W] fp32 contiguous on the device;
+    tgt_planes [sum G, Ht, Wt] fp32, image b owning planes starts[b] .. starts[b] + counts[b] (int32 [B] device tensors);
+    coords [B, P, 2] (x, y), one row per image.  max_targets: the number of columns (the largest count; it is read from `counts`
+    with one host synchronisation when not given).  -> cost [B, Q, max_targets] fp32, zero past an image's count.  No gradient."""
+    if not pred.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    dev = pred.device
+    starts = starts.to(device=dev, dtype=torch.int32).contiguous()
+    counts = counts.to(device=dev, dtype=torch.int32).contiguous()
+    gmax = int(counts.max()) if max_targets is None else int(max_targets)
+    coords = coords.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if coords.dim() != 3 or coords.shape[2] != 2 or coords.shape[0] != pred.shape[0]:
+        raise RuntimeError("coords must be [B, P, 2]")
+    P = int(coords.shape[1])
+    if not match_cost_supported(pred, tgt_planes, P, gmax):
+        raise RuntimeError("match_costs needs contiguous fp32 device planes, pred [B, Q, H, W], at least one point and target")
+    B, Q, H, W = pred.shape
+    if tuple(starts.shape) != (B,) or tuple(counts.shape) != (B,):
+        raise RuntimeError("starts and counts must be vectors of %d entries" % B)
+    Ht, Wt = tgt_planes.shape[-2:]
+    cost = torch.empty((B, Q, gmax), dtype=torch.float32, device=dev)
+    ws = torch.empty(match_cost_workspace_bytes(B, Q, gmax, P) // 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timing.timed("point_match_cost", cost):
+        rc = _lib.lib().pct_point_match_cost_f32(
+            pred.data_ptr(), B, Q, H, W, tgt_planes.data_ptr(), int(tgt_planes.shape[0]), Ht, Wt, starts.data_ptr(),
+            counts.data_ptr(), gmax, coords.data_ptr(), P, float(cost_mask), float(cost_dice), ws.data_ptr(), cost.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, "point_match_cost")
+    return cost
 
 
 def point_mask_loss_forward(pred_planes, src_index, tgt_planes, tgt_index, coords):

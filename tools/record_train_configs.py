@@ -61,6 +61,8 @@ def build(c):
         model.criterion.point_loss = model.criterion.matcher.point_sample = "hip"
     if c.get("hip_point_select"):
         model.criterion.point_select = "hip"
+    if c.get("hip_match_cost"):
+        model.criterion.matcher.match_cost = "hip"
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -91,6 +93,8 @@ def selected_configs(argv):
     if "--hip-point-select" in argv:        # and the point-loss configs again with the uncertain points chosen by the kernel
         configs.update({k + " + HIP point select": dict(v, hip_point_select=True) for k, v in list(configs.items())
                         if v.get("hip_point_loss")})
+    if "--hip-match-cost" in argv:          # and every selected config again with the matcher's cost matrices from the fused kernel
+        configs.update({k + " + HIP match cost": dict(v, hip_match_cost=True) for k, v in list(configs.items())})
     return configs
 
 
@@ -142,7 +146,8 @@ def main():
     the same fragility).  `--rounds R` repeats the whole list R times, so that flag-off and flag-on steps alternate on one
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
-    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select")]
+    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select",
+                                                "--hip-match-cost")]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
