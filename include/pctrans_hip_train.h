@@ -140,6 +140,59 @@ PCT_API int pct_point_match_cost_f32(const float *pred, int batch, int num_query
                                      const int32_t *tgt_count, int max_targets, const float *coords, int num_points,
                                      float cost_mask, float cost_dice, void *workspace, float *cost, void *stream);
 
+/* ---- pixel-embedding loss (SetCriterion.loss_embedding: the label map and the reference's discriminative_loss,
+ * loss/loss.py:297-355) -----------------------------------------------------------------------------------------------------
+ * Label map.  planes [num_planes, plane_height, plane_width] fp32 are the images' target masks concatenated, image b owning the
+ * planes plane_start[b] .. plane_start[b] + plane_count[b] (int32 [batch] on the device).  labels [batch, height, width] int32,
+ * fully overwritten:
+ *   labels[b, y, x] = 1 + the lowest g with plane g of image b > 0 at (sy, sx), else 0
+ *   sy = min((int)floorf(y * (float)plane_height / height), plane_height - 1), sx likewise: torch's "nearest" source index
+ * which is argmax over the zero-prepended stack of F.interpolate(masks, (height, width), "nearest") > 0 (ties go to the first
+ * index; a NaN is not positive).  Only the sampled elements are read; a plane outside 0 .. num_planes is skipped and not read.
+ * One launch.  Covered: both sizes below 2^31 - 1 pixels, batch <= 65535. */
+PCT_API int pct_instance_label_map_f32(const float *planes, int num_planes, int plane_height, int plane_width,
+                                       const int32_t *plane_start, const int32_t *plane_count, int batch, int height, int width,
+                                       int32_t *labels, void *stream);
+
+/* Loss forward.  embedding [batch, channels, height, width] fp32 contiguous, labels [batch, height, width] int32 in
+ * 0 .. num_labels (0 is background).  With P_g the pixels of label g of one image, n_g their number, mu_g their mean,
+ * r_p = |e_p - mu_g| and the image's present labels (n_g > 0, g >= 1), num_id of them:
+ *   var  = (1 / num_id) sum_g (1 / n_g) sum_p (r_p - delta_v)^2                                  (no hinge: the reference has none)
+ *   dist = sum_{i != j} relu(delta_d - |mu_i - mu_j|)^2 / (num_id (num_id - 1)) / 2              (only when num_id > 1)
+ *   reg  = (1 / num_id) sum_g |mu_g|
+ *   loss = (alpha sum_b var + beta sum_b dist + gama sum_b reg) / batch,   an image without instances adding 0
+ * `loss`: one float on the device.  `status`: one int32 on the device, the number of labels outside 0 .. num_labels; such pixels
+ * contribute nothing (they count as background) and nothing synchronises.
+ * `table` [batch, num_labels + 1, 68] fp32, fully overwritten, is what the backward needs, per label: [0] n_g, [1] the coefficient
+ * c_g = alpha / (batch num_id n_g), [2] sum_p (r_p - delta_v)^2, [3] 0, [4 .. 36) mu_g, [36 .. 68) the vector
+ *   T_g = -c_g S_g / n_g + (beta d dist / d mu_g + gama d reg / d mu_g) / (batch n_g),   S_g = sum_p 2 (r_p - delta_v)(e_p - mu_g) / r_p
+ * (everything that reaches a pixel through its centroid; terms with r_p = 0, coinciding centroids and a zero centroid have
+ * gradient 0, as torch's norm backward makes them).  Channels past `channels`, absent labels and row 0 are zero.
+ * Six launches: per-label sums over (chunk of pixels, tile of 32 labels, image) on v_mfma_f32_32x32x2_f32 with the one-hot
+ * operand formed in registers from the labels -- a 0 / 1 operand makes every product exact: a label's sum is the fp32 sum of its
+ * pixels in ascending order inside a chunk -- the chunks added in ascending order; the same again for S_g with mu_g known; 32
+ * labels per workgroup against all for the pairwise term; workgroups and images added in ascending order.  No floating-point
+ * atomic, nothing allocated, no host synchronisation: results are bit-identical from call to call and the call may be recorded
+ * into a HIP graph.
+ * `workspace`: caller-owned, 16-byte aligned, at least
+ *   4 * batch * (chunks * (34 * 32 * (num_labels / 32 + 1) + 1) + 4 * ceil(num_labels / 32)) bytes,
+ *   subs = ceil(height * width / 256), passes = ceil(subs / 64), chunks = ceil(subs / passes)
+ * Status: a non-positive size or count or a missing pointer PCT_ERR_BAD_ARG; misaligned pointer PCT_ERR_ALIGNMENT.
+ * Covered: channels <= 32, num_labels <= 1024, height * width < 2^31 - 1, batch <= 65535; anything else PCT_ERR_UNSUPPORTED and
+ * callers keep their torch formulation. */
+PCT_API int pct_discriminative_loss_forward_f32(const float *embedding, const int32_t *labels, int batch, int channels, int height,
+                                                int width, int num_labels, float delta_v, float delta_d, float alpha, float beta,
+                                                float gama, void *workspace, float *table, float *loss, int32_t *status,
+                                                void *stream);
+
+/* Loss backward, per pixel, no scatter: with g the pixel's label and grad_out one float on the device,
+ *   grad_embedding[b, :, p] = grad_out (c_g 2 (1 - delta_v / r_p)(e_p - mu_g) + T_g)
+ * and 0 for background and labels outside 0 .. num_labels; the first term is 0 where r_p = 0.  r_p is recomputed by the forward's
+ * code.  grad_embedding [batch, channels, height, width] is fully overwritten.  One launch.  Covered: as the forward. */
+PCT_API int pct_discriminative_loss_backward_f32(const float *embedding, const int32_t *labels, const float *table,
+                                                 const float *grad_out, int batch, int channels, int height, int width,
+                                                 int num_labels, float delta_v, float *grad_embedding, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

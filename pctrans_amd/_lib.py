@@ -67,6 +67,11 @@ OPT_IN_SYMBOLS = {
                                        "tests/test_point_select_gpu.py"),
     "pct_point_match_cost_f32": ([_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, ctypes.c_float,
                                   _vp, _vp, _vp], _i, "tests/test_match_cost_gpu.py"),
+    "pct_instance_label_map_f32": ([_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp], _i, "tests/test_embedding_loss_gpu.py"),
+    "pct_discriminative_loss_forward_f32": ([_vp, _vp] + [_i] * 5 + [ctypes.c_float] * 5 + [_vp] * 5, _i,
+                                            "tests/test_embedding_loss_gpu.py"),
+    "pct_discriminative_loss_backward_f32": ([_vp] * 4 + [_i] * 5 + [ctypes.c_float, _vp, _vp], _i,
+                                             "tests/test_embedding_loss_gpu.py"),
 }
 
 # Entry points of the opt-in instance post-processing (include/pctrans_hip_post.h; pctrans_amd/postprocess.py, reached with

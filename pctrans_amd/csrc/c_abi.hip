@@ -458,6 +458,42 @@ int pct_point_match_cost_f32(const float *pred, int batch, int num_query, int he
                                       static_cast<hipStream_t>(stream));
 }
 
+int pct_instance_label_map_f32(const float *planes, int num_planes, int plane_height, int plane_width, const int32_t *plane_start,
+                               const int32_t *plane_count, int batch, int height, int width, int32_t *labels, void *stream)
+{
+  if (num_planes < 0 || plane_height <= 0 || plane_width <= 0 || batch < 0 || height <= 0 || width <= 0) return PCT_ERR_BAD_ARG;
+  if (batch == 0) return PCT_OK;
+  if ((!planes && num_planes > 0) || !plane_start || !plane_count || !labels) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)planes | (uintptr_t)plane_start | (uintptr_t)plane_count | (uintptr_t)labels) & 3u) return PCT_ERR_ALIGNMENT;
+  return pct::launch_instance_label_map(planes, num_planes, plane_height, plane_width, plane_start, plane_count, batch, height,
+                                        width, labels, static_cast<hipStream_t>(stream));
+}
+
+int pct_discriminative_loss_forward_f32(const float *embedding, const int32_t *labels, int batch, int channels, int height,
+                                        int width, int num_labels, float delta_v, float delta_d, float alpha, float beta,
+                                        float gama, void *workspace, float *table, float *loss, int32_t *status, void *stream)
+{
+  if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || num_labels <= 0) return PCT_ERR_BAD_ARG;
+  if (!embedding || !labels || !workspace || !table || !loss || !status) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)embedding | (uintptr_t)labels | (uintptr_t)table | (uintptr_t)loss | (uintptr_t)status) & 3u) ||
+      ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_emb_loss_forward(embedding, labels, batch, channels, height, width, num_labels, delta_v, delta_d, alpha, beta,
+                                      gama, workspace, table, loss, status, static_cast<hipStream_t>(stream));
+}
+
+int pct_discriminative_loss_backward_f32(const float *embedding, const int32_t *labels, const float *table, const float *grad_out,
+                                         int batch, int channels, int height, int width, int num_labels, float delta_v,
+                                         float *grad_embedding, void *stream)
+{
+  if (batch <= 0 || channels <= 0 || height <= 0 || width <= 0 || num_labels <= 0) return PCT_ERR_BAD_ARG;
+  if (!embedding || !labels || !table || !grad_out || !grad_embedding) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)embedding | (uintptr_t)labels | (uintptr_t)table | (uintptr_t)grad_out | (uintptr_t)grad_embedding) & 3u)
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_emb_loss_backward(embedding, labels, table, grad_out, batch, channels, height, width, num_labels, delta_v,
+                                       grad_embedding, static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

@@ -142,6 +142,16 @@ int launch_point_match_cost(const float *pred, int B, int Q, int H, int W, const
                             const int *tgt_start, const int *tgt_count, int Gmax, const float *coords, int P, float cost_mask,
                             float cost_dice, void *workspace, float *cost, hipStream_t stream);
 
+// ---- pixel-embedding loss (embedding_loss.hip; include/pctrans_hip_train.h).  PCT_ERR_UNSUPPORTED before any launch for a
+// geometry the kernels do not cover ---------------------------------------------------------------------------------------
+int launch_instance_label_map(const float *planes, int num_planes, int Ht, int Wt, const int *start, const int *count, int B, int h,
+                              int w, int *labels, hipStream_t stream);
+int launch_emb_loss_forward(const float *emb, const int *labels, int B, int E, int h, int w, int L, float delta_v, float delta_d,
+                            float alpha, float beta, float gama, void *workspace, float *table, float *loss, int *status,
+                            hipStream_t stream);
+int launch_emb_loss_backward(const float *emb, const int *labels, const float *table, const float *grad_out, int B, int E, int h,
+                             int w, int L, float delta_v, float *grad_emb, hipStream_t stream);
+
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
 int launch_instance_masks(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, unsigned *bits,

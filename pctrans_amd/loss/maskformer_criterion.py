@@ -12,6 +12,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
+from .. import embedding_loss as _embedding_loss
 from .. import point_loss as _point_loss
 from .point_features import get_uncertain_point_coords_with_randomness, point_sample
 
@@ -147,7 +148,12 @@ class SetCriterion(nn.Module):
         # "hip": one selection kernel instead (point_loss.select_uncertain_points), where it covers the shape.  A plain
         # attribute; process default from PCT_POINT_SELECT
         self.point_select = _point_loss.select_default()
+        # "torch": loss_embedding as written below.  "hip": the label map and the loss on the device kernels of
+        # pctrans_amd/embedding_loss.py where their conditions hold (device tensors, target masks of one size, fp32 contiguous
+        # embedding, covered geometry), the code below otherwise.  A plain attribute; process default from PCT_EMB_LOSS
+        self.emb_loss = _embedding_loss.default()
         self._target_planes = None
+        self._emb_plane_index = None
 
     def _hip_target_planes(self, targets, like):
         """The images' target masks as one fp32 [sum G, Ht, Wt] tensor and each image's first plane, or None when the masks
@@ -220,7 +226,28 @@ class SetCriterion(nn.Module):
         return {"loss_mask": sigmoid_ce_loss(point_logits, point_labels, num_masks),
                 "loss_dice": dice_loss(point_logits, point_labels, num_masks)}
 
+    def _loss_embedding_hip(self, emb, targets, alpha, beta, gama):
+        """loss_embedding on the device kernels: the label map from the cached target planes, the loss with L = the largest
+        target count.  No host synchronisation.  None when the conditions do not hold."""
+        counts = [int(t["masks"].shape[0]) for t in targets]
+        if not counts or len(counts) != emb.shape[0] or not _embedding_loss.supported(emb, max(counts)):
+            return None
+        got = self._hip_target_planes(targets, emb)
+        if got is None:
+            return None
+        planes, starts = got
+        key = self._target_planes[0]
+        if self._emb_plane_index is None or self._emb_plane_index[0] != key:
+            vec = torch.tensor([starts, counts], dtype=torch.int32).to(emb.device, non_blocking=True)
+            self._emb_plane_index = (key, vec[0], vec[1])
+        labels = _embedding_loss.instance_label_map(planes, self._emb_plane_index[1], self._emb_plane_index[2], emb.shape[2:])
+        return {"loss_emb": _embedding_loss.discriminative_loss(emb, labels, max(counts), alpha=alpha, beta=beta, gama=gama)}
+
     def loss_embedding(self, emb, targets, alpha=1, beta=1, gama=0.001):
+        if self.emb_loss == "hip":
+            got = self._loss_embedding_hip(emb, targets, alpha, beta, gama)
+            if got is not None:
+                return got
         gt = []
         for target in targets:
             down = F.interpolate(target["masks"][:, None].to(torch.float), size=[emb.shape[2], emb.shape[3]],

@@ -63,6 +63,8 @@ def build(c):
         model.criterion.point_select = "hip"
     if c.get("hip_match_cost"):
         model.criterion.matcher.match_cost = "hip"
+    if c.get("hip_emb_loss"):
+        model.criterion.emb_loss = "hip"
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -95,6 +97,8 @@ def selected_configs(argv):
                         if v.get("hip_point_loss")})
     if "--hip-match-cost" in argv:          # and every selected config again with the matcher's cost matrices from the fused kernel
         configs.update({k + " + HIP match cost": dict(v, hip_match_cost=True) for k, v in list(configs.items())})
+    if "--hip-emb-loss" in argv:            # and every selected config again with the pixel-embedding loss on the device
+        configs.update({k + " + HIP embedding loss": dict(v, hip_emb_loss=True) for k, v in list(configs.items())})
     return configs
 
 
@@ -147,7 +151,7 @@ def main():
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
     flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select",
-                                                "--hip-match-cost")]
+                                                "--hip-match-cost", "--hip-emb-loss")]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
