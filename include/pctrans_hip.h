@@ -191,6 +191,8 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_train.h"
 /* ... and the instance post-processing of eval mode (logits -> label maps), behind MaskFormer.postprocess = "hip" */
 #include "pctrans_hip_post.h"
+/* the semantic head in eval mode on bf16 maps */
+#include "pctrans_hip_seg.h"
 
 /* ---- fused residual add + LayerNorm:  out = LayerNorm(x + y) * gamma + beta  over the last dimension ----------
  * Replaces the `x + dropout(y)` / `nn.LayerNorm` pairs of the encoder and decoder layers in eval mode

@@ -87,6 +87,15 @@ POST_SYMBOLS = {
     "pct_instance_labels_bf16": (_POST_LABELS, _i, "tests/test_postprocess_gpu.py"),
 }
 
+# Entry points of the semantic head in eval mode (include/pctrans_hip_seg.h; fused_ops.seg_head_forward, the decoder's default
+# on bf16 maps with gradients disabled).  A table of its own, as the post-processing's: name -> (argtypes, restype, the test
+# module that checks the entry against float64)
+SEG_SYMBOLS = {
+    "pct_conv3x3_bn_relu_bf16": ([_vp] * 6 + [ctypes.c_float, _vp] + [_i] * 5 + [_vp, _vp], _i, "tests/test_seg_head_gpu.py"),
+    "pct_seg_head_bf16": ([_vp] * 6 + [ctypes.c_float] + [_vp] * 5 + [ctypes.c_float] + [_vp] * 4 + [_i] * 5 + [_vp, _vp], _i,
+                          "tests/test_seg_head_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -104,7 +113,7 @@ def lib():
             "pctrans_amd has no CPU / eager fallback for device tensors." % LIB_PATH)
     l = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
-            (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items())]:
+            (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

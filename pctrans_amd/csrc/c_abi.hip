@@ -190,6 +190,40 @@ int pct_instance_labels_bf16(const void *logits, int batch, int num_query, int h
   return instance_labels_impl(logits, 1, batch, num_query, h, w, height, width, dataset, workspace, labels, stream);
 }
 
+int pct_conv3x3_bn_relu_bf16(const void *x, const float *w, const float *mean, const float *var, const float *gamma,
+                             const float *beta, float eps, void *w_ws, int batch, int channels, int height, int width,
+                             int channels_last, void *out, void *stream)
+{
+  if (batch < 0 || channels <= 0 || height <= 0 || width <= 0) return PCT_ERR_BAD_ARG;
+  if (batch == 0) return PCT_OK;
+  if (!x || !w || !mean || !var || !gamma || !beta || !w_ws || !out) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)x | (uintptr_t)out) & (channels_last ? 15u : 1u)) ||
+      (((uintptr_t)w | (uintptr_t)mean | (uintptr_t)var | (uintptr_t)gamma | (uintptr_t)beta) & 3u) || ((uintptr_t)w_ws & 15u))
+    return PCT_ERR_ALIGNMENT;
+  const float *const bnp[4] = {mean, var, gamma, beta};
+  return abi_status(pct::launch_conv3x3_bn_relu(x, channels_last, w, bnp, eps, w_ws, batch, channels, height, width, out,
+                                                static_cast<hipStream_t>(stream)));
+}
+
+int pct_seg_head_bf16(const void *x, const float *w_a, const float *mean_a, const float *var_a, const float *gamma_a,
+                      const float *beta_a, float eps_a, const float *w_b, const float *mean_b, const float *var_b,
+                      const float *gamma_b, const float *beta_b, float eps_b, const float *w_logits, const float *b_logits, void *w_ws,
+                      void *mid, int batch, int channels, int height, int width, int channels_last, void *out, void *stream)
+{
+  if (batch < 0 || channels <= 0 || height <= 0 || width <= 0) return PCT_ERR_BAD_ARG;
+  if (batch == 0) return PCT_OK;
+  const float *const bn_a[4] = {mean_a, var_a, gamma_a, beta_a}, *const bn_b[4] = {mean_b, var_b, gamma_b, beta_b};
+  uintptr_t f32_bits = (uintptr_t)w_a | (uintptr_t)w_b | (uintptr_t)w_logits | (uintptr_t)b_logits;
+  for (int i = 0; i < 4; ++i) {
+    if (!bn_a[i] || !bn_b[i]) return PCT_ERR_BAD_ARG;
+    f32_bits |= (uintptr_t)bn_a[i] | (uintptr_t)bn_b[i];
+  }
+  if (!x || !w_a || !w_b || !w_logits || !w_ws || !mid || !out) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)x | (uintptr_t)mid) & (channels_last ? 15u : 1u)) || ((uintptr_t)out & 1u) || (f32_bits & 3u) || ((uintptr_t)w_ws & 15u)) return PCT_ERR_ALIGNMENT;
+  return abi_status(pct::launch_seg_head(x, channels_last, w_a, bn_a, eps_a, w_b, bn_b, eps_b, w_logits, b_logits, w_ws, mid, batch, channels,
+                                         height, width, out, static_cast<hipStream_t>(stream)));
+}
+
 int pct_abi_version(void) { return PCT_ABI_VERSION; }
 
 const char *pct_error_string(int code)

@@ -118,6 +118,15 @@ int launch_add_layernorm(const float *x, const float *y, const float *gamma, con
 int launch_groupnorm_flatten(const float *x, const float *gamma, const float *beta, int N, int C, int HW, int groups, float eps,
                              float *stats, float *out, long long out_batch_stride, long long out_offset, hipStream_t stream);
 
+// ---- the decoder's semantic head in eval mode (conv3x3_bn_relu.hip; include/pctrans_hip_seg.h): bf16 maps of 128 channels, NCHW or
+// channels-last (nhwc).  PCT_NOT_COVERED for any other channel count or an image of 2^24 pixels or more.
+// bnp / bn_a / bn_b: {mean, var, gamma, beta} ----
+int launch_conv3x3_bn_relu(const void *x, int nhwc, const float *w, const float *const *bnp, float eps, void *w_ws, int N, int C, int H,
+                           int W, void *out, hipStream_t stream);
+int launch_seg_head(const void *x, int nhwc, const float *w_a, const float *const *bn_a, float eps_a, const float *w_b,
+                    const float *const *bn_b, float eps_b, const float *w_logits, const float *b_logits, void *w_ws, void *mid,
+                    int N, int C, int H, int W, void *out, hipStream_t stream);
+
 // ---- the decoder's attention and the matcher ------------------------------------------------------------------------
 int launch_masked_attention(const void *q, const void *k, const void *vT, const unsigned char *mask, int N, int heads, int Q,
                             int S, int head_dim, int v_head_dim, float scale, int out_dtype, void *out, hipStream_t stream);

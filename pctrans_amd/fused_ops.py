@@ -356,6 +356,109 @@ def conv1x1_groupnorm_tokens_into(x, conv, gn, out, row_offset):
     _lib.check(rc, "conv1x1_groupnorm_tokens")
 
 
+_SEG_WS = {}                  # (device, stream) -> weight-image workspace of the semantic head's two 3x3 convolutions
+
+
+def _seg_block_supported(x, block):
+    """Sequential(conv3x3(128 -> 128, stride 1, padding 1, no bias), a _BatchNorm in eval mode with running statistics, ReLU)
+    with fp32 parameters on x's device."""
+    if not (isinstance(block, torch.nn.Sequential) and len(block) == 3):
+        return False
+    conv, bn, act = block[0], block[1], block[2]
+    if not (isinstance(conv, torch.nn.Conv2d) and isinstance(bn, torch.nn.modules.batchnorm._BatchNorm)
+            and isinstance(act, torch.nn.ReLU)):
+        return False
+    w = conv.weight
+    tensors = (w, bn.running_mean, bn.running_var, bn.weight, bn.bias)
+    return (tuple(w.shape) == (128, 128, 3, 3) and conv.bias is None and tuple(conv.stride) == (1, 1)
+            and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1
+            and conv.padding_mode == "zeros" and getattr(conv, "norm", None) is None
+            and getattr(conv, "activation", None) is None and not bn.training and bn.num_features == 128
+            and all(t is not None and t.dtype == torch.float32 and t.device == x.device and t.is_contiguous()
+                    for t in tensors))
+
+
+def _seg_layout(x):
+    """0: contiguous NCHW; 1: dense channels-last (what the mask features are as a view of the encoder's token rows); None."""
+    if x.is_contiguous():
+        return 0
+    n, c, h, w = x.shape
+    if x.stride() == (h * w * c, 1, w * c, c) and x.data_ptr() % 16 == 0:
+        return 1
+    return None
+
+
+def _seg_input_supported(x):
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[1] == 128 and x.numel() > 0
+            and _seg_layout(x) is not None and x.shape[2] * x.shape[3] < 2 ** 24 and not torch.is_grad_enabled())
+
+
+def _seg_ws(x):
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    ws = _SEG_WS.get((x.device, stream))
+    if ws is None:
+        ws = _SEG_WS[(x.device, stream)] = torch.empty((2, 128 * 128 * 9), dtype=torch.bfloat16, device=x.device)
+    return ws, stream
+
+
+def _bn_args(bn):
+    return (bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), float(bn.eps))
+
+
+def conv3x3_bn_relu_supported(x, block):
+    """A dense bf16 device map with 128 channels, NCHW or channels-last, gradients disabled, through one block of the semantic head in eval
+    mode (csrc/conv3x3_bn_relu.hip)."""
+    return _seg_input_supported(x) and _seg_block_supported(x, block)
+
+
+def conv3x3_bn_relu(x, block):
+    """block(x) for Sequential(Conv2d(128, 128, 3, padding=1, bias=False), BatchNorm.eval(), ReLU) on a bf16 map: one HIP
+    kernel with the rounding points of the autocast chain.  Falls back to the module where the kernel does not apply."""
+    if not conv3x3_bn_relu_supported(x, block):
+        return block(x)
+    n, _, h, w_ = x.shape
+    ws, stream = _seg_ws(x)
+    out = torch.empty_like(x)                                    # (keeps x's layout, as the library convolution does)
+    with torch.cuda.device(x.device), _timing.timed("conv3x3_bn_relu", x):
+        rc = _lib.lib().pct_conv3x3_bn_relu_bf16(x.data_ptr(), block[0].weight.data_ptr(), *_bn_args(block[1]), ws.data_ptr(),
+                                                 n, 128, h, w_, _seg_layout(x), out.data_ptr(), stream)
+    _lib.check(rc, "conv3x3_bn_relu")
+    return out
+
+
+def seg_head_supported(x, seg_head, logits):
+    """The decoder's semantic head in eval mode: a dense bf16 [N, 128, H, W] device map (NCHW or channels-last), gradients disabled, two
+    conv3x3 + BatchNorm(eval) + ReLU blocks and a 1x1 convolution to one channel."""
+    if not (_seg_input_supported(x) and isinstance(seg_head, torch.nn.Sequential) and len(seg_head) == 2
+            and all(_seg_block_supported(x, b) for b in seg_head) and isinstance(logits, torch.nn.Conv2d)):
+        return False
+    w, b = logits.weight, logits.bias
+    return (tuple(w.shape) == (1, 128, 1, 1) and tuple(logits.stride) == (1, 1) and tuple(logits.padding) == (0, 0)
+            and logits.groups == 1 and getattr(logits, "norm", None) is None and getattr(logits, "activation", None) is None
+            and w.dtype == torch.float32 and w.device == x.device and w.is_contiguous()
+            and (b is None or (b.dtype == torch.float32 and b.device == x.device)))
+
+
+def seg_head_forward(x, seg_head, logits):
+    """logits(seg_head(x)) as bf16 [N, 1, H, W] (csrc/conv3x3_bn_relu.hip): each block is one kernel, the second with the 1x1
+    convolution in its epilogue, so neither the batch-norm and ReLU passes nor the second block's map touch memory.  Where
+    seg_head_supported does not hold: the torch expression, unchanged."""
+    if not seg_head_supported(x, seg_head, logits):
+        return logits(seg_head(x))
+    n, _, h, w_ = x.shape
+    ws, stream = _seg_ws(x)
+    mid = torch.empty_like(x)
+    out = torch.empty((n, 1, h, w_), dtype=torch.bfloat16, device=x.device)
+    a, b = seg_head[0], seg_head[1]
+    with torch.cuda.device(x.device), _timing.timed("seg_head", x):
+        rc = _lib.lib().pct_seg_head_bf16(
+            x.data_ptr(), a[0].weight.data_ptr(), *_bn_args(a[1]), b[0].weight.data_ptr(), *_bn_args(b[1]),
+            logits.weight.data_ptr(), logits.bias.data_ptr() if logits.bias is not None else None, ws.data_ptr(),
+            mid.data_ptr(), n, 128, h, w_, _seg_layout(x), out.data_ptr(), stream)
+    _lib.check(rc, "seg_head")
+    return out
+
+
 def groupnorm_flatten_supported(x, gn):
     """fp32 NCHW device tensor, 128 channels, groups of a multiple of 4 channels, affine, forward only."""
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 128 and x.is_contiguous()

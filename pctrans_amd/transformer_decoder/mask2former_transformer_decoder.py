@@ -419,7 +419,8 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         predictions_mask = list(flat[2:2 + n_pred])
         # the semantic head (:533-534) stays outside the core: it holds the decoder's only BatchNorm (SyncBN in the shipped
         # yamls), whose cross-rank exchange cannot be part of a captured graph
-        sem_logits_pred = self.logits(self.seg_head(mf_lp)) if self.sem_loss_on else None
+        # (in eval mode on bf16 maps: two fused HIP kernels, fused_ops.seg_head_forward; otherwise this torch expression)
+        sem_logits_pred = fused_ops.seg_head_forward(mf_lp, self.seg_head, self.logits) if self.sem_loss_on else None
 
         indices_list = []
         if targets is not None:

@@ -1,0 +1,194 @@
+"""GPU: the semantic head in eval mode on the HIP kernels (csrc/conv3x3_bn_relu.hip; fused_ops.seg_head_forward,
+fused_ops.conv3x3_bn_relu) against the torch chain it replaces, with float64 as the arbiter.
+
+The reference is the same modules evaluated by torch on the GPU under bf16 autocast.  The arbiter is the float64 CPU evaluation
+of conv -> BN -> ReLU -> conv -> BN -> ReLU -> 1x1 from the bf16-rounded input and the bf16-rounded convolution weights, with no
+intermediate rounding.  No tolerance is invented: with e_torch = max |torch - fp64| and e_hip = max |HIP - fp64| over all
+elements of a case,
+    whole head:  e_hip <= 2 * e_torch + one bf16 ulp at the output's magnitude   (another fp32 summation order flips bf16
+                 roundings of the first block, which then propagate through the second convolution)
+    one block:   e_hip <= e_torch + one bf16 ulp                                  (one rounding chain)
+Shapes: the smallest at which the kernel can go wrong -- all halo (1 x 1), odd sizes, more than one tile in each direction, and
+one pixel less / more than the kernel's 8 x 32 tile in each dimension (7 x 31, 9 x 33) -- each as a contiguous NCHW map and as
+the dense channels-last map the decoder's mask features are.  PCT_SEG_HEAD_REPORT=<file> writes the
+measured figures of every case there as JSON."""
+import atexit
+import copy
+import json
+import math
+import os
+
+import pytest
+import torch
+from torch import nn
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1, 1), (2, 5, 7), (1, 17, 23), (3, 33, 16), (2, 64, 64), (1, 7, 31), (1, 9, 33)]
+_FIGURES = {}
+
+
+def _report():
+    path = os.environ.get("PCT_SEG_HEAD_REPORT")
+    if path and _FIGURES:
+        with open(path, "w") as f:
+            json.dump(_FIGURES, f, indent=1, sort_keys=True)
+
+
+atexit.register(_report)
+
+
+def _head(seed, channels=128, gamma_zero=False):
+    """The decoder's seg_head + logits as it builds them (conv_with_kaiming_uniform("BN", activation=True)), with non-trivial
+    BatchNorm buffers: running_var in [0.25, 4], mean != 0, gamma of both signs."""
+    from pctrans_amd.transformer_decoder.mask2former_transformer_decoder import conv_with_kaiming_uniform
+    from pctrans_amd.layers import Conv2d
+    g = torch.Generator().manual_seed(seed)
+    block = conv_with_kaiming_uniform("BN", activation=True)
+    seg = nn.Sequential(block(channels, channels, kernel_size=3, stride=1), block(channels, channels, kernel_size=3, stride=1))
+    logits = Conv2d(channels, 1, kernel_size=1, stride=1)
+    with torch.no_grad():
+        for b in seg:
+            b[0].weight.copy_(torch.randn(b[0].weight.shape, generator=g) * (2.0 / (channels * 9)) ** 0.5)
+            b[1].running_var.copy_(torch.rand(channels, generator=g) * 3.75 + 0.25)
+            b[1].running_mean.copy_(torch.randn(channels, generator=g) * 0.5 + 0.1)
+            b[1].weight.copy_(torch.randn(channels, generator=g))
+            b[1].bias.copy_(torch.randn(channels, generator=g) * 0.5)
+            if gamma_zero:
+                b[1].weight[5] = 0.0
+        logits.weight.copy_(torch.randn(logits.weight.shape, generator=g) * channels ** -0.5)
+        logits.bias.fill_(-math.log(99.0))
+    return seg.cuda().eval(), logits.cuda().eval()
+
+
+def _bf16_64(t):
+    return t.detach().to(torch.bfloat16).double().cpu()
+
+
+def _block64(x64, block):
+    bn = block[1]
+    z = torch.nn.functional.conv2d(x64, _bf16_64(block[0].weight), padding=1)
+    s = (bn.running_var.double().cpu() + bn.eps).rsqrt() * bn.weight.detach().double().cpu()
+    z = (z - bn.running_mean.double().cpu()[None, :, None, None]) * s[None, :, None, None]
+    return (z + bn.bias.detach().double().cpu()[None, :, None, None]).clamp_(min=0)
+
+
+def _head64(x, seg, logits):
+    a1 = _block64(x.double().cpu(), seg[0])
+    a2 = _block64(a1, seg[1])
+    out = torch.nn.functional.conv2d(a2, _bf16_64(logits.weight), logits.bias.detach().double().cpu())
+    return a1, out
+
+
+def _ulp(ref):
+    m = float(ref.abs().max())
+    return 2.0 ** (math.floor(math.log2(m)) - 7) if m > 0 else 2.0 ** -133
+
+
+def _err(got, ref):
+    return float((got.double().cpu() - ref).abs().max())
+
+
+def _check(N, H, W, gamma_zero, channels_last=False):
+    from pctrans_amd import fused_ops
+    seg, logits = _head(100 + H * W, gamma_zero=gamma_zero)
+    g = torch.Generator().manual_seed(N * 1000 + H * 31 + W)
+    x = torch.randn(N, 128, H, W, generator=g).to(torch.bfloat16).cuda()
+    if channels_last:
+        x = x.contiguous(memory_format=torch.channels_last)
+    ref1, ref = _head64(x, seg, logits)
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+        want1 = seg[0](x)
+        want = logits(seg(x))
+        assert fused_ops.conv3x3_bn_relu_supported(x, seg[0]) and fused_ops.seg_head_supported(x, seg, logits)
+        got1 = fused_ops.conv3x3_bn_relu(x, seg[0])
+        got = fused_ops.seg_head_forward(x, seg, logits)
+    torch.cuda.synchronize()
+    assert got.dtype == want.dtype == torch.bfloat16 and got.shape == want.shape == (N, 1, H, W)
+    assert got1.dtype == torch.bfloat16 and got1.shape == want1.shape and got1.stride() == x.stride()
+    fig = {"block1": {"e_torch": _err(want1, ref1), "e_hip": _err(got1, ref1), "ulp": _ulp(ref1)},
+           "head": {"e_torch": _err(want, ref), "e_hip": _err(got, ref), "ulp": _ulp(ref)}}
+    _FIGURES["%dx%dx%d%s%s" % (N, H, W, "_nhwc" if channels_last else "", "_gamma0" if gamma_zero else "")] = fig
+    print(N, H, W, channels_last, gamma_zero, fig)
+    assert fig["block1"]["e_hip"] <= fig["block1"]["e_torch"] + fig["block1"]["ulp"], fig
+    assert fig["head"]["e_hip"] <= 2 * fig["head"]["e_torch"] + fig["head"]["ulp"], fig
+    if gamma_zero:                                   # relu(bf16(beta)) in every pixel of that channel
+        b = seg[0][1].bias[5].to(torch.bfloat16).clamp(min=0)
+        assert bool((got1[:, 5] == b).all())
+
+
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+def test_borders_are_zero_padded_exactly(channels_last):
+    """All-ones input and weights, BatchNorm as the identity (mean 0, var 1, eps 0): block 1's values are the number of taps
+    inside the image times 128 -- 4 * 128 in the corners, 6 * 128 on the edges, 9 * 128 inside -- also where tiles meet."""
+    from pctrans_amd import fused_ops
+    seg, _ = _head(1)
+    blk = seg[0]
+    with torch.no_grad():
+        blk[0].weight.fill_(1.0)
+        blk[1].running_mean.zero_()
+        blk[1].running_var.fill_(1.0)
+        blk[1].weight.fill_(1.0)
+        blk[1].bias.zero_()
+    blk[1].eps = 0.0
+    H, W = 17, 65
+    x = torch.ones(2, 128, H, W, dtype=torch.bfloat16, device="cuda")
+    if channels_last:
+        x = x.contiguous(memory_format=torch.channels_last)
+    with torch.no_grad():
+        assert fused_ops.conv3x3_bn_relu_supported(x, blk)
+        got = fused_ops.conv3x3_bn_relu(x, blk).float()
+    taps = torch.full((H, W), 9.0)
+    taps[0, :] = taps[-1, :] = 6.0
+    taps[:, 0] = taps[:, -1] = 6.0
+    taps[0, 0] = taps[0, -1] = taps[-1, 0] = taps[-1, -1] = 4.0
+    assert torch.equal(got.cpu(), (taps * 128.0).expand(2, 128, H, W))
+
+
+def test_everything_outside_the_contract_keeps_the_torch_path(monkeypatch):
+    """fp32 input, BatchNorm in training mode, 64 channels, a strided view, gradients enabled: the torch expression is evaluated
+    and the library is not entered.  (The library convolutions are not bit-reproducible from call to call, so the values are
+    compared at the dtype's default closeness; that the HIP entry is not reached is what is exact.)"""
+    from pctrans_amd import fused_ops
+    seg, logits = _head(2)
+    x = torch.randn(2, 128, 9, 12, device="cuda")
+    xb = x.to(torch.bfloat16)
+    with torch.no_grad():
+        assert fused_ops.seg_head_supported(xb, seg, logits)
+    monkeypatch.setattr(fused_ops._lib, "lib", lambda: (_ for _ in ()).throw(AssertionError("HIP path taken")))
+    close = torch.testing.assert_close
+    with torch.no_grad():
+        assert not fused_ops.seg_head_supported(x, seg, logits)                       # fp32 input
+        close(fused_ops.seg_head_forward(x, seg, logits), logits(seg(x)))
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            # BatchNorm in training mode (batch statistics): two copies, as each evaluation updates the running buffers
+            a, b = copy.deepcopy(seg).train(), copy.deepcopy(seg).train()
+            assert not fused_ops.seg_head_supported(xb, a, logits)
+            close(fused_ops.seg_head_forward(xb, a, logits), logits(b(xb)))
+            close(a[0][1].running_mean, b[0][1].running_mean)
+            assert not torch.equal(a[0][1].running_mean, seg[0][1].running_mean)       # ... and they were updated
+            seg64, logits64 = _head(3, channels=64)                                      # 64 channels
+            x64 = xb[:, :64].contiguous()
+            assert not fused_ops.seg_head_supported(x64, seg64, logits64)
+            assert not fused_ops.conv3x3_bn_relu_supported(x64, seg64[0])
+            close(fused_ops.seg_head_forward(x64, seg64, logits64), logits64(seg64(x64)))
+            close(fused_ops.conv3x3_bn_relu(x64, seg64[0]), seg64[0](x64))
+            xt = xb.transpose(2, 3)                                                      # a view that is not dense in either layout
+            assert not fused_ops.seg_head_supported(xt, seg, logits)
+            close(fused_ops.seg_head_forward(xt, seg, logits), logits(seg(xt)))
+    with torch.autocast("cuda", dtype=torch.bfloat16):                                   # gradients enabled
+        assert not fused_ops.seg_head_supported(xb, seg, logits)
+        out = fused_ops.seg_head_forward(xb, seg, logits)
+        assert out.requires_grad
+        close(out, logits(seg(xb)))
+
+
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("N,H,W", SHAPES)
+def test_head_and_first_block_are_as_close_to_float64_as_the_torch_chain(N, H, W, channels_last):
+    _check(N, H, W, False, channels_last)
+
+
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+def test_a_channel_with_gamma_zero(channels_last):
+    _check(1, 17, 23, True, channels_last)
