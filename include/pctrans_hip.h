@@ -193,6 +193,8 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_post.h"
 /* the semantic head in eval mode on bf16 maps */
 #include "pctrans_hip_seg.h"
+/* one FPN level of the pixel decoder in eval mode, behind MSDeformAttnPixelDecoder.fpn = "hip" */
+#include "pctrans_hip_fpn.h"
 
 /* ---- fused residual add + LayerNorm:  out = LayerNorm(x + y) * gamma + beta  over the last dimension ----------
  * Replaces the `x + dropout(y)` / `nn.LayerNorm` pairs of the encoder and decoder layers in eval mode

@@ -96,6 +96,15 @@ SEG_SYMBOLS = {
                           "tests/test_seg_head_gpu.py"),
 }
 
+# Entry point of the pixel decoder's FPN level in eval mode (include/pctrans_hip_fpn.h; fused_ops.fpn_stage, reached with
+# MSDeformAttnPixelDecoder.fpn = "hip").  A table of its own, as the semantic head's: name -> (argtypes, restype, the test module
+# that checks the entry against float64)
+_FPN_CONV = [_vp] * 6 + [ctypes.c_float]                          # w, bias, mean, var, gamma, beta, eps
+FPN_SYMBOLS = {
+    "pct_fpn_stage_f32": ([_vp, _vp, ctypes.c_longlong, _i] + _FPN_CONV + _FPN_CONV + [_vp, _vp] + [_i] * 5 + [_vp, _vp], _i,
+                          "tests/test_fpn_stage_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -113,7 +122,8 @@ def lib():
             "pctrans_amd has no CPU / eager fallback for device tensors." % LIB_PATH)
     l = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
-            (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())]:
+            (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
+            + list(FPN_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

@@ -224,6 +224,34 @@ int pct_seg_head_bf16(const void *x, const float *w_a, const float *mean_a, cons
                                          height, width, out, static_cast<hipStream_t>(stream)));
 }
 
+int pct_fpn_stage_f32(const float *x, const float *enc, long long enc_batch_stride, int enc_channels_last, const float *w_lateral,
+                      const float *b_lateral, const float *mean_lateral, const float *var_lateral, const float *gamma_lateral,
+                      const float *beta_lateral, float eps_lateral, const float *w_output, const float *b_output,
+                      const float *mean_output, const float *var_output, const float *gamma_output, const float *beta_output,
+                      float eps_output, void *w_ws, float *y_ws, int batch, int in_channels, int channels, int height, int width,
+                      float *out, void *stream)
+{
+  if (batch < 0 || in_channels <= 0 || channels <= 0 || height <= 0 || width <= 0) return PCT_ERR_BAD_ARG;
+  if (enc_batch_stride < (long long)channels * height * width) return PCT_ERR_BAD_ARG;
+  if (batch == 0) return PCT_OK;
+  if (!x || !enc || !w_lateral || !w_output || !w_ws || !y_ws || !out) return PCT_ERR_BAD_ARG;
+  const float *const n1[4] = {mean_lateral, var_lateral, gamma_lateral, beta_lateral};
+  const float *const n3[4] = {mean_output, var_output, gamma_output, beta_output};
+  uintptr_t f32_bits = (uintptr_t)w_lateral | (uintptr_t)b_lateral | (uintptr_t)w_output | (uintptr_t)b_output | (uintptr_t)out;
+  for (int i = 0; i < 4; ++i) {                                    /* a norm is given whole or not at all */
+    if ((n1[0] && !n1[i]) || (n3[0] && !n3[i]) || (!n1[0] && n1[1]) || (!n3[0] && n3[1])) return PCT_ERR_BAD_ARG;
+    if (n1[0]) f32_bits |= (uintptr_t)n1[i];
+    if (n3[0]) f32_bits |= (uintptr_t)n3[i];
+  }
+  if (channels != 128 || in_channels % 16 || (long long)height * width >= (1LL << 24)) return PCT_ERR_UNSUPPORTED;
+  if ((((uintptr_t)x | (uintptr_t)w_ws | (uintptr_t)y_ws) & 15u) || (f32_bits & 3u) ||
+      ((uintptr_t)enc & (enc_channels_last ? 15u : 3u)) || (enc_channels_last && (enc_batch_stride & 3)))
+    return PCT_ERR_ALIGNMENT;
+  return abi_status(pct::launch_fpn_stage(x, enc, enc_batch_stride, enc_channels_last, w_lateral, b_lateral, n1, eps_lateral, w_output,
+                                          b_output, n3, eps_output, w_ws, y_ws, batch, in_channels, height, width, out,
+                                          static_cast<hipStream_t>(stream)));
+}
+
 int pct_abi_version(void) { return PCT_ABI_VERSION; }
 
 const char *pct_error_string(int code)

@@ -127,6 +127,13 @@ int launch_seg_head(const void *x, int nhwc, const float *w_a, const float *cons
                     const float *const *bn_b, float eps_b, const float *w_logits, const float *b_logits, void *w_ws, void *mid,
                     int N, int C, int H, int W, void *out, hipStream_t stream);
 
+// ---- one FPN level of the pixel decoder in eval mode (fpn_stage.hip; include/pctrans_hip_fpn.h): fp32, split-bf16 products.
+// norm1 / norm3: {mean, var, gamma, beta}, a null mean = no norm.  PCT_NOT_COVERED: in_channels % 16 != 0 or an image of 2^24
+// pixels or more ----
+int launch_fpn_stage(const float *x, const float *enc, long long enc_batch_stride, int enc_nhwc, const float *w1, const float *b1,
+                     const float *const *norm1, float eps1, const float *w3, const float *b3, const float *const *norm3, float eps3,
+                     void *w_ws, float *y_ws, int N, int K, int H, int W, float *out, hipStream_t stream);
+
 // ---- the decoder's attention and the matcher ------------------------------------------------------------------------
 int launch_masked_attention(const void *q, const void *k, const void *vT, const unsigned char *mask, int N, int heads, int Q,
                             int S, int head_dim, int v_head_dim, float scale, int out_dtype, void *out, hipStream_t stream);

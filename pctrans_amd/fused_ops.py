@@ -459,6 +459,117 @@ def seg_head_forward(x, seg_head, logits):
     return out
 
 
+_FPN_WS = {}                  # (device, stream, in_channels) -> weight-image workspace of fpn_stage (refilled per call)
+
+
+def fpn_default():
+    """Process default of MSDeformAttnPixelDecoder's `fpn` switch: PCT_FPN = hip | torch (default torch)."""
+    import os
+    v = os.environ.get("PCT_FPN") or "torch"
+    if v not in ("hip", "torch"):
+        raise RuntimeError("PCT_FPN must be 'hip' or 'torch', got %r" % v)
+    return v
+
+
+def _fpn_norm_tensors(norm):
+    """The norm of a layers.Conv2d as fixed statistics -> (running_mean, running_var, weight, bias); () for no norm; None for
+    anything that is not a per-channel affine at this point (GroupNorm, LayerNorm2d, batch statistics)."""
+    from .layers import FrozenBatchNorm2d
+    if norm is None:
+        return ()
+    if isinstance(norm, torch.nn.modules.batchnorm._BatchNorm):
+        if norm.training or norm.running_mean is None or norm.running_var is None or norm.weight is None or norm.bias is None:
+            return None
+    elif not isinstance(norm, FrozenBatchNorm2d):
+        return None
+    return (norm.running_mean, norm.running_var, norm.weight, norm.bias)
+
+
+def _fpn_conv_tensors(conv, in_channels, kernel, padding):
+    """-> the tensors of a layers.Conv2d(in_channels -> 128, kernel) + norm the kernels read, or None where they do not apply."""
+    if not (isinstance(conv, torch.nn.Conv2d) and conv.out_channels == 128 and conv.in_channels == in_channels
+            and tuple(conv.kernel_size) == (kernel, kernel) and tuple(conv.stride) == (1, 1) and tuple(conv.dilation) == (1, 1)
+            and conv.padding == (padding, padding) and conv.padding_mode == "zeros" and conv.groups == 1):
+        return None
+    nt = _fpn_norm_tensors(getattr(conv, "norm", None))
+    if nt is None or (nt == () and conv.bias is None):
+        return None
+    if nt and int(nt[0].numel()) != 128:
+        return None
+    return (conv.weight,) + ((conv.bias,) if conv.bias is not None else ()) + nt
+
+
+def _fpn_enc_layout(enc):
+    """0: contiguous NCHW; 1: channels-last view of token rows (images any multiple of 4 floats >= H * W * 128 apart); None."""
+    if enc.is_contiguous():
+        return 0
+    n, c, h, w = enc.shape
+    s = enc.stride()
+    if (s[1:] == (1, w * c, c) and (n == 1 or (s[0] >= h * w * c and s[0] % 4 == 0)) and enc.data_ptr() % 16 == 0):
+        return 1
+    return None
+
+
+def fpn_stage_supported(x, enc, lateral_conv, output_conv):
+    """One FPN level on the HIP kernels (csrc/fpn_stage.hip): fp32 device maps outside autocast with no gradient required, x
+    contiguous NCHW with in_channels % 16 == 0 and exactly twice enc's height and width, enc [N, 128, H, W] contiguous or the
+    channels-last view of the encoder's token rows, lateral_conv a 1x1 and output_conv a 3x3 (padding 1, ReLU) layers.Conv2d to
+    128 channels, each with no norm (and a bias), a _BatchNorm in eval mode with running statistics, or FrozenBatchNorm2d."""
+    if not (torch.is_tensor(x) and torch.is_tensor(enc) and x.is_cuda and enc.is_cuda and x.dtype == torch.float32
+            and enc.dtype == torch.float32 and x.device == enc.device and x.dim() == 4 and enc.dim() == 4):
+        return False
+    if torch.is_autocast_enabled():
+        return False
+    n, c, h, w = enc.shape
+    if not (c == 128 and x.shape[0] == n and n > 0 and h > 0 and w > 0 and tuple(x.shape[2:]) == (2 * h, 2 * w)
+            and x.shape[1] % 16 == 0 and h * w < 2 ** 24 and n * ((h + 3) // 4) * ((w + 31) // 32) < 2 ** 31 - 1
+            and x.is_contiguous() and x.data_ptr() % 16 == 0 and _fpn_enc_layout(enc) is not None):
+        return False
+    if getattr(lateral_conv, "activation", None) is not None or getattr(output_conv, "activation", None) is not F.relu:
+        return False
+    lat, outc = _fpn_conv_tensors(lateral_conv, x.shape[1], 1, 0), _fpn_conv_tensors(output_conv, 128, 3, 1)
+    if lat is None or outc is None:
+        return False
+    tensors = lat + outc
+    if not all(t.dtype == torch.float32 and t.device == x.device and t.is_contiguous() for t in tensors):
+        return False
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, enc) + tensors))
+
+
+def _fpn_conv_args(conv):
+    norm = getattr(conv, "norm", None)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    if norm is None:
+        return [ptr(conv.weight), ptr(conv.bias), None, None, None, None, 0.0]
+    return [ptr(conv.weight), ptr(conv.bias), ptr(norm.running_mean), ptr(norm.running_var), ptr(norm.weight), ptr(norm.bias),
+            float(norm.eps)]
+
+
+def fpn_stage(x, enc, lateral_conv, output_conv):
+    """output_conv(enc + F.interpolate(lateral_conv(x), size=enc.shape[-2:], mode="bilinear", align_corners=False)) as dense fp32
+    NCHW, for x twice as high and wide as enc (the resize is then the 2 x 2 mean, taken before the 1x1 convolution): three launches,
+    exact split-bf16 products, enc read where it lies.  Where fpn_stage_supported does not hold: the torch expression, unchanged."""
+    if not fpn_stage_supported(x, enc, lateral_conv, output_conv):
+        cur_fpn = lateral_conv(x)
+        return output_conv(enc + F.interpolate(cur_fpn, size=enc.shape[-2:], mode="bilinear", align_corners=False))
+    n, _, h, w_ = enc.shape
+    k = x.shape[1]
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    key = (x.device, stream, k)
+    ws = _FPN_WS.get(key)
+    if ws is None:
+        ws = _FPN_WS[key] = torch.empty(((k // 16 + 72) * 12288,), dtype=torch.uint8, device=x.device)
+    nhwc = _fpn_enc_layout(enc)
+    y = torch.empty((n, 128, h, w_), dtype=torch.float32, device=x.device)       # scratch in the kernels' own layout
+    out = torch.empty((n, 128, h, w_), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timing.timed("fpn_stage", x):
+        rc = _lib.lib().pct_fpn_stage_f32(
+            x.data_ptr(), enc.data_ptr(), enc.stride(0) if n > 1 else 128 * h * w_, nhwc, *_fpn_conv_args(lateral_conv),
+            *_fpn_conv_args(output_conv), ws.data_ptr(), y.data_ptr(), n, k, 128, h, w_, out.data_ptr(), stream)
+    _lib.check(rc, "fpn_stage")
+    return out
+
+
 def groupnorm_flatten_supported(x, gn):
     """fp32 NCHW device tensor, 128 channels, groups of a multiple of 4 channels, affine, forward only."""
     return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 128 and x.is_contiguous()

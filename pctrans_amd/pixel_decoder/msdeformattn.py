@@ -245,6 +245,9 @@ class MSDeformAttnPixelDecoder(nn.Module):
             output_convs.append(output_conv)
         self.lateral_convs = lateral_convs[::-1]     # top-down order
         self.output_convs = output_convs[::-1]
+        # "hip": an FPN level that fused_ops.fpn_stage_supported covers (eval mode, fixed-statistics norms, fp32, resize ratio 2)
+        # runs on csrc/fpn_stage.hip; "torch": the statements below for every level.  Process default: PCT_FPN
+        self.fpn = fused_ops.fpn_default()
 
     @classmethod
     def from_config(cls, cfg, input_shape: Dict[str, ShapeSpec]):
@@ -300,6 +303,11 @@ class MSDeformAttnPixelDecoder(nn.Module):
                    for z, s in zip(torch.split(y, sizes, dim=1), srcs)]
 
             for idx, f in enumerate(self.in_features[:self.num_fpn_levels][::-1]):
+                if self.fpn == "hip":
+                    x = features[f].float()
+                    if fused_ops.fpn_stage_supported(x, out[-1], self.lateral_convs[idx], self.output_convs[idx]):
+                        out.append(fused_ops.fpn_stage(x, out[-1], self.lateral_convs[idx], self.output_convs[idx]))
+                        continue
                 cur_fpn = self.lateral_convs[idx](features[f].float())
                 y = out[-1] + F.interpolate(cur_fpn, size=out[-1].shape[-2:], mode="bilinear", align_corners=False)
                 out.append(self.output_convs[idx](y))

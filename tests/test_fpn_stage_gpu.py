@@ -1,0 +1,278 @@
+"""GPU: one FPN level of the pixel decoder on the HIP kernels (csrc/fpn_stage.hip; fused_ops.fpn_stage, reached with
+MSDeformAttnPixelDecoder.fpn = "hip") against the torch statements it replaces, with float64 as the arbiter.
+
+The yardstick is the unchanged statements of forward_features (lateral conv + norm, F.interpolate, add, output conv + norm +
+ReLU) evaluated by torch on the GPU in fp32.  The arbiter is their float64 evaluation on the CPU from the same fp32 inputs and
+parameters, in the statements' own order (convolution, then resize), with no intermediate rounding.  No tolerance is invented:
+with e = max |. - fp64| over all elements of a case,
+    e_hip <= 2 * e_torch + 2^-22 * max |ref|
+(the rule of test_fused_ops_gpu.py for the split-bf16 convolutions: 2 because the two results sum in different orders, the
+floor for cases where torch happens to be exact).
+Shapes (N, Cin, H, W of the output map): all halo (1 x 1), odd sizes, more than one tile in each direction, the BBBC map
+65 x 87, and one pixel less / more than the tile in each dimension -- both kernels tile the output map in 4 rows x 32 columns,
+so (3, 31) and (5, 33).  Each with enc as a contiguous NCHW map and as the channels-last view of a larger [N, S, 128] token
+tensor at a non-zero row offset, and with the norms "", "BN" and "FrozenBN" (var in [0.25, 4], mean != 0, gamma of both signs,
+one gamma = 0 on the output convolution, whose channel must be exactly relu(beta)).
+PCT_FPN_REPORT=<file> writes the measured figures of every case there as JSON."""
+import atexit
+import copy
+import json
+import os
+
+import pytest
+import torch
+from torch.nn import functional as F
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 16, 1, 1), (2, 64, 5, 7), (1, 256, 17, 23), (3, 64, 33, 16), (2, 256, 64, 64), (1, 128, 65, 87), (1, 16, 3, 31),
+          (1, 16, 5, 33)]
+NORMS = ["", "BN", "FrozenBN"]
+ZERO_GAMMA = 5
+_FIGURES = {}
+_CASES = {}
+
+
+def _report():
+    path = os.environ.get("PCT_FPN_REPORT")
+    if path and _FIGURES:
+        with open(path, "w") as f:
+            json.dump(_FIGURES, f, indent=1, sort_keys=True)
+
+
+atexit.register(_report)
+
+
+def _fill_norm(norm, g, zero=None):
+    if norm is None:
+        return
+    with torch.no_grad():
+        norm.running_var.copy_(torch.rand(128, generator=g) * 3.75 + 0.25)
+        norm.running_mean.copy_(torch.randn(128, generator=g) * 0.5 + 0.1)
+        norm.weight.copy_(torch.randn(128, generator=g))
+        norm.bias.copy_(torch.randn(128, generator=g) * 0.5)
+        if zero is not None:
+            norm.weight[zero] = 0.0
+
+
+def _convs(norm, cin, seed):
+    """The two convolutions as the pixel decoder builds them (msdeformattn.py: adapter_1 / layer_1), with non-trivial statistics"""
+    from pctrans_amd.layers import Conv2d, get_norm
+    g = torch.Generator().manual_seed(seed)
+    lat = Conv2d(cin, 128, kernel_size=1, bias=norm == "", norm=get_norm(norm, 128))
+    outc = Conv2d(128, 128, kernel_size=3, stride=1, padding=1, bias=norm == "", norm=get_norm(norm, 128), activation=F.relu)
+    with torch.no_grad():
+        lat.weight.copy_(torch.randn(lat.weight.shape, generator=g) * cin ** -0.5)
+        outc.weight.copy_(torch.randn(outc.weight.shape, generator=g) * (2.0 / (128 * 9)) ** 0.5)
+        for c in (lat, outc):
+            if c.bias is not None:
+                c.bias.copy_(torch.randn(128, generator=g) * 0.3)
+    _fill_norm(lat.norm, g)
+    _fill_norm(outc.norm, g, ZERO_GAMMA)
+    return lat.eval(), outc.eval()
+
+
+def _affine64(z, conv):
+    d = lambda t: t.detach().double().cpu()[None, :, None, None]
+    if conv.bias is not None:
+        z = z + d(conv.bias)
+    n = conv.norm
+    if n is not None:
+        z = (z - d(n.running_mean)) * (d(n.running_var) + n.eps).rsqrt() * d(n.weight) + d(n.bias)
+    return z
+
+
+def _stage64(x, enc, lat, outc):
+    """the loop's statements in float64 on the CPU"""
+    x64, e64 = x.detach().double().cpu(), enc.detach().double().cpu()
+    cur = _affine64(F.conv2d(x64, lat.weight.detach().double().cpu()), lat)
+    y = e64 + F.interpolate(cur, size=e64.shape[-2:], mode="bilinear", align_corners=False)
+    return _affine64(F.conv2d(y, outc.weight.detach().double().cpu(), padding=1), outc).clamp_(min=0)
+
+
+def _stage_torch(x, enc, lat, outc):
+    """pixel_decoder/msdeformattn.py, the FPN loop's statements, unchanged"""
+    cur_fpn = lat(x)
+    y = enc + F.interpolate(cur_fpn, size=enc.shape[-2:], mode="bilinear", align_corners=False)
+    return outc(y)
+
+
+def _case(N, Cin, H, W, norm):
+    """inputs, modules, the float64 reference and the torch result of a (shape, norm): built once, shared by both layouts of enc"""
+    key = (N, Cin, H, W, norm)
+    if key not in _CASES:
+        g = torch.Generator().manual_seed(N * 100003 + Cin * 1009 + H * 31 + W)
+        x = torch.randn(N, Cin, 2 * H, 2 * W, generator=g).cuda()
+        off, tail = 3, 2
+        tokens = torch.randn(N, off + H * W + tail, 128, generator=g).cuda()
+        enc_view = tokens[:, off:off + H * W].transpose(1, 2).reshape(N, 128, H, W)
+        assert enc_view.data_ptr() == tokens.data_ptr() + off * 512                       # a view: no copy
+        lat, outc = _convs(norm, Cin, 7 * H + W)
+        lat, outc = lat.cuda(), outc.cuda()
+        enc = enc_view.contiguous()
+        ref = _stage64(x, enc, lat, outc)
+        with torch.no_grad():
+            want = _stage_torch(x, enc, lat, outc)
+        torch.cuda.synchronize()
+        _CASES[key] = (x, enc, enc_view, tokens.clone(), tokens, lat, outc, ref, float((want.double().cpu() - ref).abs().max()))
+    return _CASES[key]
+
+
+@pytest.mark.parametrize("layout", ["nchw", "tokens"])
+@pytest.mark.parametrize("norm", NORMS, ids=["none", "BN", "FrozenBN"])
+@pytest.mark.parametrize("N,Cin,H,W", SHAPES)
+def test_stage_is_as_close_to_float64_as_the_torch_statements(N, Cin, H, W, norm, layout):
+    from pctrans_amd import fused_ops
+    x, enc_c, enc_view, tokens_before, tokens, lat, outc, ref, e_torch = _case(N, Cin, H, W, norm)
+    enc = enc_c if layout == "nchw" else enc_view
+    if layout == "tokens":
+        assert N * H * W == 1 or not enc.is_contiguous()
+    with torch.no_grad():
+        assert fused_ops.fpn_stage_supported(x, enc, lat, outc)
+        got = fused_ops.fpn_stage(x, enc, lat, outc)
+    torch.cuda.synchronize()
+    assert got.dtype == torch.float32 and got.shape == (N, 128, H, W) and got.is_contiguous()
+    assert torch.equal(tokens, tokens_before)                                              # enc is read, never written
+    e_hip = float((got.double().cpu() - ref).abs().max())
+    fig = {"e_torch": e_torch, "e_hip": e_hip, "max_ref": float(ref.abs().max()),
+           "bound": 2 * e_torch + 2.0 ** -22 * float(ref.abs().max())}
+    _FIGURES["%dx%dx%dx%d_%s_%s" % (N, Cin, H, W, norm or "none", layout)] = fig
+    print(N, Cin, H, W, norm, layout, fig)
+    assert e_hip <= fig["bound"], fig
+    if norm:                                                         # gamma = 0: relu(beta) in every pixel of that channel
+        b = outc.norm.bias[ZERO_GAMMA].clamp(min=0)
+        assert bool((got[:, ZERO_GAMMA] == b).all())
+
+
+def test_borders_are_zero_padded_exactly():
+    """All-ones x, enc = 0, all-ones weights, no norm, zero biases: the lateral map is Cin everywhere (exact), the output is the
+    number of taps inside the image times 128 * Cin -- 4 in the corners, 6 on the edges, 9 inside -- also where tiles meet."""
+    from pctrans_amd import fused_ops
+    lat, outc = _convs("", 16, 1)
+    with torch.no_grad():
+        for c in (lat, outc):
+            c.weight.fill_(1.0)
+            c.bias.zero_()
+    lat, outc = lat.cuda(), outc.cuda()
+    H, W = 9, 65
+    x = torch.ones(2, 16, 2 * H, 2 * W, device="cuda")
+    enc = torch.zeros(2, 128, H, W, device="cuda")
+    with torch.no_grad():
+        got = fused_ops.fpn_stage(x, enc, lat, outc)
+    taps = torch.full((H, W), 9.0)
+    taps[0, :] = taps[-1, :] = 6.0
+    taps[:, 0] = taps[:, -1] = 6.0
+    taps[0, 0] = taps[0, -1] = taps[-1, 0] = taps[-1, -1] = 4.0
+    assert torch.equal(got.cpu(), (taps * 128.0 * 16.0).expand(2, 128, H, W))
+
+
+def test_graph_replay_equals_the_eager_call_bit_for_bit():
+    from pctrans_amd import fused_ops
+    x, enc_c, enc_view, _, _, lat, outc, _, _ = _case(2, 64, 5, 7, "BN")
+    with torch.no_grad():
+        eager = fused_ops.fpn_stage(x, enc_view, lat, outc)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fused_ops.fpn_stage(x, enc_view, lat, outc)              # the capture stream's workspace exists before the capture
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            static = fused_ops.fpn_stage(x, enc_view, lat, outc)
+        static.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+    assert torch.equal(static, eager)
+
+
+# ------------------------------------------------------------------------------------------------------- the module ----
+_CH = {"res2": 16, "res3": 24, "res4": 32, "res5": 40}
+_STRIDE = {"res2": 4, "res3": 8, "res4": 16, "res5": 32}
+
+
+def _pixel_decoder(norm, seed=11):
+    """three encoder levels res3 .. res5 and one FPN level that brings res2 in: the shipped geometry"""
+    from pctrans_amd.layers import ShapeSpec
+    from pctrans_amd.pixel_decoder.msdeformattn import MSDeformAttnPixelDecoder
+    torch.manual_seed(seed)
+    shapes = {k: ShapeSpec(channels=c, stride=_STRIDE[k]) for k, c in _CH.items()}
+    pix = MSDeformAttnPixelDecoder(shapes, transformer_dropout=0.0, transformer_nheads=8, transformer_dim_feedforward=1024,
+                                   transformer_enc_layers=2, conv_dim=128, mask_dim=16, norm=norm,
+                                   transformer_in_features=["res3", "res4", "res5"], common_stride=4)
+    assert pix.num_fpn_levels == 1
+    g = torch.Generator().manual_seed(seed)
+    for c in (pix.lateral_convs[0], pix.output_convs[0]):
+        if isinstance(c.norm, torch.nn.modules.batchnorm._BatchNorm):
+            _fill_norm(c.norm, g)
+    return pix.cuda()
+
+
+def _features(seed=5):
+    g = torch.Generator().manual_seed(seed)
+    sizes = {"res2": (16, 20), "res3": (8, 10), "res4": (4, 5), "res5": (2, 3)}
+    return {k: torch.randn(2, _CH[k], *sizes[k], generator=g).cuda() for k in _CH}
+
+
+def _same(a, b):
+    return a.shape == b.shape and torch.equal(a, b)
+
+
+def test_forward_features_with_the_switch_against_the_torch_loop():
+    """norm = "BN" in eval mode, two encoder layers: mask_features under the rule above (float64 from the finest encoder map,
+    which both runs produce bit for bit), every other output bit-identical, and the launch really happened (its timing label)."""
+    from pctrans_amd import _timing
+    pix = _pixel_decoder("BN").eval()
+    feats = _features()
+    with torch.no_grad():
+        assert pix.fpn == "torch" or os.environ.get("PCT_FPN") == "hip"
+        pix.fpn = "torch"
+        _timing.kernel_timing(True)
+        want = pix.forward_features(feats)
+        assert "fpn_stage" not in [r[0] for r in _timing.kernel_timing(False)]
+        pix.fpn = "hip"
+        _timing.kernel_timing(True)
+        got = pix.forward_features(feats)
+        names = [r[0] for r in _timing.kernel_timing(False)]
+    assert names.count("fpn_stage") == 1
+    assert _same(got[1], want[1]) and len(got[2]) == len(want[2]) == 3 and all(_same(a, b) for a, b in zip(got[2], want[2]))
+    enc = want[2][2]                                                 # the finest encoder map
+    assert not enc.is_contiguous() and enc.stride(1) == 1             # ... is the channels-last view of the token rows
+    ref = _stage64(feats["res2"], enc, pix.lateral_convs[0], pix.output_convs[0])
+    assert got[0].shape == want[0].shape == ref.shape == (2, 128, 8, 10)
+    e_torch, e_hip = float((want[0].double().cpu() - ref).abs().max()), float((got[0].double().cpu() - ref).abs().max())
+    fig = {"e_torch": e_torch, "e_hip": e_hip, "max_ref": float(ref.abs().max()),
+           "bound": 2 * e_torch + 2.0 ** -22 * float(ref.abs().max())}
+    _FIGURES["module_BN_2x16x8x10"] = fig
+    print(fig)
+    assert e_hip <= fig["bound"], fig
+
+
+def test_outside_the_contract_the_switch_changes_nothing(monkeypatch):
+    """GroupNorm, training mode and gradients enabled: fpn = "hip" evaluates the torch statements -- bit-identical results, and
+    fused_ops.fpn_stage is never entered."""
+    from pctrans_amd import fused_ops
+    monkeypatch.setattr(fused_ops, "fpn_stage", lambda *a: (_ for _ in ()).throw(AssertionError("HIP path taken")))
+    # the library's fp32 3x3 convolution is not bit-reproducible from call to call by default (two evaluations of the SAME torch
+    # loop differ in mask_features); with its deterministic algorithms the comparison is exact
+    monkeypatch.setattr(torch.backends.cudnn, "deterministic", True)
+    feats = _features()
+
+    def both(pix_a, pix_b, grad):
+        pix_a.fpn, pix_b.fpn = "torch", "hip"
+        with torch.set_grad_enabled(grad):
+            want, got = pix_a.forward_features(feats), pix_b.forward_features(feats)
+        assert _same(got[0], want[0]) and _same(got[1], want[1]) and all(_same(a, b) for a, b in zip(got[2], want[2]))
+        return got
+
+    gn = _pixel_decoder("GN").eval()
+    with torch.no_grad():
+        gn.forward_features(feats)                                   # (the convolution library settles on its solver in the first call)
+    both(gn, gn, False)
+    bn = _pixel_decoder("BN")
+    a, b = copy.deepcopy(bn).train(), copy.deepcopy(bn).train()      # two copies: each evaluation updates the running buffers
+    both(a, b, False)
+    assert torch.equal(a.output_convs[0].norm.running_mean, b.output_convs[0].norm.running_mean)
+    assert not torch.equal(a.output_convs[0].norm.running_mean, bn.output_convs[0].norm.running_mean)
+    bn.eval()
+    out = both(bn, bn, True)                                         # eval mode, but the parameters require grad
+    assert out[0].requires_grad
