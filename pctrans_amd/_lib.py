@@ -105,6 +105,16 @@ FPN_SYMBOLS = {
                           "tests/test_fpn_stage_gpu.py"),
 }
 
+# Entry points of the differentiable fp32 cross-attention (include/pctrans_hip_attn_train.h; pctrans_amd/attention_train.py, reached
+# with CrossAttentionLayer.attn_train = "hip").  A table of its own, as the FPN level's: name -> (argtypes, restype, the test
+# module that checks the entry against float64)
+ATTN_TRAIN_SYMBOLS = {
+    "pct_cross_attention_forward_f32": ([_vp] * 7 + [_i] * 4 + [ctypes.c_float, _vp, _vp, _vp], _i,
+                                        "tests/test_attention_train_gpu.py"),
+    "pct_cross_attention_backward_f32": ([_vp] * 10 + [_i] * 4 + [ctypes.c_float] + [_vp] * 7, _i,
+                                         "tests/test_attention_train_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -123,7 +133,7 @@ def lib():
     l = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
-            + list(FPN_SYMBOLS.items())]:
+            + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

@@ -140,6 +140,16 @@ int launch_masked_attention(const void *q, const void *k, const void *vT, const 
 int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
                            const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S, float scale,
                            void *out, hipStream_t stream);
+// differentiable fp32 cross-attention (cross_attention_train.hip; include/pctrans_hip_attn_train.h).  PCT_NOT_COVERED: heads
+// outside {4, 8} or a tensor of 2^31 elements or more.  workspace: N * heads * Q floats
+int launch_cross_attention_fwd_f32(const float *q_c, const float *q_s, const float *k_c, const float *k_p, const float *v,
+                                   const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S,
+                                   float scale, float *out, float *lse, hipStream_t stream);
+int launch_cross_attention_bwd_f32(const float *q_c, const float *q_s, const float *k_c, const float *k_p, const float *v,
+                                   const unsigned char *mask, const unsigned char *row_open, const float *out, const float *lse,
+                                   const float *grad_out, int N, int heads, int Q, int S, float scale, float *workspace,
+                                   float *grad_q_c, float *grad_q_s, float *grad_k_c, float *grad_k_p, float *grad_v,
+                                   hipStream_t stream);
 int launch_lsap(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
                 int *status, hipStream_t stream);
 

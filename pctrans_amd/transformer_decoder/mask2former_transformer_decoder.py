@@ -31,6 +31,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
+from .. import attention_train
 from .. import dynamic_mask_head as dmh
 from .. import fused_ops
 from ..layers import CachedLinear, Conv2d, c2_xavier_fill, get_norm
@@ -130,6 +131,9 @@ class CrossAttentionLayer(nn.Module):
         self.nhead = nhead
         self.norm2 = nn.LayerNorm(d_model)
         self.dropout2 = nn.Dropout(dropout)
+        # "hip": when a gradient is required, fp32 operands outside autocast go through the differentiable split-operand kernels
+        # (attention_train.py) instead of the torch chain.  A plain attribute; process default from PCT_ATTN_TRAIN
+        self.attn_train = attention_train.default()
         _xavier_all(self)
 
     def forward_post(self, tgt, memory, memory_mask: Optional[Tensor] = None,
@@ -156,7 +160,16 @@ class CrossAttentionLayer(nn.Module):
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
         # the split-operand kernel takes the projections' outputs as they are: no per-head concatenation, no V^T
         split = fused and fused_ops.cross_attention_supported(q, k, k_pos, h, memory_mask)
-        if memory_row_open is not None and memory_mask is not None and not split:
+        # the differentiable fp32 kernels take the projections' outputs, the mask and memory_row_open as they are, too
+        train = (self.attn_train == "hip" and not fused and memory_key_padding_mask is None and torch.is_grad_enabled()
+                 and k.is_cuda and k.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+                 and (tgt.requires_grad or memory.requires_grad or q.requires_grad or k.requires_grad or k_pos.requires_grad
+                      or self.ca_v_proj.weight.requires_grad or self.ca_qpos_sine_proj.weight.requires_grad
+                      or self.ca_qpos_proj.weight.requires_grad)
+                 and C // h == 16 and self.cross_attn.dropout == 0.0
+                 and (memory_mask is None or (memory_mask.dtype == torch.bool
+                                              and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
+        if memory_row_open is not None and memory_mask is not None and not split and not train:
             memory_mask = memory_mask & ~memory_row_open
             memory_row_open = None
         if fused and not split:
@@ -179,6 +192,9 @@ class CrossAttentionLayer(nn.Module):
         if split and q.dtype == torch.bfloat16 and q_side.dtype == torch.bfloat16 and v.dtype == torch.bfloat16:
             # per head [content (hd) | position (hd)] on both sides (:160-172), formed inside the kernel
             core = fused_ops.cross_attention(q, q_side, k, k_pos, v, h, memory_mask, row_open=memory_row_open)
+            return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
+        if train and attention_train.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
+            core = attention_train.cross_attention_train(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
         if memory_row_open is not None and memory_mask is not None:
             memory_mask = memory_mask & ~memory_row_open

@@ -57,6 +57,10 @@ def build(c):
         for m in model.modules():
             if hasattr(m, "dmh_train"):
                 m.dmh_train = "hip"
+    if c.get("hip_attn_train"):
+        for m in model.modules():
+            if hasattr(m, "attn_train"):
+                m.attn_train = "hip"
     if c.get("hip_point_loss"):
         model.criterion.point_loss = model.criterion.matcher.point_sample = "hip"
     if c.get("hip_point_select"):
@@ -99,6 +103,8 @@ def selected_configs(argv):
         configs.update({k + " + HIP match cost": dict(v, hip_match_cost=True) for k, v in list(configs.items())})
     if "--hip-emb-loss" in argv:            # and every selected config again with the pixel-embedding loss on the device
         configs.update({k + " + HIP embedding loss": dict(v, hip_emb_loss=True) for k, v in list(configs.items())})
+    if "--hip-attn-train" in argv:          # and every selected config again with the cross-attention's HIP training path
+        configs.update({k + " + HIP attention": dict(v, hip_attn_train=True) for k, v in list(configs.items())})
     return configs
 
 
@@ -151,7 +157,7 @@ def main():
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
     flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select",
-                                                "--hip-match-cost", "--hip-emb-loss")]
+                                                "--hip-match-cost", "--hip-emb-loss", "--hip-attn-train")]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
