@@ -20,7 +20,7 @@
 // the a1w1 chain and the five small terms apart, as in the Linear kernels); x and W of step s + 1 are fetched into registers
 // while step s is multiplied, one barrier per step; 54 KB of LDS, two workgroups per CU.
 
-#include "attn_common.hpp"    // lds_read_tr16_b64; split_bf16.hpp
+#include "split_tr_gemm.hpp"    // split_bf16.hpp
 #include "launchers.hpp"
 
 namespace pct {
@@ -46,9 +46,7 @@ __global__ __launch_bounds__(256) void conv1x1_split_weights_kernel(const float 
   split_bf16x3(w[e], w[e + 1], p1, p2, p3);
   const int step = k / C1_KS, kk = k % C1_KS;
   const size_t base = (size_t)step * (C1_WBUF / 2) + (size_t)co * 16 + (size_t)((((kk >> 3) ^ ((co >> 3) & 1)) << 3) + (kk & 7));
-  *reinterpret_cast<unsigned *>(ws + base) = p1;
-  *reinterpret_cast<unsigned *>(ws + base + C1_WPLANE / 2) = p2;
-  *reinterpret_cast<unsigned *>(ws + base + C1_WPLANE) = p3;
+  store_planes(ws + base, C1_WPLANE / 2, p1, p2, p3);
 }
 
 // TOKENS: the output goes to the encoder's token rows instead -- y[n][row_offset + p][co], channels fastest, which is what a lane
@@ -76,33 +74,22 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
   const float *xn = x + (size_t)n * K * HW + p0;
   const int nsteps = K / C1_KS;
 
-  // staging roles: x -- row tid / 16 of the step, 8 pixels from (tid % 16) * 8; W -- 48 consecutive bytes of the step's image
+  // staging roles: x -- row tid / 16 of the step, 8 pixels from (tid % 16) * 8; W -- chunk tid of each plane, the image as it is
   const int sx_row = tid >> 4, sx_px = (tid & 15) * 8;
   const float *xsrc = xn + (size_t)sx_row * HW + sx_px;
   const int sx_off = sx_row * C1_XROW + sx_px * 2;
   f32x4 gx[2];
-  i32x4 gw[3];
+  WeightStepStream<C1_WPLANE, C1_WBUF / 2, C1_BLOCK> wst;
+  wst.loff = tid * 16;
   auto fetch = [&](const int step) {
     const float *p = xsrc + (size_t)step * C1_KS * HW;
     gx[0] = *reinterpret_cast<const f32x4 *>(p);
     gx[1] = *reinterpret_cast<const f32x4 *>(p + 4);
-    const i32x4 *wp = reinterpret_cast<const i32x4 *>(ws + (size_t)step * (C1_WBUF / 2)) + tid;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gw[i] = wp[i * C1_BLOCK];
+    wst.fetch(ws, step, tid);
   };
   auto stash = [&](const int buf) {
-    unsigned a[4], b[4], c[4];
-    split_bf16x3(gx[0][0], gx[0][1], a[0], b[0], c[0]);
-    split_bf16x3(gx[0][2], gx[0][3], a[1], b[1], c[1]);
-    split_bf16x3(gx[1][0], gx[1][1], a[2], b[2], c[2]);
-    split_bf16x3(gx[1][2], gx[1][3], a[3], b[3], c[3]);
-    unsigned char *d = xs[buf] + sx_off;
-    *reinterpret_cast<i32x4 *>(d) = i32x4{(int)a[0], (int)a[1], (int)a[2], (int)a[3]};
-    *reinterpret_cast<i32x4 *>(d + C1_XPLANE) = i32x4{(int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-    *reinterpret_cast<i32x4 *>(d + 2 * C1_XPLANE) = i32x4{(int)c[0], (int)c[1], (int)c[2], (int)c[3]};
-    i32x4 *wd = reinterpret_cast<i32x4 *>(wsm[buf]) + tid;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) wd[i * C1_BLOCK] = gw[i];
+    split_bf16x3_8_store(gx[0], gx[1], xs[buf] + sx_off, C1_XPLANE);
+    wst.stash(wsm[buf]);
   };
 
   // fragment addresses (fixed): wave = (channel half, pixel half)
@@ -114,50 +101,7 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
     const int co = co_half * 64 + rb * 32 + r;
     a_off[rb] = co * 32 + ((h ^ ((co >> 3) & 1)) << 4);
   }
-  // B operand through the transposing read: 16-lane group g16 = lane / 16 covers pixels 16 (g16 % 2) .. + 15 and k = 8 (g16 / 2) ..;
-  // lane 4 q + pp of the group supplies row q (+ 4 for the second read), columns 4 pp .. 4 pp + 3
-  const int g16 = lane >> 4, q4 = (lane & 15) >> 2, pp = lane & 3;
-  int b_off[2];
-#pragma unroll
-  for (int cb = 0; cb < 2; ++cb)
-    b_off[cb] = (8 * (g16 >> 1) + q4) * C1_XROW + (px_half * 64 + cb * 32 + 16 * (g16 & 1) + 4 * pp) * 2;
-
-  f32x16 acc_hi[2][2], acc_lo[2][2];
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc_hi[rb][cb][j] = acc_lo[rb][cb][j] = 0.f;
-
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  for (int step = 0; step < nsteps; ++step) {
-    const int buf = step & 1;
-    if (step + 1 < nsteps) fetch(step + 1);
-    __builtin_amdgcn_sched_barrier(0);                            // the fetches ahead of the MFMAs
-    bf16x8 wa[2][3], xb[2][3];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb)
-        wa[rb][pl] = *reinterpret_cast<const bf16x8 *>(wsm[buf] + pl * C1_WPLANE + a_off[rb]);
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const unsigned char *p = xs[buf] + pl * C1_XPLANE + b_off[cb];
-        const bf16x4 lo = lds_read_tr16_b64(p), hi = lds_read_tr16_b64(p + 4 * C1_XROW);
-        xb[cb][pl] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-    }
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-        split_mfma6(wa[rb][0], wa[rb][1], wa[rb][2], xb[cb][0], xb[cb][1], xb[cb][2], acc_hi[rb][cb], acc_lo[rb][cb]);
-    if (step + 1 < nsteps) stash(buf ^ 1);                       // (everyone left that buffer before the previous barrier)
-    __syncthreads();
-  }
+  const SplitTile2x2 acc = split_tr_gemm<C1_XROW, C1_WPLANE>(xs[0], wsm[0], a_off, lane, px_half * 64, nsteps, fetch, stash);
 
   // epilogue: acc[4 q + t] = y[co = block + 8 q + 4 h + t][pixel = block + r]
   if constexpr (TOKENS) {
@@ -175,7 +119,7 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) v[cb][t] = (acc_hi[rb][cb][4 * q + t] + acc_lo[rb][cb][4 * q + t]) + bq[t];
+          for (int t = 0; t < 4; ++t) v[cb][t] = acc.sum(rb, cb, 4 * q + t) + bq[t];
           sm += (v[cb][0] + v[cb][1]) + (v[cb][2] + v[cb][3]);
           *reinterpret_cast<f32x4 *>(yn + (size_t)(px_half * 64 + cb * 32 + r) * C1_CO + co0 + 8 * q) = v[cb];
         }
@@ -217,7 +161,7 @@ __global__ __launch_bounds__(C1_BLOCK, 2) void conv1x1_nchw_split_kernel(const f
       for (int q = 0; q < 4; ++q)
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-          dst[(size_t)(co0 + 8 * q + t) * HW] = (acc_hi[rb][cb][4 * q + t] + acc_lo[rb][cb][4 * q + t]) + bq[q][t];
+          dst[(size_t)(co0 + 8 * q + t) * HW] = acc.sum(rb, cb, 4 * q + t) + bq[q][t];
     }
   }
 }

@@ -46,18 +46,6 @@ constexpr int FF_HALF = FF_PIECES / 2;                  // 7
 constexpr int FF_LDS = 2 * FF_STAGE + 3 * FF_D * 4;     // two stages, then b2, gamma, beta
 constexpr int FF_B1OFF = 56832;                         // the chunk's 32 biases, in the padding
 
-// eight consecutive floats -> three bf16x8 pieces
-__device__ __forceinline__ void ff_split8(const f32x4 a, const f32x4 b, bf16x8 (&out)[3])
-{
-  unsigned p[3][4];
-  split_bf16x3(a[0], a[1], p[0][0], p[1][0], p[2][0]);
-  split_bf16x3(a[2], a[3], p[0][1], p[1][1], p[2][1]);
-  split_bf16x3(b[0], b[1], p[0][2], p[1][2], p[2][2]);
-  split_bf16x3(b[2], b[3], p[0][3], p[1][3], p[2][3]);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) out[q] = __builtin_bit_cast(bf16x8, i32x4{(int)p[q][0], (int)p[q][1], (int)p[q][2], (int)p[q][3]});
-}
-
 // W1 [F][128], W2 [128][F], b1 [F] fp32 -> img [F / 32][FF_STAGE bytes]: image c holds W2 and b1 of chunk c and W1 of chunk c + 1
 // (mod F / 32): what one iteration of the kernel's chunk loop reads (see the header); one thread per element pair
 __global__ __launch_bounds__(256) void ffn_split_weights_kernel(const float *__restrict__ w1, const float *__restrict__ w2,
@@ -73,9 +61,7 @@ __global__ __launch_bounds__(256) void ffn_split_weights_kernel(const float *__r
     split_bf16x3(w1[e], w1[e + 1], p1, p2, p3);
     const int c = (u / FF_CH + nch - 1) % nch;
     unsigned short *d = img + (size_t)c * (FF_STAGE / 2) + (size_t)(u % FF_CH) * (FF_W1ROW / 2) + k;
-    *reinterpret_cast<unsigned *>(d) = p1;
-    *reinterpret_cast<unsigned *>(d + FF_W1PLANE / 2) = p2;
-    *reinterpret_cast<unsigned *>(d + FF_W1PLANE) = p3;
+    store_planes(d, FF_W1PLANE / 2, p1, p2, p3);
   } else if (e < 2 * n1) {                                        // W2[c][u], u even: chunk u / 32, row c, slot of u in the chunk
     const long long e2 = e - n1;
     const int c = (int)(e2 / F), u = (int)(e2 - (long long)c * F);
@@ -87,9 +73,7 @@ __global__ __launch_bounds__(256) void ffn_split_weights_kernel(const float *__r
     const int g = v >> 3, h = (v >> 2) & 1, t = v & 3;
     unsigned short *d = img + (size_t)(u / FF_CH) * (FF_STAGE / 2) + (size_t)(FF_W2OFF / 2) + (size_t)c * (FF_W2ROW / 2) +
                         (2 * s + h) * 8 + 4 * g + t;
-    *reinterpret_cast<unsigned *>(d) = p1;                        // (t even: t and t + 1 are adjacent slots)
-    *reinterpret_cast<unsigned *>(d + FF_W2PLANE / 2) = p2;
-    *reinterpret_cast<unsigned *>(d + FF_W2PLANE) = p3;
+    store_planes(d, FF_W2PLANE / 2, p1, p2, p3);                  // (t even: t and t + 1 are adjacent slots)
   } else if (e < 2 * n1 + F) {                                    // b1[u], u even
     const int u = (int)(e - 2 * n1);
     float *d = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(img) + (size_t)(u / FF_CH) * FF_STAGE + FF_B1OFF) + u % FF_CH;
@@ -175,7 +159,7 @@ __global__ __launch_bounds__(FF_BLOCK, 1) void ffn_fused_split_kernel(
   f32x16 h_hi, h_lo;
   bf16x8 wa[2][3];
   auto split_x = [&](const int s) {
-    ff_split8(__builtin_bit_cast(f32x4, xraw[2 * s]), __builtin_bit_cast(f32x4, xraw[2 * s + 1]), xp[s]);
+    split_bf16x3_8(__builtin_bit_cast(f32x4, xraw[2 * s]), __builtin_bit_cast(f32x4, xraw[2 * s + 1]), xp[s]);
   };
   auto w1_frags = [&](const unsigned char *st, const int s) {
 #pragma unroll

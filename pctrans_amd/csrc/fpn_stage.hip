@@ -16,7 +16,8 @@
 // 16 input channels a thread loads 2 rows of 4 floats for 4 (channel, pixel pair) items as they lie in memory (8-byte loads, 16
 // lanes = 256 contiguous bytes; a pair that hangs over the right edge loads its left half, pixels outside nothing), means them, splits
 // the pair and writes three 4-byte words into the [16 k][128 pixels] planes that conv1x1_split.hip's transposing read
-// (ds_read_b64_tr_b16) turns into B fragments.  Waves = 2 x 2 blocks of 64 channels x 64 pixels, as there.  Epilogue: affine, + enc
+// (ds_read_b64_tr_b16) turns into B fragments.  Waves = 2 x 2 blocks of 64 channels x 64 pixels, the step loop is the same one
+// (split_tr_gemm.hpp).  Epilogue: affine, + enc
 // read where it lies (channels-last token rows: one 16-byte load per 4 channels; NCHW: 4 loads along the pixels), y written as
 // [N][8 slabs][H W][16 channels] fp32: what the second kernel stages as contiguous 64-byte pixels.
 //
@@ -32,7 +33,7 @@
 //
 // The weight images are re-split on every call by fpn_weight_images_kernel into the caller's workspace.
 
-#include "attn_common.hpp"    // lds_read_tr16_b64; split_bf16.hpp
+#include "split_tr_gemm.hpp"    // split_bf16.hpp
 #include "launchers.hpp"
 
 namespace pct {
@@ -78,9 +79,7 @@ __global__ __launch_bounds__(256) void fpn_weight_images_kernel(const float *__r
     split_bf16x3(p[0], p[9], p1, p2, p3);
     dst = img3 + (size_t)((ci / FP_KS) * 9 + tap) * FP_WSTEP + co * FP_KS + (ci % FP_KS);
   }
-  *reinterpret_cast<unsigned *>(dst) = p1;
-  *reinterpret_cast<unsigned *>(dst + FP_C * FP_KS) = p2;
-  *reinterpret_cast<unsigned *>(dst + 2 * FP_C * FP_KS) = p3;
+  store_planes(dst, FP_C * FP_KS, p1, p2, p3);
 }
 
 // out = fmaf(s, acc, t): s = gamma / sqrt(var + eps), t = s * (bias - mean) + beta; without statistics s = 1, t = bias
@@ -93,22 +92,9 @@ __device__ __forceinline__ f32x2 fpn_affine(const int c, const float *bias, cons
   return f32x2{s, fmaf(s, b - mean[c], beta[c])};
 }
 
-// a step's weight image: 768 chunks of 16 bytes, chunk (plane i, row tid / 2, half tid % 2) for i = 0 .. 2
-struct FpnWeightStream {
-  i32x4 g[3];
-  int loff;
+// a step's weight image in padded rows: chunk (plane i, row tid / 2, half tid % 2) for i = 0 .. 2
+struct FpnWeightStream : WeightStepStream<FP_WPLANE, FP_WSTEP, FP_BLOCK> {
   __device__ __forceinline__ void init(const int tid) { loff = (tid >> 1) * FP_WROW + (tid & 1) * 16; }
-  __device__ __forceinline__ void fetch(const unsigned short *img, const int step, const int tid)
-  {
-    const i32x4 *p = reinterpret_cast<const i32x4 *>(img + (size_t)step * FP_WSTEP) + tid;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) g[i] = p[i * FP_BLOCK];
-  }
-  __device__ __forceinline__ void stash(unsigned char *buf) const
-  {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) *reinterpret_cast<i32x4 *>(buf + i * FP_WPLANE + loff) = g[i];
-  }
 };
 
 template <bool ENC_NHWC>
@@ -178,49 +164,7 @@ __global__ __launch_bounds__(FP_BLOCK, 2) void fpn_lateral_kernel(
   int a_off[2];
 #pragma unroll
   for (int rb = 0; rb < 2; ++rb) a_off[rb] = (co_half * 64 + rb * 32 + r) * FP_WROW + h * 16;
-  // B operand through the transposing read (conv1x1_split.hip): 16-lane group g16 covers pixels 16 (g16 % 2) .. + 15 and
-  // k = 8 (g16 / 2) ..; lane 4 q + pp of the group supplies row q (+ 4 for the second read), columns 4 pp .. 4 pp + 3
-  const int g16 = lane >> 4, q4 = (lane & 15) >> 2, pp = lane & 3;
-  int b_off[2];
-#pragma unroll
-  for (int cb = 0; cb < 2; ++cb)
-    b_off[cb] = (8 * (g16 >> 1) + q4) * FL_XROW + (px_half * 64 + cb * 32 + 16 * (g16 & 1) + 4 * pp) * 2;
-
-  f32x16 acc_hi[2][2], acc_lo[2][2];
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc_hi[rb][cb][j] = acc_lo[rb][cb][j] = 0.f;
-
-  fetch(0);
-  stash(0);
-  __syncthreads();
-  for (int step = 0; step < nsteps; ++step) {
-    const int buf = step & 1;
-    if (step + 1 < nsteps) fetch(step + 1);
-    __builtin_amdgcn_sched_barrier(0);                            // the fetches ahead of the MFMAs
-    bf16x8 wa[2][3], xb[2][3];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb) wa[rb][pl] = *reinterpret_cast<const bf16x8 *>(wsm[buf] + pl * FP_WPLANE + a_off[rb]);
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const unsigned char *p = xs[buf] + pl * FL_XPLANE + b_off[cb];
-        const bf16x4 lo = lds_read_tr16_b64(p), hi = lds_read_tr16_b64(p + 4 * FL_XROW);
-        xb[cb][pl] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-    }
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-        split_mfma6(wa[rb][0], wa[rb][1], wa[rb][2], xb[cb][0], xb[cb][1], xb[cb][2], acc_hi[rb][cb], acc_lo[rb][cb]);
-    if (step + 1 < nsteps) stash(buf ^ 1);                       // (everyone left that buffer before the previous barrier)
-    __syncthreads();
-  }
+  const SplitTile2x2 acc = split_tr_gemm<FL_XROW, FP_WPLANE>(xs[0], wsm[0], a_off, lane, px_half * 64, nsteps, fetch, stash);
 
   // epilogue: acc[4 q + t] = lat[co = block + 8 q + 4 h + t][row 2 px_half + cb][column r]; y [n][co / 16][pixel][co % 16]
   const int gx = x0 + r;
@@ -247,7 +191,7 @@ __global__ __launch_bounds__(FP_BLOCK, 2) void fpn_lateral_kernel(
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const f32x2 c = aff[co0 + t];
-          v[t] = fmaf(c[0], acc_hi[rb][cb][4 * q + t] + acc_lo[rb][cb][4 * q + t], c[1]) + e[t];
+          v[t] = fmaf(c[0], acc.sum(rb, cb, 4 * q + t), c[1]) + e[t];
         }
         *reinterpret_cast<f32x4 *>(yn + ((size_t)(co0 >> 4) * HWp + pix) * FP_KS + (co0 & 15)) = v;
       }
@@ -301,15 +245,7 @@ __global__ __launch_bounds__(FP_BLOCK, 2) void fpn_output_kernel(
 #pragma unroll
     for (int rd = 0; rd < FO_ROUNDS; ++rd) {
       if (loff[rd] < 0) continue;
-      unsigned a[4], b[4], c[4];
-      split_bf16x3(gin[rd][0][0], gin[rd][0][1], a[0], b[0], c[0]);
-      split_bf16x3(gin[rd][0][2], gin[rd][0][3], a[1], b[1], c[1]);
-      split_bf16x3(gin[rd][1][0], gin[rd][1][1], a[2], b[2], c[2]);
-      split_bf16x3(gin[rd][1][2], gin[rd][1][3], a[3], b[3], c[3]);
-      unsigned char *d = xs + loff[rd];
-      *reinterpret_cast<i32x4 *>(d) = i32x4{(int)a[0], (int)a[1], (int)a[2], (int)a[3]};
-      *reinterpret_cast<i32x4 *>(d + FO_XPLANE) = i32x4{(int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-      *reinterpret_cast<i32x4 *>(d + 2 * FO_XPLANE) = i32x4{(int)c[0], (int)c[1], (int)c[2], (int)c[3]};
+      split_bf16x3_8_store(gin[rd][0], gin[rd][1], xs + loff[rd], FO_XPLANE);
     }
   };
 
@@ -319,13 +255,8 @@ __global__ __launch_bounds__(FP_BLOCK, 2) void fpn_output_kernel(
   const int a_off = (co_half * 64 + r) * FP_WROW + h * 16;
   const int b_off = (2 * rp * FO_HW + r) * FP_WROW + h * 16;
 
-  f32x16 acc_hi[2][2], acc_lo[2][2];
-#pragma unroll
-  for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc_hi[rb][cb][j] = acc_lo[rb][cb][j] = 0.f;
+  SplitTile2x2 acc;
+  acc.zero();
 
   wst.fetch(img3, 0, tid);
 #pragma unroll
@@ -353,11 +284,7 @@ __global__ __launch_bounds__(FP_BLOCK, 2) void fpn_output_kernel(
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) wa[rb][pl] = *reinterpret_cast<const bf16x8 *>(ap + pl * FP_WPLANE + rb * 32 * FP_WROW);
       }
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-          split_mfma6(wa[rb][0], wa[rb][1], wa[rb][2], xb[cb][0], xb[cb][1], xb[cb][2], acc_hi[rb][cb], acc_lo[rb][cb]);
+      acc.mac(wa, xb);
       if (tap == 8 && more_x) {
         __syncthreads();                                           // every wave has left the input block
         stash_x();
@@ -383,7 +310,7 @@ __global__ __launch_bounds__(FP_BLOCK, 2) void fpn_output_kernel(
         for (int t = 0; t < 4; ++t) {
           const int co = co_half * 64 + rb * 32 + 8 * q + 4 * h + t;
           const f32x2 c = aff[co];
-          on[(size_t)co * HWp + pix] = fmaxf(fmaf(c[0], acc_hi[rb][cb][4 * q + t] + acc_lo[rb][cb][4 * q + t], c[1]), 0.f);
+          on[(size_t)co * HWp + pix] = fmaxf(fmaf(c[0], acc.sum(rb, cb, 4 * q + t), c[1]), 0.f);
         }
   }
 }

@@ -37,9 +37,7 @@ __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float *__restri
   if (i >= count) return;
   unsigned p1, p2, p3;
   split_bf16x3(w[i], w[i + 1], p1, p2, p3);
-  *reinterpret_cast<unsigned *>(out + i) = p1;
-  *reinterpret_cast<unsigned *>(out + count + i) = p2;
-  *reinterpret_cast<unsigned *>(out + 2 * count + i) = p3;
+  store_planes(out + i, count, p1, p2, p3);
 }
 
 __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
@@ -99,20 +97,9 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
       gw[i] = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wg_voff, ((i >> 1) * LLS_N + (i & 1) * 64) * K * 2 + step * (LLS_BK * 2), 0);
   };
   auto stash = [&]() {
-    unsigned p1[8], p2[8], p3[8];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x4 v = __builtin_bit_cast(f32x4, gx[q]);
-      split_bf16x3(v[0], v[1], p1[2 * q], p2[2 * q], p3[2 * q]);
-      split_bf16x3(v[2], v[3], p1[2 * q + 1], p2[2 * q + 1], p3[2 * q + 1]);
-    }
-    unsigned char *p = xs + xs_off;
-    *reinterpret_cast<i32x4 *>(p) = i32x4{(int)p1[0], (int)p1[1], (int)p1[2], (int)p1[3]};
-    *reinterpret_cast<i32x4 *>(p + 16) = i32x4{(int)p1[4], (int)p1[5], (int)p1[6], (int)p1[7]};
-    *reinterpret_cast<i32x4 *>(p + LLS_PLANE) = i32x4{(int)p2[0], (int)p2[1], (int)p2[2], (int)p2[3]};
-    *reinterpret_cast<i32x4 *>(p + LLS_PLANE + 16) = i32x4{(int)p2[4], (int)p2[5], (int)p2[6], (int)p2[7]};
-    *reinterpret_cast<i32x4 *>(p + 2 * LLS_PLANE) = i32x4{(int)p3[0], (int)p3[1], (int)p3[2], (int)p3[3]};
-    *reinterpret_cast<i32x4 *>(p + 2 * LLS_PLANE + 16) = i32x4{(int)p3[4], (int)p3[5], (int)p3[6], (int)p3[7]};
+    for (int q = 0; q < 2; ++q)
+      split_bf16x3_8_store(__builtin_bit_cast(f32x4, gx[2 * q]), __builtin_bit_cast(f32x4, gx[2 * q + 1]), xs + xs_off + 16 * q, LLS_PLANE);
 #pragma unroll
     for (int i = 0; i < 6; ++i)
       *reinterpret_cast<i32x4 *>(ws + ws_off + (i >> 1) * LLS_PLANE + (i & 1) * 64 * LLS_ROWB) = gw[i];
@@ -125,13 +112,8 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
   long long tile = blockIdx.x;
   fetch(tile, 0);
   for (; tile < ntiles; tile += gridDim.x) {
-    f32x16 acc_hi[2][2], acc_lo[2][2];                        // [row block][column block]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc_hi[a][b][j] = acc_lo[a][b][j] = 0.f;
+    SplitTile2x2 acc;
+    acc.zero();
 
     for (int step = 0; step < ksteps; ++step) {
       __syncthreads();                                            // everyone is done reading the previous stage
@@ -151,11 +133,7 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
             a[b][p] = *reinterpret_cast<const bf16x8 *>(xs + xr_off + b * 32 * LLS_ROWB + p * LLS_PLANE + 32 * ks);
             w[b][p] = *reinterpret_cast<const bf16x8 *>(ws + wr_off + b * 32 * LLS_ROWB + p * LLS_PLANE + 32 * ks);
           }
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-            split_mfma6(w[cb][0], w[cb][1], w[cb][2], a[rb][0], a[rb][1], a[rb][2], acc_hi[rb][cb], acc_lo[rb][cb]);
+        acc.mac<true>(w, a);                                      // W is the A operand: the transposed tile (see the header)
       }
     }
 
@@ -176,7 +154,7 @@ __global__ __launch_bounds__(LLS_BLOCK, 2) void linear_ln_split_kernel(
           const f32x4 bq = *reinterpret_cast<const f32x4 *>(&gbuf[0][c0]);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            v[16 * cb + 4 * q + i] = ((acc_hi[rb][cb][4 * q + i] + acc_lo[rb][cb][4 * q + i]) + bq[i]) + res[i];
+            v[16 * cb + 4 * q + i] = (acc.sum(rb, cb, 4 * q + i) + bq[i]) + res[i];
         }
       // two-pass LayerNorm over the row's 128 columns: my 32, the other half of the wave, the other column half
       float t = 0.f;

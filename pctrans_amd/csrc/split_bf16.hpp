@@ -2,8 +2,9 @@
 // conv1x1_split.hip), stated once.  Every fp32 number is EXACTLY the sum of three bf16 numbers
 //     a = a1 + a2 + a3,   a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)
 // and a product a.w is evaluated from its six leading partial products on the bf16 matrix cores with fp32 accumulation
-// (linear_k128_split.hip has the error analysis).  Tiling, staging and epilogues stay with the kernels; what they share is
-// the split, the order of the six products and the vector types -- the GEMMs agree bit for bit only while these agree.
+// (linear_k128_split.hip has the error analysis).  Staging layouts and epilogues stay with the kernels; what they share is
+// the split, the order of the six products, the vector types and the wave's 2 x 2 accumulator tile -- the GEMMs agree bit for
+// bit only while these agree.  (split_tr_gemm.hpp: the weight-step stream and the step loop of the transposed-B kernels.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,36 @@ __device__ __forceinline__ void split_bf16x3(const float x, const float y, unsig
   p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{sx, sy}, bf16x2));
 }
 
+// the three pieces of a pair, one per plane: d, d + plane, d + 2 plane (in bf16 elements)
+__device__ __forceinline__ void store_planes(unsigned short *d, const long long plane, const unsigned p1, const unsigned p2,
+                                             const unsigned p3)
+{
+  *reinterpret_cast<unsigned *>(d) = p1;
+  *reinterpret_cast<unsigned *>(d + plane) = p2;
+  *reinterpret_cast<unsigned *>(d + 2 * plane) = p3;
+}
+
+// eight consecutive floats -> three bf16x8 pieces
+__device__ __forceinline__ void split_bf16x3_8(const f32x4 a, const f32x4 b, bf16x8 (&out)[3])
+{
+  unsigned p[3][4];
+  split_bf16x3(a[0], a[1], p[0][0], p[1][0], p[2][0]);
+  split_bf16x3(a[2], a[3], p[0][1], p[1][1], p[2][1]);
+  split_bf16x3(b[0], b[1], p[0][2], p[1][2], p[2][2]);
+  split_bf16x3(b[2], b[3], p[0][3], p[1][3], p[2][3]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) out[q] = __builtin_bit_cast(bf16x8, i32x4{(int)p[q][0], (int)p[q][1], (int)p[q][2], (int)p[q][3]});
+}
+
+// ... and staged: piece q as one 16-byte store at d + q * plane (bytes)
+__device__ __forceinline__ void split_bf16x3_8_store(const f32x4 a, const f32x4 b, unsigned char *d, const int plane)
+{
+  bf16x8 p[3];
+  split_bf16x3_8(a, b, p);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8 *>(d + q * plane) = p[q];
+}
+
 // One k-step of the product of w = w1 + w2 + w3 (A operand) and a = a1 + a2 + a3 (B operand): the six leading terms
 //     w1a1 | w1a2 + w2a1 | w2a2 + w1a3 + w3a1          (relative size 1 | 2^-9 | 2^-18)
 // Two accumulators: the w1a1 chain alone in `hi`, the five small terms in `lo`, so that the small terms are rounded at their
@@ -46,6 +77,35 @@ __device__ __forceinline__ void split_mfma6(const bf16x8 w1, const bf16x8 w2, co
   lo = mfma_bf16(w1, a2, lo);
   lo = mfma_bf16(w2, a1, lo);
 }
+
+// A wave's tile of the 128-wide GEMMs: 2 x 2 blocks of 32 x 32 outputs, each a hi / lo accumulator pair (128 VGPRs).
+struct SplitTile2x2 {
+  f32x16 hi[2][2], lo[2][2];                                        // [row block][column block]
+  __device__ __forceinline__ void zero()
+  {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) hi[rb][cb][j] = lo[rb][cb][j] = 0.f;
+  }
+  // one k-step, rows outer.  The A operand's three pieces w[.] belong to the row blocks; with W_BY_COLUMN to the column
+  // blocks (linear_ln_split.hip computes the transposed tile) and b[.] to the row blocks
+  template <bool W_BY_COLUMN = false>
+  __device__ __forceinline__ void mac(const bf16x8 (&w)[2][3], const bf16x8 (&b)[2][3])
+  {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        const bf16x8(&wp)[3] = w[W_BY_COLUMN ? cb : rb], (&bp)[3] = b[W_BY_COLUMN ? rb : cb];
+        split_mfma6(wp[0], wp[1], wp[2], bp[0], bp[1], bp[2], hi[rb][cb], lo[rb][cb]);
+      }
+  }
+  // element j of block (rb, cb): the one addition of hi and lo
+  __device__ __forceinline__ float sum(const int rb, const int cb, const int j) const { return hi[rb][cb][j] + lo[rb][cb][j]; }
+};
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v)

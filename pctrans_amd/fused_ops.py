@@ -207,8 +207,18 @@ def linear_add_layer_norm(x, linear, residual, norm):
     return out.view(residual.shape)
 
 
-_SPLIT_WS = {}                # (device, stream, K) -> workspace the kernel refills with the split weights on every call:
-                              # one per stream, so launches on two streams never share it
+_WORKSPACES = {}              # (device, stream, kernel, shape) -> workspace the kernel refills with the split weights / weight
+                              # images on every call: one per stream, so launches on two streams never share it
+
+
+def _workspace(x, kernel, shape, dtype):
+    """-> (`kernel`'s workspace on x's device and current stream, allocated on first use; the stream's handle)."""
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    key = (x.device, stream, kernel, shape)
+    ws = _WORKSPACES.get(key)
+    if ws is None:
+        ws = _WORKSPACES[key] = torch.empty(shape, dtype=dtype, device=x.device)
+    return ws, stream
 
 
 def linear_layer_norm_supported(x, linear, residual, norm):
@@ -235,11 +245,7 @@ def linear_layer_norm(x, linear, residual, norm):
         (linear.bias is None or linear.bias.data_ptr() % 16 == 0) and x2.stride(0) % 4 == 0 and r2.stride(0) % 4 == 0
     if not aligned:
         return add_layer_norm(residual, linear(x), norm)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device, stream, k)
-    ws = _SPLIT_WS.get(key)
-    if ws is None:
-        ws = _SPLIT_WS[key] = torch.empty((3, 128, k), dtype=torch.bfloat16, device=x.device)
+    ws, stream = _workspace(x, "linear_ln", (3, 128, k), torch.bfloat16)
     out = torch.empty((rows, 128), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device), _timing.timed("linear_ln k=%d" % k, x2):
         rc = _lib.lib().pct_linear_add_layernorm_f32(
@@ -248,9 +254,6 @@ def linear_layer_norm(x, linear, residual, norm):
             norm.weight.data_ptr(), norm.bias.data_ptr(), float(norm.eps), rows, out.data_ptr(), 128, stream)
     _lib.check(rc, "linear_layer_norm")
     return out.view(residual.shape)
-
-
-_FFN_WS = {}                  # (device, stream, hidden) -> weight-image workspace of ffn_layer_norm (refilled per call)
 
 
 def ffn_layer_norm_supported(x, linear1, linear2, norm):
@@ -275,11 +278,7 @@ def ffn_layer_norm(x, linear1, linear2, norm):
     if not (all(t.data_ptr() % 16 == 0 for t in ptrs) and x2.stride(0) % 4 == 0):
         return linear_layer_norm(linear(x, linear1, relu=True), linear2, x, norm)
     _lib.prepare_device(x.device)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device, stream, f)
-    ws = _FFN_WS.get(key)
-    if ws is None:
-        ws = _FFN_WS[key] = torch.empty(((f // 32) * 57344,), dtype=torch.uint8, device=x.device)
+    ws, stream = _workspace(x, "ffn", ((f // 32) * 57344,), torch.uint8)
     out = torch.empty((rows, 128), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device), _timing.timed("ffn f=%d" % f, x2):
         rc = _lib.lib().pct_ffn_layernorm_f32(
@@ -288,9 +287,6 @@ def ffn_layer_norm(x, linear1, linear2, norm):
             float(norm.eps), f, rows, ws.data_ptr(), out.data_ptr(), 128, stream)
     _lib.check(rc, "ffn_layer_norm")
     return out.view(x.shape)
-
-
-_CONV_WS = {}                 # (device, stream, in_channels) -> split-weight workspace of conv1x1_nchw (refilled per call)
 
 
 def conv1x1_nchw_supported(x, conv):
@@ -314,11 +310,7 @@ def conv1x1_nchw(x, conv):
     if not conv1x1_nchw_supported(x, conv):
         return conv(x)
     n, k, h, w_ = x.shape
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device, stream, k)
-    ws = _CONV_WS.get(key)
-    if ws is None:
-        ws = _CONV_WS[key] = torch.empty((3, 128, k), dtype=torch.bfloat16, device=x.device)
+    ws, stream = _workspace(x, "conv1x1", (3, 128, k), torch.bfloat16)
     out = torch.empty((n, 128, h, w_), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device), _timing.timed("conv1x1 k=%d" % k, x):
         rc = _lib.lib().pct_conv1x1_nchw_f32(
@@ -341,11 +333,7 @@ def conv1x1_groupnorm_tokens_into(x, conv, gn, out, row_offset):
     the pixel decoder's input projection of one level in one entry (csrc/conv1x1_split.hip)."""
     n, k, h, w_ = x.shape
     hw = h * w_
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device, stream, k)
-    ws = _CONV_WS.get(key)
-    if ws is None:
-        ws = _CONV_WS[key] = torch.empty((3, 128, k), dtype=torch.bfloat16, device=x.device)
+    ws, stream = _workspace(x, "conv1x1", (3, 128, k), torch.bfloat16)
     partial = torch.empty((n * (hw // 128) * 2 * 64,), dtype=torch.float32, device=x.device)
     stats = torch.empty((n * 64,), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device), _timing.timed("conv1x1_gn k=%d" % k, x):
@@ -354,9 +342,6 @@ def conv1x1_groupnorm_tokens_into(x, conv, gn, out, row_offset):
             gn.weight.data_ptr(), gn.bias.data_ptr(), 32, float(gn.eps), n, k, 128, hw, partial.data_ptr(), stats.data_ptr(),
             out.data_ptr(), out.stride(0), row_offset * 128, stream)
     _lib.check(rc, "conv1x1_groupnorm_tokens")
-
-
-_SEG_WS = {}                  # (device, stream) -> weight-image workspace of the semantic head's two 3x3 convolutions
 
 
 def _seg_block_supported(x, block):
@@ -394,11 +379,8 @@ def _seg_input_supported(x):
 
 
 def _seg_ws(x):
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    ws = _SEG_WS.get((x.device, stream))
-    if ws is None:
-        ws = _SEG_WS[(x.device, stream)] = torch.empty((2, 128 * 128 * 9), dtype=torch.bfloat16, device=x.device)
-    return ws, stream
+    """The weight images of the semantic head's two 3x3 convolutions."""
+    return _workspace(x, "seg_head", (2, 128 * 128 * 9), torch.bfloat16)
 
 
 def _bn_args(bn):
@@ -457,9 +439,6 @@ def seg_head_forward(x, seg_head, logits):
             mid.data_ptr(), n, 128, h, w_, _seg_layout(x), out.data_ptr(), stream)
     _lib.check(rc, "seg_head")
     return out
-
-
-_FPN_WS = {}                  # (device, stream, in_channels) -> weight-image workspace of fpn_stage (refilled per call)
 
 
 def fpn_default():
@@ -554,11 +533,7 @@ def fpn_stage(x, enc, lateral_conv, output_conv):
         return output_conv(enc + F.interpolate(cur_fpn, size=enc.shape[-2:], mode="bilinear", align_corners=False))
     n, _, h, w_ = enc.shape
     k = x.shape[1]
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device, stream, k)
-    ws = _FPN_WS.get(key)
-    if ws is None:
-        ws = _FPN_WS[key] = torch.empty(((k // 16 + 72) * 12288,), dtype=torch.uint8, device=x.device)
+    ws, stream = _workspace(x, "fpn_stage", ((k // 16 + 72) * 12288,), torch.uint8)
     nhwc = _fpn_enc_layout(enc)
     y = torch.empty((n, 128, h, w_), dtype=torch.float32, device=x.device)       # scratch in the kernels' own layout
     out = torch.empty((n, 128, h, w_), dtype=torch.float32, device=x.device)

@@ -10,8 +10,9 @@ with e = max |. - fp64| over all elements of a case,
 floor for cases where torch happens to be exact).
 Shapes (N, Cin, H, W of the output map): all halo (1 x 1), odd sizes, more than one tile in each direction, the BBBC map
 65 x 87, and one pixel less / more than the tile in each dimension -- both kernels tile the output map in 4 rows x 32 columns,
-so (3, 31) and (5, 33).  Each with enc as a contiguous NCHW map and as the channels-last view of a larger [N, S, 128] token
-tensor at a non-zero row offset, and with the norms "", "BN" and "FrozenBN" (var in [0.25, 4], mean != 0, gamma of both signs,
+so (3, 31) and (5, 33); the latter also with 48 input channels, an odd number (3) of the lateral kernel's double-buffered
+steps.  Each with enc as a contiguous NCHW map and as the channels-last view of a larger [N, S, 128] token tensor at a
+non-zero row offset, and with the norms "", "BN" and "FrozenBN" (var in [0.25, 4], mean != 0, gamma of both signs,
 one gamma = 0 on the output convolution, whose channel must be exactly relu(beta)).
 PCT_FPN_REPORT=<file> writes the measured figures of every case there as JSON."""
 import atexit
@@ -26,7 +27,7 @@ from torch.nn import functional as F
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 16, 1, 1), (2, 64, 5, 7), (1, 256, 17, 23), (3, 64, 33, 16), (2, 256, 64, 64), (1, 128, 65, 87), (1, 16, 3, 31),
-          (1, 16, 5, 33)]
+          (1, 16, 5, 33), (1, 48, 5, 33)]
 NORMS = ["", "BN", "FrozenBN"]
 ZERO_GAMMA = 5
 _FIGURES = {}

@@ -266,7 +266,7 @@ def test_linear_add_layer_norm_equals_unfused(rows):
     torch.testing.assert_close(got.double(), want, rtol=0, atol=2e-5)
 
 
-@pytest.mark.parametrize("rows,k", [(21760, 1024), (4099, 1024), (130, 256), (128, 32), (7, 2048)])
+@pytest.mark.parametrize("rows,k", [(21760, 1024), (4099, 1024), (130, 256), (128, 32), (7, 2048), (129, 96)])
 def test_linear_layer_norm_any_k_matches_fp64(rows, k):
     """Encoder FFN tail: norm2(src + linear2(h)) as one tiled GEMM on split-bf16 operands (linear_ln_split.hip),
     ragged last tile, several K; against fp64 at the fp32 noise level of a K-term dot product + LayerNorm."""
@@ -646,7 +646,8 @@ def test_token_row_conv_takes_an_nchw_contiguous_map(N, H, W):
 
 
 @pytest.mark.parametrize("N,K,H,W,bias", [(2, 256, 128, 128, True), (3, 512, 68, 64, True), (1, 2048, 16, 16, True),
-                                          (2, 32, 8, 16, False), (5, 1024, 32, 32, True), (1, 16, 16, 8, True)])
+                                          (2, 32, 8, 16, False), (5, 1024, 32, 32, True), (1, 16, 16, 8, True),
+                                          (1, 48, 8, 16, True)])         # (K = 48: an odd number of double-buffered steps)
 def test_conv1x1_nchw_is_as_accurate_as_fp32(N, K, H, W, bias):
     """The pixel decoder's 1x1 input projections on the split-bf16 MFMA kernel (csrc/conv1x1_split.hip) against fp64:
     error no larger than the fp32 convolution's own (pixel_decoder/msdeformattn.py:213-226)."""
@@ -680,7 +681,7 @@ def test_conv1x1_nchw_falls_back_where_the_kernel_does_not_apply():
     assert not fused_ops.conv1x1_nchw_supported(torch.randn(1, 64, 16, 8, device="cuda").requires_grad_(), conv)
 
 
-@pytest.mark.parametrize("N,K,H,W", [(2, 256, 32, 32), (3, 512, 16, 24), (1, 2048, 16, 16), (2, 32, 8, 16)])
+@pytest.mark.parametrize("N,K,H,W", [(2, 256, 32, 32), (3, 512, 16, 24), (1, 2048, 16, 16), (2, 32, 8, 16), (1, 48, 8, 16)])
 def test_conv1x1_groupnorm_tokens_equals_the_module_chain(N, K, H, W):
     """Input projection in one entry (csrc/conv1x1_split.hip, token epilogue + per-tile GroupNorm records + in-place
     normalisation) against nn.Sequential(Conv2d(K, 128, 1), GroupNorm(32, 128)) + flatten(2).transpose(1, 2) in fp64, written at
