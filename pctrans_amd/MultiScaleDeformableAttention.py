@@ -201,6 +201,7 @@ def from_planes(p, num_heads):
 
 def planes_forward_supported(N, S, M, D, L, Lq, P, dtype=torch.float32):
     """Geometry pct_ms_deform_attn_forward_planes_f32 covers (the pyramid-column kernel's)."""
+    # mirrors msda_col_covers (csrc/launchers.hpp), restated here because it must answer without the library
     return (dtype == torch.float32 and D == 16 and P == 4 and 3 <= L <= 5 and Lq == S and S < (1 << 24)
             and S * M * L * P * 8 < 2 ** 31 - 1 and N * (S + 4096) * M < 2 ** 31 - 1)
 

@@ -33,16 +33,18 @@ int check_common(const void *value, const int64_t *shapes, const int64_t *starts
 // a PCT_ERR_* or a hipError_t already.
 int abi_status(int rc, int not_covered = PCT_ERR_UNSUPPORTED) { return rc == pct::PCT_NOT_COVERED ? not_covered : rc; }
 
-// launch(b0, n) for images b0 .. b0 + n - 1, the batch in chunks whose value tensor stays below 2 GiB (at least one image): the
-// specialised kernels address one launch's value tensor with 32-bit byte offsets, as the reference chunks with im2col_step
-// (cu:66-80) -- same results.  Stops at the first status that is not 0 and returns it.
+// launch(sub-call) for the batch in chunks of images whose value tensor stays below 2 GiB (at least one image): the specialised
+// kernels address one launch's value tensor with 32-bit byte offsets, as the reference chunks with im2col_step (cu:66-80) --
+// same results.  elem / loc_elem: bytes per element of value and out / of loc and attn.  Stops at the first status that is
+// not 0 and returns it.
 template <typename Launch>
-int for_image_chunks(int N, long long image_bytes, Launch launch)
+int for_image_chunks(const pct::MsdaFwdCall &c, size_t elem, size_t loc_elem, Launch launch)
 {
-  int chunk = N;
+  const long long image_bytes = (long long)c.S * c.M * c.D * (long long)elem;
+  int chunk = c.N;
   while (chunk > 1 && (long long)chunk * image_bytes >= 0x7fffffffLL) chunk = (chunk + 1) / 2;
-  for (int b0 = 0; b0 < N; b0 += chunk) {
-    const int rc = launch(b0, N - b0 < chunk ? N - b0 : chunk);
+  for (int b0 = 0; b0 < c.N; b0 += chunk) {
+    const int rc = launch(c.images(b0, c.N - b0 < chunk ? c.N - b0 : chunk, elem, loc_elem));
     if (rc != 0) return rc;
   }
   return PCT_OK;
@@ -58,12 +60,8 @@ int forward_impl(const void *value, const int64_t *shapes, const int64_t *starts
   if (N == 0 || Lq == 0) return PCT_OK;
   if (!out) return PCT_ERR_BAD_ARG;
   if ((uintptr_t)out % sizeof(typename pct::Traits<T>::store_t)) return PCT_ERR_ALIGNMENT;
-  using ST = typename pct::Traits<T>::store_t;
-  return for_image_chunks(N, (long long)S * M * D * (long long)sizeof(ST), [&](const long long b0, const int n) {
-    return pct::launch_msda_forward<T>(static_cast<const ST *>(value) + b0 * S * M * D, shapes, starts, loc + b0 * Lq * M * L * P * 2,
-                                       attn + b0 * Lq * M * L * P, n, S, M, D, L, Lq, P, static_cast<ST *>(out) + b0 * Lq * M * D,
-                                       static_cast<hipStream_t>(stream));
-  });
+  const pct::MsdaFwdCall call{value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, static_cast<hipStream_t>(stream), nullptr, 0};
+  return for_image_chunks(call, sizeof(typename pct::Traits<T>::store_t), sizeof(LT), pct::launch_msda_forward<T>);
 }
 
 template <typename A>
@@ -79,8 +77,8 @@ int backward_impl(const A *value, const int64_t *shapes, const int64_t *starts, 
   if ((uintptr_t)grad_out % sizeof(A) || (uintptr_t)grad_value % sizeof(A) || (uintptr_t)grad_loc % sizeof(A) ||
       (uintptr_t)grad_attn % sizeof(A))
     return PCT_ERR_ALIGNMENT;
-  return pct::launch_msda_backward<A>(value, shapes, starts, loc, attn, grad_out, N, S, M, D, L, Lq, P,
-                                      grad_value, grad_loc, grad_attn, static_cast<hipStream_t>(stream));
+  return pct::launch_msda_backward<A>(
+      {value, shapes, starts, loc, attn, grad_out, N, S, M, D, L, Lq, P, grad_value, grad_loc, grad_attn, static_cast<hipStream_t>(stream)});
 }
 
 // The arguments the three dynamic-mask-head entry points share.  They differ in the workspace (`has_ws`: required, aligned to
@@ -320,13 +318,9 @@ int pct_ms_deform_attn_fused_forward_f32(const float *value, const int64_t *spat
   if (batch == 0 || num_query == 0) return PCT_OK;
   if (!output || !ref_points || ref_batch_stride < 0) return PCT_ERR_BAD_ARG;
   if (((uintptr_t)output | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
-  const long long S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-  return abi_status(for_image_chunks(batch, S * M * D * 4, [&](const long long b0, const int n) {
-    return pct::launch_msda_forward_special<float>(
-        value + b0 * S * M * D, spatial_shapes, level_start, offsets + b0 * Lq * M * L * P * 2, attn_logits + b0 * Lq * M * L * P,
-        n, spatial_size, num_heads, channels, num_levels, num_query, num_point, output + b0 * Lq * M * D,
-        static_cast<hipStream_t>(stream), ref_points + b0 * ref_batch_stride, ref_batch_stride);
-  }));
+  const pct::MsdaFwdCall call{value, spatial_shapes, level_start, offsets, attn_logits, batch, spatial_size, num_heads, channels,
+                              num_levels, num_query, num_point, output, static_cast<hipStream_t>(stream), ref_points, ref_batch_stride};
+  return abi_status(for_image_chunks(call, sizeof(float), sizeof(float), pct::launch_msda_forward_special<float>));
 }
 
 int pct_ms_deform_attn_forward_planes_f32(const float *value_planes, const int64_t *spatial_shapes, const int64_t *level_start,
@@ -341,14 +335,10 @@ int pct_ms_deform_attn_forward_planes_f32(const float *value_planes, const int64
   if (!output || ref_batch_stride < 0) return PCT_ERR_BAD_ARG;
   if (((uintptr_t)output | (uintptr_t)ref_points) & 3u) return PCT_ERR_ALIGNMENT;
   if (num_query != spatial_size || channels != 16 || num_point != 4) return PCT_ERR_UNSUPPORTED;
-  const long long S = spatial_size, M = num_heads, D = channels, L = num_levels, Lq = num_query, P = num_point;
-  return abi_status(for_image_chunks(batch, S * M * D * 4, [&](const long long b0, const int n) {
-    return pct::launch_msda_forward_planes(
-        value_planes + b0 * S * M * D, spatial_shapes, level_start, loc_planes + b0 * Lq * M * L * P * 2,
-        attn_planes + b0 * Lq * M * L * P, n, spatial_size, num_heads, channels, num_levels, num_query, num_point,
-        output + b0 * Lq * M * D, static_cast<hipStream_t>(stream), ref_points ? ref_points + b0 * ref_batch_stride : nullptr,
-        ref_batch_stride);
-  }));
+  const pct::MsdaFwdCall call{value_planes, spatial_shapes, level_start, loc_planes, attn_planes, batch, spatial_size, num_heads,
+                              channels, num_levels, num_query, num_point, output, static_cast<hipStream_t>(stream), ref_points,
+                              ref_batch_stride};
+  return abi_status(for_image_chunks(call, sizeof(float), sizeof(float), pct::launch_msda_forward_planes));
 }
 
 int pct_ms_deform_attn_backward_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,

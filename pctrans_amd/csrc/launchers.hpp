@@ -21,53 +21,87 @@ constexpr int PCT_NOT_COVERED = -100;
 enum MsdaFwdKernel { MSDA_FWD_AUTO = 0, MSDA_FWD_WIN = 1, MSDA_FWD_GENERIC = 2, MSDA_FWD_QUAD = 3, MSDA_FWD_COL = 4 };
 enum MsdaBwdKernel { MSDA_BWD_AUTO = 0, MSDA_BWD_WIN = 1, MSDA_BWD_GENERIC = 2, MSDA_BWD_COL = 3 };
 
-// ---- MSDeformAttn forward (msda_forward*.hip).  ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits,
-// ref = reference points, images ref_batch_stride floats apart).  The specialised kernels return PCT_NOT_COVERED for a
-// geometry they do not cover -------------------------------------------------------------------------------------------
-template <typename T>
-int launch_msda_forward(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn, int N,
-                        int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream);
-template <typename T>
-int launch_msda_forward_special(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                                const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream,
-                                const float *ref, long long ref_batch_stride);
-int launch_msda_forward_planes(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
-                               int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
-                               long long ref_batch_stride);
-template <typename T>
-int launch_msda_forward_win(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
-                            int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
-                            long long ref_batch_stride);
-template <typename T>
-int launch_msda_forward_dpp(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
-                            int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
-                            long long ref_batch_stride);
-int launch_msda_forward_col(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
-                            int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
-                            long long ref_batch_stride, bool planes);
-template <typename T>
-int launch_msda_forward_col16(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
-                              int N, int S, int M, int D, int L, int Lq, int P, void *out, hipStream_t stream, const float *ref,
-                              long long ref_batch_stride);
+// ---- MSDeformAttn: one call = one struct.  Every launch_msda_* takes it by const reference; what only one launcher needs
+// (`planes`, `forced`) comes as an extra argument.  value / out are of the launcher's storage type, loc / attn of its
+// accumulator type (float, or double for the fp64 kernels).
+// ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits, ref = reference points, images ref_batch_stride
+// floats apart) -----------------------------------------------------------------------------------------------------------
+struct MsdaFwdCall {
+  const void *value;
+  const int64_t *shapes, *starts;
+  const void *loc, *attn;
+  int N, S, M, D, L, Lq, P;
+  void *out;
+  hipStream_t stream;
+  const float *ref;
+  long long ref_batch_stride;
+
+  // the same call for images b0 .. b0 + n - 1 (elem / loc_elem: bytes per element of value and out / of loc and attn)
+  MsdaFwdCall images(long long b0, int n, size_t elem, size_t loc_elem) const
+  {
+    MsdaFwdCall c = *this;
+    const long long rec0 = b0 * Lq * M;                                        // first (query, head) record of image b0
+    c.value = static_cast<const char *>(value) + b0 * S * M * D * (long long)elem;
+    c.loc = static_cast<const char *>(loc) + rec0 * L * P * 2 * (long long)loc_elem;
+    c.attn = static_cast<const char *>(attn) + rec0 * L * P * (long long)loc_elem;
+    c.out = static_cast<char *>(out) + rec0 * D * (long long)elem;
+    if (ref) c.ref = ref + b0 * ref_batch_stride;
+    c.N = n;
+    return c;
+  }
+};
+struct MsdaBwdCall {
+  const void *value;
+  const int64_t *shapes, *starts;
+  const void *loc, *attn, *grad_out;
+  int N, S, M, D, L, Lq, P;
+  void *grad_value, *grad_loc, *grad_attn;
+  hipStream_t stream;
+};
+
+// The geometry and arithmetic headroom the two fp32 pyramid-column kernels (msda_forward_col.hip, msda_backward_col.hip)
+// share; each launcher adds its own alignment checks.  (planes_forward_supported in MultiScaleDeformableAttention.py mirrors it.)
+template <typename Call>   // MsdaFwdCall or MsdaBwdCall
+inline bool msda_col_covers(const Call &c)
+{
+  const int N = c.N, S = c.S, M = c.M, D = c.D, L = c.L, Lq = c.Lq, P = c.P;
+  if (D != 16 || P != 4 || L < 3 || L > 5 || Lq != S || M < 1) return false;
+  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return false;   // item / record arithmetic headroom
+  if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return false;               // 32-bit byte offsets inside an image, all tensors
+  if ((long long)S * M * D * 4 >= 0x7fffffffLL) return false;                   // (0x80000000 is the out-of-range sentinel)
+  return S < (1 << 24) && M < (1 << 16);                                        // 24-bit multiplies in the record index
+}
+
+// ---- MSDeformAttn forward.  launch_msda_forward is the route the plain entry points take (msda_route.hip: a specialised
+// kernel, else the generic one), launch_msda_forward_special the specialised kernels alone and launch_msda_forward_planes
+// the piece-plane operands' one.  The others launch one kernel each (msda_forward*.hip); the specialised ones return
+// PCT_NOT_COVERED for a call they do not cover ----------------------------------------------------------------------------
+template <typename T> int launch_msda_forward(const MsdaFwdCall &c);
+template <typename T> int launch_msda_forward_special(const MsdaFwdCall &c);
+int launch_msda_forward_planes(const MsdaFwdCall &c);
+template <typename T> int launch_msda_forward_generic(const MsdaFwdCall &c);
+template <typename T> int launch_msda_forward_win(const MsdaFwdCall &c);
+template <typename T> int launch_msda_forward_dpp(const MsdaFwdCall &c);
+int launch_msda_forward_col(const MsdaFwdCall &c, bool planes);
+template <typename T> int launch_msda_forward_col16(const MsdaFwdCall &c);
 void set_msda_kernel_choice(int v);     // a MsdaFwdKernel; anything else: follow PCT_MSDA_KERNEL
-int msda_kernel_choice();
-void note_msda_kernel(int k);
 int msda_last_kernel();
 
-// ---- MSDeformAttn backward (msda_backward*.hip) ------------------------------------------------------------------------
-template <typename A>
-int launch_msda_backward(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc, const void *attn,
-                         const void *grad_out, int N, int S, int M, int D, int L, int Lq, int P, void *grad_value, void *grad_loc,
-                         void *grad_attn, hipStream_t stream);
-int launch_msda_backward_win(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
-                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                             float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream);
-int launch_msda_backward_col(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
-                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P,
-                             float *grad_value, float *grad_loc, float *grad_attn, bool forced, hipStream_t stream);
+// ---- MSDeformAttn backward.  launch_msda_backward is the route (msda_route.hip): it zeroes the gradients, then column ->
+// windowed -> generic.  The others launch one kernel each (msda_backward*.hip) into gradients already zeroed --------------
+template <typename A> int launch_msda_backward(const MsdaBwdCall &c);
+template <typename A> int launch_msda_backward_generic(const MsdaBwdCall &c);
+int launch_msda_backward_win(const MsdaBwdCall &c);
+int launch_msda_backward_col(const MsdaBwdCall &c, bool forced);
+// the generic backward kernel reduces a record's three channel sums by wave shuffles and stores grad_loc / grad_attn plainly
+// (as the specialised kernels do) when its D / VEC lanes form a power-of-two group inside a wave; otherwise it adds into them
+inline bool msda_backward_shuffles(int D, size_t elem)
+{
+  const int vecw = 16 / (int)elem, cv = D / vecw;
+  return D % vecw == 0 && cv <= 64 && (cv & (cv - 1)) == 0;
+}
+hipError_t zero_fill(void *ptr, size_t bytes, hipStream_t stream);   // msda_backward.hip: by a kernel, not hipMemsetAsync
 void set_msda_bwd_kernel_choice(int c);  // a MsdaBwdKernel; anything else: follow PCT_MSDA_BWD_KERNEL
-int msda_bwd_kernel_choice();
-void note_msda_bwd_kernel(int k);
 int msda_bwd_last_kernel();
 
 // ---- once per device, outside any stream capture (pct_prepare_device) ---------------------------------------------------

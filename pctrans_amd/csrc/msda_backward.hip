@@ -12,9 +12,6 @@
 // the three channel sums are xor-butterflies in registers.  Their results overwrite the record's staged
 // (x,y,weight) slots in LDS and leave the block as coalesced 16-byte stores.  grad_value uses hardware float
 // atomics (global_atomic_add_f32 / _f64), 64 contiguous bytes per record-corner.
-#include <stdlib.h>
-#include <string.h>
-
 #include "msda_common.hpp"
 #include "launchers.hpp"
 
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(256) void zero_fill_kernel(unsigned *__restrict__ p
   for (size_t i = i0; i < n16; i += stride) q[i] = u32x4{0u, 0u, 0u, 0u};
   if (i0 < tail) p[head + n16 * 4 + i0] = 0u;
 }
-static hipError_t zero_fill(void *ptr, const size_t bytes, hipStream_t stream)
+hipError_t zero_fill(void *ptr, const size_t bytes, hipStream_t stream)
 {
   if (bytes == 0) return hipSuccess;
   // (every caller passes fp32 / fp64 tensors: 4-byte aligned, a multiple of 4 bytes.  Anything else is refused rather than
@@ -198,54 +195,19 @@ static hipError_t zero_fill(void *ptr, const size_t bytes, hipStream_t stream)
   return hipGetLastError();
 }
 
+// the generic kernel's own launcher (grad_value zeroed by the caller, and grad_loc / grad_attn unless msda_backward_shuffles)
 template <typename A>
-int launch_msda_backward(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                         const void *attn, const void *grad_out, int N, int S, int M, int D, int L, int Lq,
-                         int P, void *grad_value, void *grad_loc, void *grad_attn, hipStream_t stream)
+int launch_msda_backward_generic(const MsdaBwdCall &c)
 {
+  const int N = c.N, S = c.S, M = c.M, D = c.D, L = c.L, Lq = c.Lq, P = c.P;
   constexpr int VECW = 16 / (int)sizeof(A);
   const bool vec = (D % VECW) == 0;   // the backward touches channels one scalar at a time: no 16-B alignment need
   const int VEC = vec ? VECW : 1;
   const int CV = D / VEC;
-  const bool shfl = vec && CV <= 64 && (CV & (CV - 1)) == 0;
+  const bool shfl = msda_backward_shuffles(D, sizeof(A));
   const long long total_lanes = (long long)N * Lq * M * CV;
   const int LP = L * P;
-
-  hipError_t e = zero_fill(grad_value, sizeof(A) * (size_t)N * S * M * D, stream);
-  if (e != hipSuccess) return (int)e;
-  if (!shfl) {
-    e = zero_fill(grad_loc, sizeof(A) * (size_t)N * Lq * M * LP * 2, stream);
-    if (e != hipSuccess) return (int)e;
-    e = zero_fill(grad_attn, sizeof(A) * (size_t)N * Lq * M * LP, stream);
-    if (e != hipSuccess) return (int)e;
-  }
   if (total_lanes == 0) return 0;
-  if constexpr (sizeof(A) == 4) {
-    // PCT_MSDA_BWD_KERNEL = auto (pyramid-column when the queries are the pyramid's own pixels and the problem fills the
-    // chip, else windowed, else generic) | col | win | generic; pct_msda_set_bwd_kernel_choice overrides the environment
-    const int mode = msda_bwd_kernel_choice();
-    if (shfl && (mode == MSDA_BWD_AUTO || mode == MSDA_BWD_COL) && Lq == S) {
-      const int rc = launch_msda_backward_col(
-          static_cast<const float *>(value), shapes, starts, static_cast<const float *>(loc),
-          static_cast<const float *>(attn), static_cast<const float *>(grad_out), N, S, M, D, L, Lq, P,
-          static_cast<float *>(grad_value), static_cast<float *>(grad_loc), static_cast<float *>(grad_attn), mode == MSDA_BWD_COL, stream);
-      if (rc != PCT_NOT_COVERED) {
-        note_msda_bwd_kernel(MSDA_BWD_COL);
-        return rc;
-      }
-    }
-    if (shfl && mode != MSDA_BWD_GENERIC && (mode == MSDA_BWD_WIN || Lq == S)) {
-      const int rc = launch_msda_backward_win(
-          static_cast<const float *>(value), shapes, starts, static_cast<const float *>(loc),
-          static_cast<const float *>(attn), static_cast<const float *>(grad_out), N, S, M, D, L, Lq, P,
-          static_cast<float *>(grad_value), static_cast<float *>(grad_loc), static_cast<float *>(grad_attn), stream);
-      if (rc != PCT_NOT_COVERED) {
-        note_msda_bwd_kernel(MSDA_BWD_WIN);
-        return rc;
-      }
-    }
-  }
-  note_msda_bwd_kernel(MSDA_BWD_GENERIC);
   const long long nblk = (total_lanes + BWD_BLOCK - 1) / BWD_BLOCK;
   if (nblk > 0x7fffffffLL) return PCT_ERR_UNSUPPORTED;
   const int rec_stride = sizeof(A) == 4 ? padded_record_stride(LP * 3) : LP * 3 + 1;
@@ -254,13 +216,13 @@ int launch_msda_backward(const void *value, const int64_t *shapes, const int64_t
   if (lds_bytes > 64 * 1024) return PCT_ERR_UNSUPPORTED;
 
   const dim3 grid((unsigned)nblk), block(BWD_BLOCK);
-  const A *go = static_cast<const A *>(grad_out), *v = static_cast<const A *>(value);
-  const A *lc = static_cast<const A *>(loc), *at = static_cast<const A *>(attn);
-  A *gv = static_cast<A *>(grad_value), *gl = static_cast<A *>(grad_loc), *ga = static_cast<A *>(grad_attn);
+  const A *go = static_cast<const A *>(c.grad_out), *v = static_cast<const A *>(c.value);
+  const A *lc = static_cast<const A *>(c.loc), *at = static_cast<const A *>(c.attn);
+  A *gv = static_cast<A *>(c.grad_value), *gl = static_cast<A *>(c.grad_loc), *ga = static_cast<A *>(c.grad_attn);
 
-#define PCT_LAUNCH(VEC_, CVT_, PT_, SH_)                                                                     \
-  hipLaunchKernelGGL((msda_backward_kernel<A, VEC_, CVT_, PT_, SH_>), grid, block, lds_bytes, stream, go, v, \
-                     shapes, starts, lc, at, S, M, D, L, Lq, P, CV, total_lanes, rec_stride, gv, gl, ga)
+#define PCT_LAUNCH(VEC_, CVT_, PT_, SH_)                                                                       \
+  hipLaunchKernelGGL((msda_backward_kernel<A, VEC_, CVT_, PT_, SH_>), grid, block, lds_bytes, c.stream, go, v, \
+                     c.shapes, c.starts, lc, at, S, M, D, L, Lq, P, CV, total_lanes, rec_stride, gv, gl, ga)
 #define PCT_CV_CASE(CVT_)                        \
   case CVT_:                                     \
     if (P == 4) PCT_LAUNCH(VECW, CVT_, 4, true); \
@@ -280,11 +242,7 @@ int launch_msda_backward(const void *value, const int64_t *shapes, const int64_t
   return (int)hipGetLastError();
 }
 
-template int launch_msda_backward<float>(const void *, const int64_t *, const int64_t *, const void *,
-                                         const void *, const void *, int, int, int, int, int, int, int, void *,
-                                         void *, void *, hipStream_t);
-template int launch_msda_backward<double>(const void *, const int64_t *, const int64_t *, const void *,
-                                          const void *, const void *, int, int, int, int, int, int, int, void *,
-                                          void *, void *, hipStream_t);
+template int launch_msda_backward_generic<float>(const MsdaBwdCall &);
+template int launch_msda_backward_generic<double>(const MsdaBwdCall &);
 
 }  // namespace pct

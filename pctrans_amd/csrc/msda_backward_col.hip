@@ -33,9 +33,7 @@
 //     the main kernel that cold path cost 120 spilled registers whose reloads sat in the per-item planning.
 #include <math.h>
 #include <stdlib.h>
-#include <string.h>
 
-#include <atomic>
 #include <mutex>
 #include <utility>
 
@@ -55,12 +53,6 @@ constexpr size_t BCOL_FLAG_STRIDE = BCOL_FLAG_BYTES + 64;
 static_assert(BCOL_POOL_BYTES >= BCOL_GPX * 64, "value windows must fit the pool");
 static_assert(BCOL_CNT_BYTES + 7 * BCOL_PLANE_BYTES + 8 < 65536, "ds immediate offsets");
 static_assert((BCOL_PLANE_BYTES / 4) % 64 == 8, "plane stride in banks");
-
-template <int L>
-__host__ __device__ constexpr int bcol_level_of_step(const int ll)   // finest, coarsest, then the middle levels (as the forward)
-{
-  return ll == 0 ? L - 1 : (ll == 1 ? 0 : L - ll);
-}
 
 template <int L, bool DIRECT>
 __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
@@ -548,7 +540,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
       bool any = false;
 #pragma unroll
       for (int ll = 0; ll < L; ++ll) {
-        const int l = bcol_level_of_step<L>(ll);
+        const int l = col_level_of_step<L>(ll);
         if (wsize[l] > pool_use || big_map) {
           phase_of[l] = -1;
           wbase[l] = 0;
@@ -876,24 +868,6 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
   }
 }
 
-// ---- kernel choice for the backward (diagnostics; see include/pctrans_hip.h) ---------------------------------------------
-static std::atomic<int> g_bwd_choice{-1};                                    // -1: follow PCT_MSDA_BWD_KERNEL
-static std::atomic<int> g_bwd_last{0};
-void set_msda_bwd_kernel_choice(int c) { g_bwd_choice.store((c >= MSDA_BWD_AUTO && c <= MSDA_BWD_COL) ? c : -1); }
-int msda_bwd_last_kernel() { return g_bwd_last.load(); }
-void note_msda_bwd_kernel(int k) { g_bwd_last.store(k); }
-int msda_bwd_kernel_choice()
-{
-  const int c = g_bwd_choice.load();
-  if (c >= 0) return c;
-  static const int env = [] {
-    const char *e = getenv("PCT_MSDA_BWD_KERNEL");
-    if (!e) return MSDA_BWD_AUTO;
-    return !strcmp(e, "win") ? MSDA_BWD_WIN : (!strcmp(e, "generic") ? MSDA_BWD_GENERIC : (!strcmp(e, "col") ? MSDA_BWD_COL : MSDA_BWD_AUTO));
-  }();
-  return env;
-}
-
 // One byte per work item for the main launch to tell the DIRECT one which levels are left (see the header).  Buffers of
 // BCOL_FLAG_BYTES each, allocated once per device: a ring for eager launches (launches in flight together on different
 // streams must not share one) and a pool handed out once each to launches recorded into a HIP graph (the pointer is baked
@@ -986,18 +960,18 @@ int prepare_msda_backward_col_device()
 }
 
 // returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel)
-int launch_msda_backward_col(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
-                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
-                             int P, float *grad_value, float *grad_loc, float *grad_attn, bool forced, hipStream_t stream)
+int launch_msda_backward_col(const MsdaBwdCall &c, bool forced)
 {
+  const int N = c.N, S = c.S, M = c.M, L = c.L;
+  hipStream_t stream = c.stream;
+  const float *value = static_cast<const float *>(c.value), *grad_out = static_cast<const float *>(c.grad_out);
+  const float *loc = static_cast<const float *>(c.loc), *attn = static_cast<const float *>(c.attn);
+  float *grad_value = static_cast<float *>(c.grad_value), *grad_loc = static_cast<float *>(c.grad_loc);
+  float *grad_attn = static_cast<float *>(c.grad_attn);
   if ((((uintptr_t)value | (uintptr_t)grad_out | (uintptr_t)loc | (uintptr_t)attn | (uintptr_t)grad_loc |
         (uintptr_t)grad_attn) & 15u) || ((uintptr_t)grad_value & 3u))
     return PCT_NOT_COVERED;
-  if (D != 16 || P != 4 || L < 3 || L > 5 || Lq != S || M < 1) return PCT_NOT_COVERED;
-  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;   // item / record arithmetic headroom
-  if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return PCT_NOT_COVERED;               // 32-bit byte offsets inside an image, all tensors
-  if ((long long)S * M * D * 4 >= 0x7fffffffLL) return PCT_NOT_COVERED;                   // (0x80000000 is the out-of-range sentinel)
-  if (S >= (1 << 24) || M >= (1 << 16)) return PCT_NOT_COVERED;                           // 24-bit multiplies in the record index
+  if (!msda_col_covers(c)) return PCT_NOT_COVERED;
   // (measured against the windowed kernel down to one 256^2-image pyramid, 43 k (query, head) pairs: 0.042 vs 0.055 ms;
   // profiles/r03_bwd_small_sizes.txt)
   if (!forced && (long long)N * S * M < 32768) return PCT_NOT_COVERED;
@@ -1017,10 +991,10 @@ int launch_msda_backward_col(const float *value, const int64_t *shapes, const in
     const hipError_t attr_rc2 = func_attr_per_device(reinterpret_cast<const void *>(&msda_backward_col_kernel<L_, true>));  \
     if (attr_rc != hipSuccess) return (int)attr_rc;                                                                        \
     if (attr_rc2 != hipSuccess) return (int)attr_rc2;                                                                      \
-    hipLaunchKernelGGL((msda_backward_col_kernel<L_, false>), grid, block, lds, stream, grad_out, value, shapes, starts,   \
-                       loc, attn, N, S, M, grad_value, grad_loc, grad_attn, queue, flags, flag_cap);                          \
-    hipLaunchKernelGGL((msda_backward_col_kernel<L_, true>), grid, block, lds_direct, stream, grad_out, value, shapes,     \
-                       starts, loc, attn, N, S, M, grad_value, grad_loc, grad_attn, nullptr, flags, flag_cap);               \
+    hipLaunchKernelGGL((msda_backward_col_kernel<L_, false>), grid, block, lds, stream, grad_out, value, c.shapes,         \
+                       c.starts, loc, attn, N, S, M, grad_value, grad_loc, grad_attn, queue, flags, flag_cap);             \
+    hipLaunchKernelGGL((msda_backward_col_kernel<L_, true>), grid, block, lds_direct, stream, grad_out, value, c.shapes,   \
+                       c.starts, loc, attn, N, S, M, grad_value, grad_loc, grad_attn, nullptr, flags, flag_cap);           \
   } while (0)
   if (L == 3) PCT_BCOL(3);
   else if (L == 4) PCT_BCOL(4);

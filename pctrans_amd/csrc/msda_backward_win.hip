@@ -544,10 +544,12 @@ __global__ __launch_bounds__(WIN_BLOCK, 2) void msda_backward_win_kernel(
 }
 
 // returns PCT_NOT_COVERED when this geometry is not covered (caller uses msda_backward.hip)
-int launch_msda_backward_win(const float *value, const int64_t *shapes, const int64_t *starts, const float *loc,
-                             const float *attn, const float *grad_out, int N, int S, int M, int D, int L, int Lq,
-                             int P, float *grad_value, float *grad_loc, float *grad_attn, hipStream_t stream)
+int launch_msda_backward_win(const MsdaBwdCall &c)
 {
+  const int N = c.N, S = c.S, M = c.M, D = c.D, L = c.L, Lq = c.Lq, P = c.P;
+  const float *value = static_cast<const float *>(c.value), *grad_out = static_cast<const float *>(c.grad_out);
+  const float *loc = static_cast<const float *>(c.loc), *attn = static_cast<const float *>(c.attn);
+  float *grad_value = static_cast<float *>(c.grad_value), *grad_loc = static_cast<float *>(c.grad_loc);
   if ((((uintptr_t)value | (uintptr_t)grad_out) & 15u) || (((uintptr_t)loc | (uintptr_t)grad_loc) & 7u)) return PCT_NOT_COVERED;
   if (D != 16 || P != 4 || L < 3 || L > 5) return PCT_NOT_COVERED;
   if ((long long)N * Lq * M < 32768) return PCT_NOT_COVERED;
@@ -559,10 +561,10 @@ int launch_msda_backward_win(const float *value, const int64_t *shapes, const in
   const int wg_per_cu = wg_fit < 1 ? 1 : (wg_fit > 3 ? 3 : wg_fit);
   const int pyramid = Lq == S ? 1 : 0;
   const dim3 grid(256 * wg_per_cu), block(WIN_BLOCK);
-  unsigned *queue = win_queue_slot(stream);                        // nullptr: static item stride
-#define PCT_BWIN(L_)                                                                                               \
-  hipLaunchKernelGGL((msda_backward_win_kernel<L_>), grid, block, lds, stream, grad_out, value, shapes, starts, loc, \
-                     attn, N, S, M, Lq, pyramid, grad_value, grad_loc, grad_attn, queue)
+  unsigned *queue = win_queue_slot(c.stream);                      // nullptr: static item stride
+#define PCT_BWIN(L_)                                                                                                  \
+  hipLaunchKernelGGL((msda_backward_win_kernel<L_>), grid, block, lds, c.stream, grad_out, value, c.shapes, c.starts, \
+                     loc, attn, N, S, M, Lq, pyramid, grad_value, grad_loc, static_cast<float *>(c.grad_attn), queue)
   if (L == 3) PCT_BWIN(3);
   else if (L == 4) PCT_BWIN(4);
   else PCT_BWIN(5);

@@ -1,5 +1,5 @@
 // Helpers shared by the pyramid-column MSDeformAttn kernels (msda_forward_col.hip: fp32 values, 4 points;
-// msda_forward_col16.hip: 16-bit values, 4 or 8 points).
+// msda_forward_col16.hip: 16-bit values, 4 or 8 points; msda_backward_col.hip: the fp32 backward).
 #pragma once
 #include "msda_win_common.hpp"
 
@@ -8,6 +8,17 @@ namespace pct {
 typedef int col_i32x4 __attribute__((ext_vector_type(4)));
 typedef float col_f32x2 __attribute__((ext_vector_type(2)));
 typedef float col_f32x4 __attribute__((ext_vector_type(4)));
+
+// Gather order of the levels (step ll -> level).  The finest level (the last one in PCTrans' pyramids) comes first; its
+// window is the largest, and the level that most often still fits beside it in the pool is the COARSEST one, so that
+// one goes second and the two middle levels share the next phase: with model-like offsets at the north-star shape
+// {finest, coarsest} + {the two middle levels} is two phases where finest-to-coarsest order needed three for every
+// fifth item (each phase costs a re-staging of the pool and two barriers).
+template <int L>
+__host__ __device__ constexpr int col_level_of_step(const int ll)
+{
+  return ll == 0 ? L - 1 : (ll == 1 ? 0 : L - ll);
+}
 
 // first pixel x of column c (of C) on a level W pixels wide: the pixels whose centre (x + 0.5) / W lies in
 // [c / C, (c + 1) / C); every pixel belongs to exactly one column, col_lo(C) == W

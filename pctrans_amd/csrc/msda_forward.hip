@@ -15,10 +15,6 @@
 //     branches around loads; an Inf/NaN in an unread texel can not leak through a 0 * v product);
 //   * the point loop is unrolled at compile time for P = 4 / 8 so 4*P 16-byte gathers are in flight per lane;
 //   * logical block order is remapped so that each XCD's L2 serves one contiguous range of queries.
-#include <stdlib.h>
-
-#include <atomic>
-
 #include "msda_common.hpp"
 #include "launchers.hpp"
 
@@ -193,112 +189,16 @@ __global__ __launch_bounds__(FWD_BLOCK) void msda_forward_kernel(
   }
 }
 
-// Kernel choice for PCTrans' geometry.  Default "auto": the windowed-LDS kernel when the queries are the pyramid's
-// own pixels (Lq == S: neighbouring queries sample neighbouring texels, the case it is built for) and the problem fills
-// its persistent grid (except where it was measured slower, see below), else the quad-owner kernel.
-// PCT_MSDA_KERNEL = auto | win | dpp | generic | col (development A/B).
-static std::atomic<int> g_kernel_override{-1};     // pct_msda_set_kernel_choice (diagnostic): -1 = follow the environment
-static std::atomic<int> g_last_kernel{0};          // pct_msda_last_kernel (diagnostic): what the last forward call launched
-void set_msda_kernel_choice(int v) { g_kernel_override.store((v >= MSDA_FWD_AUTO && v <= MSDA_FWD_COL) ? v : -1, std::memory_order_relaxed); }
-int msda_last_kernel() { return g_last_kernel.load(std::memory_order_relaxed); }
-void note_msda_kernel(int k) { g_last_kernel.store(k, std::memory_order_relaxed); }
-
-int msda_kernel_choice()
-{
-  const int ov = g_kernel_override.load(std::memory_order_relaxed);
-  if (ov >= 0) return ov;
-  static const int v = [] {
-    const char *e = getenv("PCT_MSDA_KERNEL");
-    if (!e) return MSDA_FWD_AUTO;
-    if (e[0] == 'w') return MSDA_FWD_WIN;
-    if (e[0] == 'd') return MSDA_FWD_QUAD;
-    if (e[0] == 'g') return MSDA_FWD_GENERIC;
-    if (e[0] == 'c') return MSDA_FWD_COL;
-    return MSDA_FWD_AUTO;
-  }();
-  return v;
-}
-
-// shared by the plain and the fused entry points: PCT_NOT_COVERED = geometry not covered by the specialised kernels
-template <typename T>
-int launch_msda_forward_special(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                                const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                                hipStream_t stream, const float *ref, long long ref_batch_stride)
-{
-  const int choice = msda_kernel_choice();
-  if (choice == MSDA_FWD_GENERIC) return PCT_NOT_COVERED;
-  int rc = PCT_NOT_COVERED;
-  // 16-bit values with 8 points per level (SURVEY config 5): the windowed variant (2 lanes per head-pixel, 4 points per
-  // lane and level, 20-40 spilled VGPRs) loses to the quad-owner kernel (P3, N = 1: 0.49 vs 0.34 ms) -- measured, so
-  // "auto" skips it there; fp32 with 8 points and 16-bit with 4 points stay on the windowed kernel (faster)
-  const bool win_loses = sizeof(typename Traits<T>::store_t) == 2 && P == 8;
-  // ... and a persistent grid of 768 workgroups needs about three work items each to beat the quad-owner kernel
-  // (P2: N = 1 0.046 vs 0.040 ms, N = 2 equal, N = 4 0.089 vs 0.113 ms; P4, N = 1: 0.024 vs 0.014 ms)
-  const long long per_item = P == 8 ? 128 : (sizeof(typename Traits<T>::store_t) == 2 ? 512 : 256);   // queries per item
-  const bool win_small = (long long)N * ((Lq + per_item - 1) / per_item) * M < 3 * 768;
-  // the pyramid-column kernel (fp32, 4 points): persistent grid of 768 workgroups with items of <= 256 queries.  Measured
-  // crossover against the windowed / quad-owner kernels (model-like locations, profiles/r02_small_batch.txt): with 4
-  // levels it wins from one 512^2 image on (N * S * M = 174 k); with 3 levels from about 450 k (quad-owner before that)
-  if constexpr (sizeof(typename Traits<T>::store_t) == 4) {
-    const bool col_big = (long long)N * S * M >= (L >= 4 ? 160000LL : 450000LL);
-    if (choice == MSDA_FWD_COL || (choice == MSDA_FWD_AUTO && Lq == S && P == 4 && col_big)) {
-      rc = launch_msda_forward_col(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref, ref_batch_stride, false);
-      if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_COL);
-    }
-  }
-  if constexpr (sizeof(typename Traits<T>::store_t) == 2) {
-    // 16-bit values: the column kernel's 16-bit variant (4 or 8 points; two lanes per (query, head) with 8 points)
-    const bool col_big = (long long)N * S * M * (P / 4) >= (L >= 4 ? 160000LL : 450000LL);
-    if (choice == MSDA_FWD_COL || (choice == MSDA_FWD_AUTO && Lq == S && (P == 4 || P == 8) && col_big)) {
-      rc = launch_msda_forward_col16<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
-                                        ref_batch_stride);
-      if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_COL);
-    }
-  }
-  if (rc == PCT_NOT_COVERED && (choice == MSDA_FWD_WIN || (choice == MSDA_FWD_AUTO && Lq == S && !win_loses && !win_small))) {
-    rc = launch_msda_forward_win<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
-                                    ref_batch_stride);
-    if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_WIN);
-  }
-  if (rc == PCT_NOT_COVERED) {
-    rc = launch_msda_forward_dpp<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
-                                    ref_batch_stride);
-    if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_QUAD);
-  }
-  return rc;
-}
-// piece-plane operands (pct_ms_deform_attn_forward_planes_f32): the pyramid-column kernel or nothing (PCT_NOT_COVERED)
-int launch_msda_forward_planes(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                               const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                               hipStream_t stream, const float *ref, long long ref_batch_stride)
-{
-  const int rc = launch_msda_forward_col(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream, ref,
-                                         ref_batch_stride, true);
-  if (rc != PCT_NOT_COVERED) note_msda_kernel(MSDA_FWD_COL);
-  return rc;
-}
-
-template int launch_msda_forward_special<float>(const void *, const int64_t *, const int64_t *, const void *,
-                                                const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                                const float *, long long);
-
 // ---- host-side launcher ---------------------------------------------------------------------------------
 template <typename T>
-int launch_msda_forward(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                        const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                        hipStream_t stream)
+int launch_msda_forward_generic(const MsdaFwdCall &c)
 {
   using A = typename Traits<T>::acc_t;
   using ST = typename Traits<T>::store_t;
-  if constexpr (sizeof(A) == 4) {
-    const int rc = launch_msda_forward_special<T>(value, shapes, starts, loc, attn, N, S, M, D, L, Lq, P, out, stream,
-                                                  nullptr, 0);
-    if (rc != PCT_NOT_COVERED) return rc;
-  }
-  note_msda_kernel(MSDA_FWD_GENERIC);
+  const int N = c.N, S = c.S, M = c.M, D = c.D, L = c.L, Lq = c.Lq, P = c.P;
   constexpr int VECW = 16 / (int)sizeof(ST);                    // channels in one 16-byte lane load
-  const bool aligned16 = (((uintptr_t)value | (uintptr_t)out) & 15u) == 0 &&
-                         (((uintptr_t)loc | (uintptr_t)attn) & 15u) == 0;
+  const bool aligned16 = (((uintptr_t)c.value | (uintptr_t)c.out) & 15u) == 0 &&
+                         (((uintptr_t)c.loc | (uintptr_t)c.attn) & 15u) == 0;
   const bool vec = aligned16 && (D % VECW) == 0;
   const int VEC = vec ? VECW : 1;
   const int CV = D / VEC;
@@ -313,14 +213,14 @@ int launch_msda_forward(const void *value, const int64_t *shapes, const int64_t 
   if (lds_bytes > 64 * 1024) return PCT_ERR_UNSUPPORTED;
 
   const dim3 grid((unsigned)nblk), block(FWD_BLOCK);
-  const ST *v = static_cast<const ST *>(value);
-  const A *lc = static_cast<const A *>(loc);
-  const A *at = static_cast<const A *>(attn);
-  ST *o = static_cast<ST *>(out);
+  const ST *v = static_cast<const ST *>(c.value);
+  const A *lc = static_cast<const A *>(c.loc);
+  const A *at = static_cast<const A *>(c.attn);
+  ST *o = static_cast<ST *>(c.out);
 
-#define PCT_LAUNCH(VEC_, CVT_, PT_)                                                                        \
-  hipLaunchKernelGGL((msda_forward_kernel<T, VEC_, CVT_, PT_>), grid, block, lds_bytes, stream, v, shapes, \
-                     starts, lc, at, S, M, D, L, Lq, P, CV, total_lanes, rec_stride, o)
+#define PCT_LAUNCH(VEC_, CVT_, PT_)                                                                            \
+  hipLaunchKernelGGL((msda_forward_kernel<T, VEC_, CVT_, PT_>), grid, block, lds_bytes, c.stream, v, c.shapes, \
+                     c.starts, lc, at, S, M, D, L, Lq, P, CV, total_lanes, rec_stride, o)
   if (vec) {
     if (D == 16 && P == 4) {
       PCT_LAUNCH(VECW, 16 / VECW, 4);
@@ -342,15 +242,9 @@ int launch_msda_forward(const void *value, const int64_t *shapes, const int64_t 
   return (int)hipGetLastError();
 }
 
-template int launch_msda_forward<float>(const void *, const int64_t *, const int64_t *, const void *,
-                                        const void *, int, int, int, int, int, int, int, void *, hipStream_t);
-template int launch_msda_forward<double>(const void *, const int64_t *, const int64_t *, const void *,
-                                         const void *, int, int, int, int, int, int, int, void *, hipStream_t);
-template int launch_msda_forward<half_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                            const void *, int, int, int, int, int, int, int, void *,
-                                            hipStream_t);
-template int launch_msda_forward<bf16_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                            const void *, int, int, int, int, int, int, int, void *,
-                                            hipStream_t);
+template int launch_msda_forward_generic<float>(const MsdaFwdCall &);
+template int launch_msda_forward_generic<double>(const MsdaFwdCall &);
+template int launch_msda_forward_generic<half_bits>(const MsdaFwdCall &);
+template int launch_msda_forward_generic<bf16_bits>(const MsdaFwdCall &);
 
 }  // namespace pct

@@ -34,17 +34,6 @@
 
 namespace pct {
 
-// Gather order of the levels (step ll -> level).  The finest level (the last one in PCTrans' pyramids) comes first; its
-// window is the largest, and the level that most often still fits beside it in the pool is the COARSEST one, so that
-// one goes second and the two middle levels share the next phase: with model-like offsets at the north-star shape
-// {finest, coarsest} + {the two middle levels} is two phases where finest-to-coarsest order needed three for every
-// fifth item (each phase costs a re-staging of the pool and two barriers).
-template <int L>
-__host__ __device__ constexpr int col_level_of_step(const int ll)
-{
-  return ll == 0 ? L - 1 : (ll == 1 ? 0 : L - ll);
-}
-
 // 256 threads per workgroup, 3 workgroups per CU, a ~50 KB LDS pool each (168 registers): the memory phases of one
 // workgroup (records, staging) overlap the gather of the others.
 constexpr int COL_BLOCK = 256, COL_WG_PER_CU = 3, COL_POOL_KB = 50;
@@ -948,31 +937,27 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
 
 // ---- launcher: returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel) ----------------------------
 // ref == nullptr: plain op; ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits).
-int launch_msda_forward_col(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                            const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                            hipStream_t stream, const float *ref, long long ref_batch_stride, bool planes)
+int launch_msda_forward_col(const MsdaFwdCall &c, bool planes)
 {
-  if ((((uintptr_t)value | (uintptr_t)out | (uintptr_t)loc | (uintptr_t)attn) & 15u)) return PCT_NOT_COVERED;
+  const int N = c.N, S = c.S, M = c.M, L = c.L;
+  const float *ref = c.ref;
+  if ((((uintptr_t)c.value | (uintptr_t)c.out | (uintptr_t)c.loc | (uintptr_t)c.attn) & 15u)) return PCT_NOT_COVERED;
   if (ref && (((uintptr_t)ref) & ((L % 2 == 0) ? 15u : 7u))) return PCT_NOT_COVERED;
-  if (ref && (L % 2 == 0) && (ref_batch_stride & 3)) return PCT_NOT_COVERED;
-  if (D != 16 || P != 4 || L < 3 || L > 5 || Lq != S || M < 1) return PCT_NOT_COVERED;
-  if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;   // item / record arithmetic headroom
-  if ((long long)S * M * L * P * 8 >= 0x7fffffffLL) return PCT_NOT_COVERED;               // 32-bit byte offsets inside an image, all tensors
-  if ((long long)S * M * D * 4 >= 0x7fffffffLL) return PCT_NOT_COVERED;                   // (0x80000000 is the out-of-range sentinel)
-  if (S >= (1 << 24) || M >= (1 << 16)) return PCT_NOT_COVERED;                           // 24-bit multiplies in the record index
+  if (ref && (L % 2 == 0) && (c.ref_batch_stride & 3)) return PCT_NOT_COVERED;
+  if (!msda_col_covers(c)) return PCT_NOT_COVERED;
   const int pool_px = COL_POOL_KB * 1024 / 64;
   const size_t lds = (size_t)pool_px * 64 + ((size_t)(COL_BLOCK / 64) * L * 2 + 4) * sizeof(unsigned);   // pool, boxes, queue words
   const dim3 grid(256 * COL_WG_PER_CU), block(COL_BLOCK);
-  unsigned *queue = win_queue_slot(stream);                                    // nullptr: static item stride
-  const float *v = static_cast<const float *>(value);
-  const float *lc = static_cast<const float *>(loc), *at = static_cast<const float *>(attn);
-  float *o = static_cast<float *>(out);
+  unsigned *queue = win_queue_slot(c.stream);                                  // nullptr: static item stride
+  const float *v = static_cast<const float *>(c.value);
+  const float *lc = static_cast<const float *>(c.loc), *at = static_cast<const float *>(c.attn);
+  float *o = static_cast<float *>(c.out);
 #define PCT_COL(L_, FU_, PP_)                                                                                           \
   do {                                                                                                                  \
     const hipError_t attr_rc = func_attr_per_device(reinterpret_cast<const void *>(&msda_forward_col_kernel<L_, FU_, PP_>)); \
     if (attr_rc != hipSuccess) return (int)attr_rc;                                                                     \
-    hipLaunchKernelGGL((msda_forward_col_kernel<L_, FU_, PP_>), grid, block, lds, stream, v, shapes, starts, lc, at, N, \
-                       S, M, pool_px, o, ref, ref_batch_stride, queue);                                                 \
+    hipLaunchKernelGGL((msda_forward_col_kernel<L_, FU_, PP_>), grid, block, lds, c.stream, v, c.shapes, c.starts, lc,  \
+                       at, N, S, M, pool_px, o, ref, c.ref_batch_stride, queue);                                        \
   } while (0)
 #define PCT_COL_L(FU_, PP_)               \
   do {                                    \

@@ -23,14 +23,6 @@
 
 namespace pct {
 
-// Gather order of the levels (step -> level): finest, coarsest, then the rest (as in msda_forward_col.hip: the coarsest
-// level is the one that most often still fits beside the finest in the pool, which saves a phase).
-template <int L>
-__host__ __device__ constexpr int col16_level_of_step(const int ll)
-{
-  return ll == 0 ? L - 1 : (ll == 1 ? 0 : L - ll);
-}
-
 template <typename T, int L, int P, bool FUSED, int BLOCK>
 __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
     const typename Traits<T>::store_t *__restrict__ value, const int64_t *__restrict__ shapes,
@@ -347,7 +339,7 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
       bool fresh = true;
 #pragma unroll
       for (int ll = 0; ll < L; ++ll) {
-        const int l = col16_level_of_step<L>(ll);
+        const int l = col_level_of_step<L>(ll);
         starts_phase[l] = false;
         if (wsize[l] > pool_use - 2 || big_map) {     // (or too large for the 16-bit box corners)
           phase_of[l] = -1;
@@ -588,7 +580,7 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
     if (have_n && !starts_phase[L - 1]) decode(item_n, b_n, m_n, qv_n);
     auto level_step = [&](auto llc) {
       constexpr int ll = decltype(llc)::value;
-      constexpr int l = col16_level_of_step<L>(ll);
+      constexpr int l = col_level_of_step<L>(ll);
       if (starts_phase[l]) {
         if (ll > 0) __syncthreads();
         stage_phase(phase_of[l]);
@@ -641,12 +633,12 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
 
 // ---- launcher: returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel) ----------------------------
 template <typename T>
-int launch_msda_forward_col16(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                              const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                              hipStream_t stream, const float *ref, long long ref_batch_stride)
+int launch_msda_forward_col16(const MsdaFwdCall &c)
 {
   using ST = typename Traits<T>::store_t;
-  if ((((uintptr_t)value | (uintptr_t)out | (uintptr_t)loc | (uintptr_t)attn) & 15u)) return PCT_NOT_COVERED;
+  const int N = c.N, S = c.S, M = c.M, D = c.D, L = c.L, Lq = c.Lq, P = c.P;
+  const float *ref = c.ref;
+  if ((((uintptr_t)c.value | (uintptr_t)c.out | (uintptr_t)c.loc | (uintptr_t)c.attn) & 15u)) return PCT_NOT_COVERED;
   if (ref && (((uintptr_t)ref) & 7u)) return PCT_NOT_COVERED;
   if (D != 16 || (P != 4 && P != 8) || L < 3 || L > 5 || Lq != S || M < 1) return PCT_NOT_COVERED;
   if ((long long)N * ((long long)S + 4096) * M >= 0x7fffffffLL) return PCT_NOT_COVERED;
@@ -655,13 +647,13 @@ int launch_msda_forward_col16(const void *value, const int64_t *shapes, const in
   const int pool_px = 50 * 1024 / 32;                                          // ~50 KB of LDS per workgroup, 3 per CU
   const size_t lds = (size_t)pool_px * 32 + ((size_t)(BLOCK / 64) * L * 2 + 4) * sizeof(unsigned);
   const dim3 grid(256 * 3), block(BLOCK);
-  unsigned *queue = win_queue_slot(stream);
-  const ST *v = static_cast<const ST *>(value);
-  const float *lc = static_cast<const float *>(loc), *at = static_cast<const float *>(attn);
-  ST *o = static_cast<ST *>(out);
-#define PCT_COL16(L_, P_, FU_)                                                                                          \
-  hipLaunchKernelGGL((msda_forward_col16_kernel<T, L_, P_, FU_, BLOCK>), grid, block, lds, stream, v, shapes, starts,  \
-                     lc, at, N, S, M, pool_px, o, ref, ref_batch_stride, queue)
+  unsigned *queue = win_queue_slot(c.stream);
+  const ST *v = static_cast<const ST *>(c.value);
+  const float *lc = static_cast<const float *>(c.loc), *at = static_cast<const float *>(c.attn);
+  ST *o = static_cast<ST *>(c.out);
+#define PCT_COL16(L_, P_, FU_)                                                                                         \
+  hipLaunchKernelGGL((msda_forward_col16_kernel<T, L_, P_, FU_, BLOCK>), grid, block, lds, c.stream, v, c.shapes,      \
+                     c.starts, lc, at, N, S, M, pool_px, o, ref, c.ref_batch_stride, queue)
 #define PCT_COL16_L(P_, FU_)                 \
   do {                                       \
     if (L == 3) PCT_COL16(3, P_, FU_);       \
@@ -680,11 +672,7 @@ int launch_msda_forward_col16(const void *value, const int64_t *shapes, const in
   return (int)hipGetLastError();
 }
 
-template int launch_msda_forward_col16<half_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                                  const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                                  const float *, long long);
-template int launch_msda_forward_col16<bf16_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                                  const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                                  const float *, long long);
+template int launch_msda_forward_col16<half_bits>(const MsdaFwdCall &);
+template int launch_msda_forward_col16<bf16_bits>(const MsdaFwdCall &);
 
 }  // namespace pct

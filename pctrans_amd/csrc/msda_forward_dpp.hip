@@ -223,14 +223,14 @@ __global__ __launch_bounds__(1024) void msda_forward_dpp_kernel(
 // ref == nullptr: plain op (loc = sampling locations, attn = attention weights);
 // ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits, ref = [N or 1, Lq, L, 2] reference points).
 template <typename T>
-int launch_msda_forward_dpp(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                            const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                            hipStream_t stream, const float *ref, long long ref_batch_stride)
+int launch_msda_forward_dpp(const MsdaFwdCall &c)
 {
   using ST = typename Traits<T>::store_t;
   constexpr int VEC = 16 / (int)sizeof(ST);
+  const int N = c.N, S = c.S, M = c.M, D = c.D, L = c.L, Lq = c.Lq, P = c.P;
+  const float *ref = c.ref;
   if (D != 16 || (P != 4 && P != 8)) return PCT_NOT_COVERED;
-  if ((((uintptr_t)value | (uintptr_t)out) & 15u) || (((uintptr_t)loc) & 7u) || (((uintptr_t)attn) & 3u)) return PCT_NOT_COVERED;
+  if ((((uintptr_t)c.value | (uintptr_t)c.out) & 15u) || (((uintptr_t)c.loc) & 7u) || (((uintptr_t)c.attn) & 3u)) return PCT_NOT_COVERED;
   const long long vbytes = (long long)N * S * M * D * (long long)sizeof(ST);
   if (vbytes >= 0x7fffffffLL) return PCT_NOT_COVERED;                          // 32-bit buffer offsets, OOB sentinel at 2^31
   constexpr int QL = 16 / VEC;
@@ -241,12 +241,12 @@ int launch_msda_forward_dpp(const void *value, const int64_t *shapes, const int6
   const long long nblk = qmajor ? ((long long)N * Lq + 64 / QL - 1) / (64 / QL) : (total_recs + per_blk - 1) / per_blk;
   if (nblk > 0x7fffffffLL) return PCT_NOT_COVERED;
   const dim3 grid((unsigned)nblk), block(qmajor ? 64 * M : DPP_BLOCK);
-  const ST *v = static_cast<const ST *>(value);
-  const float *lc = static_cast<const float *>(loc), *at = static_cast<const float *>(attn);
-  ST *o = static_cast<ST *>(out);
-#define PCT_DPP(P_, QM_, FU_)                                                                                      \
-  hipLaunchKernelGGL((msda_forward_dpp_kernel<T, 16, P_, QM_, FU_>), grid, block, 0, stream, v, shapes, starts, lc, \
-                     at, S, M, L, Lq, total_recs, (unsigned)vbytes, o, ref, ref_batch_stride)
+  const ST *v = static_cast<const ST *>(c.value);
+  const float *lc = static_cast<const float *>(c.loc), *at = static_cast<const float *>(c.attn);
+  ST *o = static_cast<ST *>(c.out);
+#define PCT_DPP(P_, QM_, FU_)                                                                                       \
+  hipLaunchKernelGGL((msda_forward_dpp_kernel<T, 16, P_, QM_, FU_>), grid, block, 0, c.stream, v, c.shapes, c.starts, \
+                     lc, at, S, M, L, Lq, total_recs, (unsigned)vbytes, o, ref, c.ref_batch_stride)
   if (ref) {
     if (P == 4 && qmajor) PCT_DPP(4, true, true);
     else if (P == 4) PCT_DPP(4, false, true);
@@ -262,14 +262,8 @@ int launch_msda_forward_dpp(const void *value, const int64_t *shapes, const int6
   return (int)hipGetLastError();
 }
 
-template int launch_msda_forward_dpp<float>(const void *, const int64_t *, const int64_t *, const void *,
-                                            const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                            const float *, long long);
-template int launch_msda_forward_dpp<half_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                                const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                                const float *, long long);
-template int launch_msda_forward_dpp<bf16_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                                const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                                const float *, long long);
+template int launch_msda_forward_dpp<float>(const MsdaFwdCall &);
+template int launch_msda_forward_dpp<half_bits>(const MsdaFwdCall &);
+template int launch_msda_forward_dpp<bf16_bits>(const MsdaFwdCall &);
 
 }  // namespace pct

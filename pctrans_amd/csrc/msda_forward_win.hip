@@ -570,13 +570,13 @@ int prepare_win_queue_device()
 // ---- launcher: returns PCT_NOT_COVERED when this geometry is not covered (caller uses another kernel) ----------------------
 // ref == nullptr: plain op; ref != nullptr: fused front-end (loc = raw offsets, attn = raw logits).
 template <typename T>
-int launch_msda_forward_win(const void *value, const int64_t *shapes, const int64_t *starts, const void *loc,
-                            const void *attn, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                            hipStream_t stream, const float *ref, long long ref_batch_stride)
+int launch_msda_forward_win(const MsdaFwdCall &c)
 {
   using ST = typename Traits<T>::store_t;
   constexpr int VEC = 16 / (int)sizeof(ST);
-  if ((((uintptr_t)value | (uintptr_t)out) & 15u) || (((uintptr_t)loc) & 7u) || (((uintptr_t)attn) & 3u)) return PCT_NOT_COVERED;
+  const int N = c.N, S = c.S, M = c.M, D = c.D, L = c.L, Lq = c.Lq, P = c.P;
+  const float *ref = c.ref;
+  if ((((uintptr_t)c.value | (uintptr_t)c.out) & 15u) || (((uintptr_t)c.loc) & 7u) || (((uintptr_t)c.attn) & 3u)) return PCT_NOT_COVERED;
   if (ref && (((uintptr_t)ref) & 7u)) return PCT_NOT_COVERED;
   if (D != 16 || (P != 4 && P != 8) || L < 3 || L > 5) return PCT_NOT_COVERED;
   if ((long long)N * Lq * M < 32768) return PCT_NOT_COVERED;                  // too small to fill a persistent grid
@@ -588,13 +588,13 @@ int launch_msda_forward_win(const void *value, const int64_t *shapes, const int6
   const size_t lds = (size_t)pool_px * QL * 16 + 2 * (WIN_BLOCK / 64) * WIN_MAXL * 2 * sizeof(unsigned) + 16;
   const int pyramid = Lq == S ? 1 : 0;
   const dim3 grid(256 * 3), block(WIN_BLOCK);
-  unsigned *queue = win_queue_slot(stream);                        // nullptr: static item stride
-  const ST *v = static_cast<const ST *>(value);
-  const float *lc = static_cast<const float *>(loc), *at = static_cast<const float *>(attn);
-  ST *o = static_cast<ST *>(out);
-#define PCT_WIN(L_, P_, NS_, FU_)                                                                                     \
-  hipLaunchKernelGGL((msda_forward_win_kernel<T, 16, L_, P_, NS_, FU_>), grid, block, lds, stream, v, shapes, starts, \
-                     lc, at, N, S, M, Lq, pyramid, pool_px, o, ref, ref_batch_stride, queue)
+  unsigned *queue = win_queue_slot(c.stream);                      // nullptr: static item stride
+  const ST *v = static_cast<const ST *>(c.value);
+  const float *lc = static_cast<const float *>(c.loc), *at = static_cast<const float *>(c.attn);
+  ST *o = static_cast<ST *>(c.out);
+#define PCT_WIN(L_, P_, NS_, FU_)                                                                                   \
+  hipLaunchKernelGGL((msda_forward_win_kernel<T, 16, L_, P_, NS_, FU_>), grid, block, lds, c.stream, v, c.shapes,   \
+                     c.starts, lc, at, N, S, M, Lq, pyramid, pool_px, o, ref, c.ref_batch_stride, queue)
 #define PCT_WIN_L(P_, NS_, FU_)             \
   do {                                      \
     if (L == 3) PCT_WIN(3, P_, NS_, FU_);   \
@@ -614,14 +614,8 @@ int launch_msda_forward_win(const void *value, const int64_t *shapes, const int6
   return (int)hipGetLastError();
 }
 
-template int launch_msda_forward_win<float>(const void *, const int64_t *, const int64_t *, const void *,
-                                            const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                            const float *, long long);
-template int launch_msda_forward_win<half_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                                const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                                const float *, long long);
-template int launch_msda_forward_win<bf16_bits>(const void *, const int64_t *, const int64_t *, const void *,
-                                                const void *, int, int, int, int, int, int, int, void *, hipStream_t,
-                                                const float *, long long);
+template int launch_msda_forward_win<float>(const MsdaFwdCall &);
+template int launch_msda_forward_win<half_bits>(const MsdaFwdCall &);
+template int launch_msda_forward_win<bf16_bits>(const MsdaFwdCall &);
 
 }  // namespace pct
