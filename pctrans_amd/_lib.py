@@ -115,6 +115,14 @@ ATTN_TRAIN_SYMBOLS = {
                                          "tests/test_attention_train_gpu.py"),
 }
 
+# Entry points of the mask side of the query-contrast loss (include/pctrans_hip_reid.h; pctrans_amd/reid_dice.py, reached with
+# MultiScaleMaskedTransformerDecoder.reid_dice = "hip").  A table of its own, as the attention's: name -> (argtypes, restype,
+# the test module that checks the entry against float64)
+REID_SYMBOLS = {
+    "pct_reid_dice_rows_forward_f32": ([_vp] * 3 + [_i] * 5 + [_vp] * 5, _i, "tests/test_reid_dice_gpu.py"),
+    "pct_reid_dice_rows_backward_f32": ([_vp] * 6 + [_i] * 5 + [_vp] * 3, _i, "tests/test_reid_dice_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -133,7 +141,7 @@ def lib():
     l = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
-            + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items())]:
+            + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

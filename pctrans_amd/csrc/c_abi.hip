@@ -546,6 +546,34 @@ int pct_discriminative_loss_backward_f32(const float *embedding, const int32_t *
                                        grad_embedding, static_cast<hipStream_t>(stream));
 }
 
+int pct_reid_dice_rows_forward_f32(const float *logits, const int32_t *image_start, const int32_t *key, int batch, int num_query,
+                                   int height, int width, int num_rows, void *workspace, float *sums, float *dice, int32_t *status,
+                                   void *stream)
+{
+  if (batch <= 0 || num_query <= 0 || height <= 0 || width <= 0 || num_rows < 0) return PCT_ERR_BAD_ARG;
+  if (num_rows == 0) return PCT_OK;
+  if (!logits || !image_start || !key || !workspace || !sums || !dice || !status) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)logits | (uintptr_t)image_start | (uintptr_t)key | (uintptr_t)sums | (uintptr_t)dice | (uintptr_t)status) & 3u) ||
+      ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_reid_dice_forward(logits, image_start, key, batch, num_query, height, width, num_rows, workspace, sums, dice,
+                                       status, static_cast<hipStream_t>(stream));
+}
+
+int pct_reid_dice_rows_backward_f32(const float *logits, const int32_t *image_start, const int32_t *key, const float *dice,
+                                    const float *sums, const float *grad_dice, int batch, int num_query, int height, int width,
+                                    int num_rows, void *workspace, float *grad_logits, void *stream)
+{
+  if (batch <= 0 || num_query <= 0 || height <= 0 || width <= 0 || num_rows < 0) return PCT_ERR_BAD_ARG;
+  if (!logits || !image_start || !workspace || !grad_logits) return PCT_ERR_BAD_ARG;
+  if (num_rows > 0 && (!key || !dice || !sums || !grad_dice)) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)logits | (uintptr_t)image_start | (uintptr_t)key | (uintptr_t)dice | (uintptr_t)sums | (uintptr_t)grad_dice |
+        (uintptr_t)grad_logits) & 3u) || ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_reid_dice_backward(logits, image_start, key, dice, sums, grad_dice, batch, num_query, height, width, num_rows,
+                                        workspace, grad_logits, static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

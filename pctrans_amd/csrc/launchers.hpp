@@ -212,6 +212,14 @@ int launch_emb_loss_forward(const float *emb, const int *labels, int B, int E, i
 int launch_emb_loss_backward(const float *emb, const int *labels, const float *table, const float *grad_out, int B, int E, int h,
                              int w, int L, float delta_v, float *grad_emb, hipStream_t stream);
 
+// ---- mask side of the query-contrast loss (reid_dice.hip; include/pctrans_hip_reid.h): rows of the pairwise sigmoid dice and
+// their backward.  PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover ----------------------------
+int launch_reid_dice_forward(const float *logits, const int *image_start, const int *key, int N, int Q, int h, int w, int I,
+                             void *workspace, float *sums, float *dice, int *status, hipStream_t stream);
+int launch_reid_dice_backward(const float *logits, const int *image_start, const int *key, const float *dice, const float *sums,
+                              const float *grad_dice, int N, int Q, int h, int w, int I, void *workspace, float *grad_logits,
+                              hipStream_t stream);
+
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
 int launch_instance_masks(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, unsigned *bits,

@@ -34,6 +34,7 @@ from torch.nn import functional as F
 from .. import attention_train
 from .. import dynamic_mask_head as dmh
 from .. import fused_ops
+from .. import reid_dice
 from ..layers import CachedLinear, Conv2d, c2_xavier_fill, get_norm
 from .attention import MultiheadAttention
 from .position_encoding import PositionEmbeddingSine
@@ -380,6 +381,9 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         # training path of the dynamic mask head: "torch" (differentiable batched formulation) or "hip" (the fp32 forward
         # kernel with its HIP backward, where its conditions hold).  A plain attribute; process default from PCT_DMH_TRAIN
         self.dmh_train = dmh.train_default()
+        # mask side of the query-contrast loss: "torch" (dice_for of all queries, then the items' rows) or "hip" (the items' rows
+        # alone with a HIP backward, pctrans_amd/reid_dice.py).  A plain attribute; process default from PCT_REID_DICE
+        self.reid_dice = reid_dice.default()
         self.mask_out_stride = 4
         self.rel_coord = rel_coord
         ch = self.dynamic_mask_channels
@@ -446,7 +450,11 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             else:
                 indices_list = [criterion.matcher({"pred_masks": pm}, targets) for pm in predictions_mask]
             from .query_contrast import query_contrast_items
-            contrast_items_query, contrast_items_mask = query_contrast_items(output, predictions_mask[-1], indices_list[-1])
+            if self.reid_dice not in ("torch", "hip"):
+                raise ValueError("MultiScaleMaskedTransformerDecoder.reid_dice must be 'torch' or 'hip', got %r"
+                                 % (self.reid_dice,))
+            contrast_items_query, contrast_items_mask = query_contrast_items(output, predictions_mask[-1], indices_list[-1],
+                                                                             mask_dice=self.reid_dice)
 
         out = {
             "pred_masks": predictions_mask[-1],

@@ -125,18 +125,45 @@ def select_pos_neg_query(query, emb_dist, pos_indices, _plan_cache=None):
     return items
 
 
-def select_pos_neg_mask(query_mask, emb_dist, pos_indices, _plan_cache=None):
-    """query_mask [N, Q, H, W] mask logits."""
+def _dice_rows_hip(query_mask, plan):
+    """The [I, Q] dice rows of the plan's items from the HIP kernels (pctrans_amd/reid_dice.py), or None where they do not
+    cover the call.  The plan is in image order: image_start is built from it on the host."""
+    from .. import reid_dice
+    if not torch.is_tensor(query_mask) or query_mask.dim() != 4:
+        return None
+    counts = [0] * query_mask.shape[0]
+    for p in plan:
+        counts[p[0]] += 1
+    if not reid_dice.supported(query_mask, counts):
+        return None
+    starts = [0]
+    for c in counts:
+        starts.append(starts[-1] + c)
+    dev = query_mask.device
+    image_start = torch.tensor(starts, dtype=torch.int32).to(dev)
+    key = torch.tensor([p[1] for p in plan], dtype=torch.int32).to(dev)
+    return reid_dice.dice_rows(query_mask, image_start, key)
+
+
+def select_pos_neg_mask(query_mask, emb_dist, pos_indices, _plan_cache=None, mask_dice="torch"):
+    """query_mask [N, Q, H, W] mask logits.  mask_dice: "torch" (dice_for of all images, then the items' rows) or "hip" (the
+    items' rows alone from pctrans_amd/reid_dice.py where it covers the call, the torch chain otherwise)."""
+    if mask_dice not in ("torch", "hip"):
+        raise ValueError("mask_dice must be 'torch' or 'hip', got %r" % (mask_dice,))
     plan = _plan(emb_dist, pos_indices) if _plan_cache is None else _plan_cache
     items = ContrastItems()
     if not plan:
         return items
     dev = query_mask.device
     img, key, order, n_pos = _index_tensors(plan, dev)
-    x = query_mask.flatten(2).sigmoid()                                                         # dice_for, all images at once
-    s = x.sum(-1)
-    dice = (2 * torch.bmm(x, x.transpose(1, 2)) + 1) / (s[:, :, None] + s[:, None, :] + 1)     # [N, Q, Q]
-    contrast = dice[img[:, None], key[:, None], order]                                          # [I, Q - 1]
+    rows = _dice_rows_hip(query_mask, plan) if mask_dice == "hip" else None
+    if rows is not None:
+        contrast = rows.gather(1, order)                                                        # [I, Q - 1]
+    else:
+        x = query_mask.flatten(2).sigmoid()                                                     # dice_for, all images at once
+        s = x.sum(-1)
+        dice = (2 * torch.bmm(x, x.transpose(1, 2)) + 1) / (s[:, :, None] + s[:, None, :] + 1) # [N, Q, Q]
+        contrast = dice[img[:, None], key[:, None], order]                                      # [I, Q - 1]
     label = (torch.arange(order.shape[1], device=dev)[None, :] < n_pos[:, None]).to(query_mask.dtype)
     items.batched = {"contrast": contrast, "label": label, "n_pos": n_pos}
     for i in range(len(plan)):
@@ -144,10 +171,11 @@ def select_pos_neg_mask(query_mask, emb_dist, pos_indices, _plan_cache=None):
     return items
 
 
-def query_contrast_items(output, outputs_mask, indices):
-    """Last-layer hook of the decoder (:618-622): output [Q, N, C] query embeddings, outputs_mask [N, Q, H, W]."""
+def query_contrast_items(output, outputs_mask, indices, mask_dice="torch"):
+    """Last-layer hook of the decoder (:618-622): output [Q, N, C] query embeddings, outputs_mask [N, Q, H, W]; mask_dice as
+    select_pos_neg_mask's."""
     q = output.permute(1, 0, 2)
     emb_dist = F.cosine_similarity(q.unsqueeze(2), q.unsqueeze(1), dim=-1)          # [N, Q, Q]
     plan = _plan(emb_dist, indices)
     return (select_pos_neg_query(output, emb_dist, indices, _plan_cache=plan),
-            select_pos_neg_mask(outputs_mask, emb_dist, indices, _plan_cache=plan))
+            select_pos_neg_mask(outputs_mask, emb_dist, indices, _plan_cache=plan, mask_dice=mask_dice))

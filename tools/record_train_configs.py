@@ -69,6 +69,8 @@ def build(c):
         model.criterion.matcher.match_cost = "hip"
     if c.get("hip_emb_loss"):
         model.criterion.emb_loss = "hip"
+    if c.get("hip_reid_dice"):
+        model.sem_seg_head.predictor.reid_dice = "hip"
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -105,6 +107,8 @@ def selected_configs(argv):
         configs.update({k + " + HIP embedding loss": dict(v, hip_emb_loss=True) for k, v in list(configs.items())})
     if "--hip-attn-train" in argv:          # and every selected config again with the cross-attention's HIP training path
         configs.update({k + " + HIP attention": dict(v, hip_attn_train=True) for k, v in list(configs.items())})
+    if "--hip-reid-dice" in argv:           # and every selected config again with the re-id mask dice rows from the HIP kernels
+        configs.update({k + " + HIP re-id dice": dict(v, hip_reid_dice=True) for k, v in list(configs.items())})
     return configs
 
 
@@ -157,7 +161,7 @@ def main():
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
     flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select",
-                                                "--hip-match-cost", "--hip-emb-loss", "--hip-attn-train")]
+                                                "--hip-match-cost", "--hip-emb-loss", "--hip-attn-train", "--hip-reid-dice")]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
