@@ -123,6 +123,15 @@ REID_SYMBOLS = {
     "pct_reid_dice_rows_backward_f32": ([_vp] * 6 + [_i] * 5 + [_vp] * 3, _i, "tests/test_reid_dice_gpu.py"),
 }
 
+# Entry points of the instance targets from label maps (include/pctrans_hip_targets.h; pctrans_amd/targets.py:
+# prepare_instance_targets, MaskFormer.prepare_instance_targets).  A table of its own, as the re-id loss's: name -> (argtypes,
+# restype, the test module that checks the entry -- against the torch formulation: the outputs are exact)
+TARGETS_SYMBOLS = {
+    "pct_instance_targets_census": ([_vp] + [_i] * 5 + [_vp] * 7, _i, "tests/test_targets_gpu.py"),
+    "pct_instance_targets_planes": ([_vp] + [_i] * 4 + [_vp, _vp, ctypes.c_longlong, _i] + [_vp] * 5, _i,
+                                    "tests/test_targets_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -141,7 +150,7 @@ def lib():
     l = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
-            + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items())]:
+            + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

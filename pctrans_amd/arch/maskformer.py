@@ -23,6 +23,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import postprocess as post
+from .. import targets as _targets
 from ..loss import Point_HungarianMatcher, SetCriterion
 from ..meta_arch.mask_former_head import MaskFormerHead
 
@@ -150,6 +151,16 @@ class MaskFormer(nn.Module):
                     size_divisibility=mf.SIZE_DIVISIBILITY, sem_seg_postprocess_before_inference=True,
                     semantic_on=mf.TEST.SEMANTIC_ON, instance_on=mf.TEST.INSTANCE_ON, panoptic_on=mf.TEST.PANOPTIC_ON,
                     dataset_name=cfg.DATASET.DATA_TYPE)
+
+    def prepare_instance_targets(self, label_maps, instance_discriminative=False, ignore_label=0):
+        """The training targets of `forward(volume, targets, True)` from the loader's label maps [N, H, W]: the reference
+        trainer's prepare_intance_targets as one call (pctrans_amd/targets.py), with the number of position points, the
+        semantic loss and the device taken from this model.  On the device kernels by default (PCT_TARGETS); that path makes
+        one small device -> host copy, so the call does not belong inside a graph capture."""
+        predictor = self.sem_seg_head.predictor
+        return _targets.prepare_instance_targets(
+            label_maps, points_num=predictor.points_num, semantic_loss_on=predictor.sem_loss_on,
+            instance_discriminative=instance_discriminative, ignore_label=ignore_label, device=next(self.parameters()).device)
 
     def forward(self, volume, targets=None, train=False):
         features = self.backbone(volume)

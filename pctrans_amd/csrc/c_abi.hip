@@ -574,6 +574,35 @@ int pct_reid_dice_rows_backward_f32(const float *logits, const int32_t *image_st
                                         workspace, grad_logits, static_cast<hipStream_t>(stream));
 }
 
+int pct_instance_targets_census(const void *labels, int dtype, int batch, int height, int width, int ignore_label, void *workspace,
+                                int32_t *ids, int32_t *pixels, float *centres, int32_t *num, int32_t *status, void *stream)
+{
+  if (batch <= 0 || height <= 0 || width <= 0) return PCT_ERR_BAD_ARG;
+  if (!labels || !workspace || !ids || !pixels || !centres || !num || !status) return PCT_ERR_BAD_ARG;
+  static const uintptr_t elem[5] = {1, 2, 4, 8, 4};
+  if (dtype < 0 || dtype > 4) return PCT_ERR_UNSUPPORTED;
+  if (((uintptr_t)labels & (elem[dtype] - 1)) || (((uintptr_t)ids | (uintptr_t)pixels | (uintptr_t)num | (uintptr_t)status) & 3u) ||
+      ((uintptr_t)centres & 7u) || ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_instance_targets_census(labels, dtype, batch, height, width, ignore_label, workspace, ids, pixels, centres, num,
+                                             status, static_cast<hipStream_t>(stream));
+}
+
+int pct_instance_targets_planes(const void *labels, int dtype, int batch, int height, int width, const void *workspace,
+                                const int32_t *counts, long long total_planes, int max_count, int32_t *starts, uint8_t *masks,
+                                float *planes, uint8_t *fg, void *stream)
+{
+  if (batch <= 0 || height <= 0 || width <= 0 || total_planes <= 0 || max_count <= 0) return PCT_ERR_BAD_ARG;
+  if (!labels || !workspace || !counts || !starts || !masks) return PCT_ERR_BAD_ARG;
+  static const uintptr_t elem[5] = {1, 2, 4, 8, 4};
+  if (dtype < 0 || dtype > 4 || max_count > PCT_TARGETS_MAX_INSTANCES) return PCT_ERR_UNSUPPORTED;
+  if (((uintptr_t)labels & (elem[dtype] - 1)) || (((uintptr_t)counts | (uintptr_t)starts) & 3u) ||
+      (((uintptr_t)workspace | (uintptr_t)masks | (uintptr_t)planes | (uintptr_t)fg) & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_instance_targets_planes(labels, dtype, batch, height, width, workspace, counts, total_planes, max_count, starts,
+                                             masks, planes, fg, static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

@@ -220,6 +220,15 @@ int launch_reid_dice_backward(const float *logits, const int *image_start, const
                               const float *grad_dice, int N, int Q, int h, int w, int I, void *workspace, float *grad_logits,
                               hipStream_t stream);
 
+// ---- instance targets from label maps (instance_targets.hip; include/pctrans_hip_targets.h).  dtype: 0 uint8, 1 int16, 2 int32,
+// 3 int64, 4 float32.  PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover -------------------------
+int instance_targets_geometry_status(int dtype, int N, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
+int launch_instance_targets_census(const void *labels, int dtype, int N, int H, int W, int ignore_label, void *workspace, int *ids,
+                                   int *pixels, float *centres, int *num, int *status, hipStream_t stream);
+int launch_instance_targets_planes(const void *labels, int dtype, int N, int H, int W, const void *workspace, const int *counts,
+                                   long long total_planes, int max_count, int *starts, uint8_t *masks, float *planes, uint8_t *fg,
+                                   hipStream_t stream);
+
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
 int launch_instance_masks(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, unsigned *bits,

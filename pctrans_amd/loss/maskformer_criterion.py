@@ -14,6 +14,7 @@ from torch import nn
 
 from .. import embedding_loss as _embedding_loss
 from .. import point_loss as _point_loss
+from .. import targets as _targets
 from .point_features import get_uncertain_point_coords_with_randomness, point_sample
 
 
@@ -157,13 +158,16 @@ class SetCriterion(nn.Module):
 
     def _hip_target_planes(self, targets, like):
         """The images' target masks as one fp32 [sum G, Ht, Wt] tensor and each image's first plane, or None when the masks
-        differ in size.  Kept for the calls that follow with the same masks (the ten predictions of a step)."""
+        differ in size.  Kept for the calls that follow with the same masks (the ten predictions of a step).  A list that carries
+        its planes (targets.TargetList from the device path) hands them over: nothing is concatenated or converted."""
         masks = [t["masks"] for t in targets]
         if not masks or len({tuple(m.shape[-2:]) for m in masks}) != 1 or any(m.dim() != 3 or m.device != like.device for m in masks):
             return None
         key = tuple((m.data_ptr(), m._version, tuple(m.shape), m.dtype) for m in masks)
         if self._target_planes is None or self._target_planes[0] != key:
-            planes = torch.cat(masks).to(torch.float32).contiguous()
+            planes = _targets.handed_planes(targets, masks, like)
+            if planes is None:
+                planes = torch.cat(masks).to(torch.float32).contiguous()
             starts = [0]
             for m in masks[:-1]:
                 starts.append(starts[-1] + m.shape[0])
@@ -238,7 +242,10 @@ class SetCriterion(nn.Module):
         planes, starts = got
         key = self._target_planes[0]
         if self._emb_plane_index is None or self._emb_plane_index[0] != key:
-            vec = torch.tensor([starts, counts], dtype=torch.int32).to(emb.device, non_blocking=True)
+            if getattr(targets, "planes", None) is planes:       # handed over with their index vectors
+                vec = (targets.starts, targets.counts)
+            else:
+                vec = torch.tensor([starts, counts], dtype=torch.int32).to(emb.device, non_blocking=True)
             self._emb_plane_index = (key, vec[0], vec[1])
         labels = _embedding_loss.instance_label_map(planes, self._emb_plane_index[1], self._emb_plane_index[2], emb.shape[2:])
         return {"loss_emb": _embedding_loss.discriminative_loss(emb, labels, max(counts), alpha=alpha, beta=beta, gama=gama)}

@@ -12,6 +12,7 @@ from scipy.optimize import linear_sum_assignment
 from torch import nn
 
 from .. import point_loss as _point_loss
+from .. import targets as _targets
 from .point_features import point_sample
 
 
@@ -52,16 +53,21 @@ class Point_HungarianMatcher(nn.Module):
     def _match_target_planes(self, targets, like):
         """The images' target masks as one fp32 [sum G, Ht, Wt] tensor with each image's first plane and count as int32 device
         vectors, or None when the masks differ in size or device.  Kept for the calls that follow with the same masks (the ten
-        predictions of a step): keyed as SetCriterion._hip_target_planes."""
+        predictions of a step): keyed as SetCriterion._hip_target_planes.  A list that carries its planes (targets.TargetList from
+        the device path) hands them over with its index vectors: nothing is concatenated, converted or copied."""
         masks = [t["masks"] for t in targets]
         if not masks or len({tuple(m.shape[-2:]) for m in masks}) != 1 or any(m.dim() != 3 or m.device != like.device for m in masks):
             return None
         key = tuple((m.data_ptr(), m._version, tuple(m.shape), m.dtype) for m in masks)
         if self._target_planes is None or self._target_planes[0] != key:
-            planes = torch.cat(masks).to(torch.float32).contiguous()
-            counts = [int(m.shape[0]) for m in masks]
-            starts = [sum(counts[:b]) for b in range(len(counts))]
-            vec = torch.tensor([starts, counts], dtype=torch.int32).to(like.device, non_blocking=True)
+            planes = _targets.handed_planes(targets, masks, like)
+            if planes is not None:
+                vec = (targets.starts, targets.counts)
+            else:
+                planes = torch.cat(masks).to(torch.float32).contiguous()
+                counts = [int(m.shape[0]) for m in masks]
+                starts = [sum(counts[:b]) for b in range(len(counts))]
+                vec = torch.tensor([starts, counts], dtype=torch.int32).to(like.device, non_blocking=True)
             self._target_planes = (key, planes, vec[0], vec[1], masks)    # (the masks: their addresses stay theirs while kept)
         return self._target_planes[1:4]
 

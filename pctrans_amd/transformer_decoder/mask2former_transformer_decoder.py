@@ -399,6 +399,7 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         nn.init.constant_(self.mask_head.bias, 0)
 
         self.sem_loss_on = sem_loss_on
+        self.points_num = points_num                     # what MaskFormer.prepare_instance_targets builds its targets for
         if self.sem_loss_on:
             conv_block = conv_with_kaiming_uniform(norm, activation=True)
             self.seg_head = nn.Sequential(conv_block(hidden_dim, hidden_dim, kernel_size=3, stride=1),
