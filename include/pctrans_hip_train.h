@@ -140,6 +140,54 @@ PCT_API int pct_point_match_cost_f32(const float *pred, int batch, int num_query
                                      const int32_t *tgt_count, int max_targets, const float *coords, int num_points,
                                      float cost_mask, float cost_dice, void *workspace, float *cost, void *stream);
 
+/* ---- the same three stages for several prediction heads in one launch -------------------------------------------------------
+ * A training step supervises the decoder's last layer and its auxiliary heads against the same targets; their predictions are
+ * separate tensors of one geometry.  The three entries below give the selection, the loss forward and the matcher costs a head
+ * dimension: one launch (two for the costs) covers every (head, pair) or (head, image), the workgroup taking its head from a grid
+ * dimension.  `preds` is a HOST array of num_heads device pointers, each to fp32 planes [num_pred_planes, height, width] (the
+ * costs: [batch * num_query, height, width]) of the one common geometry.  The call copies the pointers into a structure that is
+ * passed to the kernel by value: nothing is uploaded, allocated or synchronised, and the array may be reused at once.
+ * Every per-head array is the single-head array with a leading [num_heads] dimension; the target planes, tgt_start and
+ * tgt_count are shared by all heads.
+ * Bit identity.  The workgroups run the code of their single-head siblings (the same device functions, on the head's pointer
+ * and the head's slices): for every head the entry writes exactly the bits the single-head entry writes when called with
+ * preds[h] and the slices [h] of the arrays -- the NaN rows of an index outside the planes and the zero columns past an image's
+ * target count included.
+ * Status: num_heads < 0 or > PCT_POINT_MAX_HEADS, preds == NULL with num_heads > 0, or a NULL entry PCT_ERR_BAD_ARG; num_heads == 0
+ * PCT_OK with nothing launched; otherwise the rules of the single-head entry, the alignment of every entry included.
+ *
+ * Selection: pct_point_select_uncertain_f32 per head.  src_index [num_heads, num_pairs] or NULL (the identity in every head),
+ * cand_coords [num_heads, num_pairs, num_cand, 2], out_coords [num_heads, num_pairs, out_row_points, 2], out_index
+ * [num_heads, num_pairs, num_keep] or NULL.  The same three kernel classes by num_cand (16, 40 or 64 keys per thread).
+ *
+ * Loss forward: pct_point_mask_loss_forward_f32 per head.  src_index, tgt_index [num_heads, num_pairs] (each may be NULL: the
+ * identity in every head), coords [num_heads, num_pairs, num_points, 2], x, t [num_heads, num_pairs, num_points], sums
+ * [num_heads, num_pairs, 4].
+ * The loss backward needs no entry of its own: pct_point_mask_loss_backward_f32 never reads the prediction, so called with
+ * num_pairs = num_heads * num_pairs on the stacked x, t, coords and alpha, beta, gamma [num_heads * num_pairs] it IS the backward
+ * of all heads in one launch, grad_planes [num_heads * num_pairs, height, width] compact.
+ *
+ * Matcher costs: pct_point_match_cost_f32 per head.  coords [num_heads, batch, num_points, 2], cost
+ * [num_heads, batch, num_query, max_targets].  The points are chunked as the single-head call chunks them for `batch` images
+ * (not for num_heads * batch), so every sum runs in the single call's order.  `workspace`: caller-owned, 16-byte aligned, at least
+ *   num_heads * (4 * batch * chunks * (2 Qp Gp + Qp + Gp)) bytes, with Qp, Gp and chunks of pct_point_match_cost_f32 for `batch`;
+ * head h owns the h-th part.  Covered: what the single-head entry covers, and num_heads * batch <= 65535. */
+#define PCT_POINT_MAX_HEADS 16
+PCT_API int pct_point_select_uncertain_many_f32(const float *const *preds, int num_heads, const int32_t *src_index,
+                                                int num_pred_planes, int height, int width, const float *cand_coords,
+                                                int num_pairs, int num_cand, int num_keep, float *out_coords, int out_row_points,
+                                                int32_t *out_index, void *stream);
+PCT_API int pct_point_mask_loss_forward_many_f32(const float *const *preds, int num_heads, const int32_t *src_index,
+                                                 int num_pred_planes, int height, int width, const float *tgt,
+                                                 const int32_t *tgt_index, int num_tgt_planes, int tgt_height, int tgt_width,
+                                                 const float *coords, int num_pairs, int num_points, float *x, float *t,
+                                                 float *sums, void *stream);
+PCT_API int pct_point_match_cost_many_f32(const float *const *preds, int num_heads, int batch, int num_query, int height, int width,
+                                          const float *tgt, int num_tgt_planes, int tgt_height, int tgt_width,
+                                          const int32_t *tgt_start, const int32_t *tgt_count, int max_targets, const float *coords,
+                                          int num_points, float cost_mask, float cost_dice, void *workspace, float *cost,
+                                          void *stream);
+
 /* ---- pixel-embedding loss (SetCriterion.loss_embedding: the label map and the reference's discriminative_loss,
  * loss/loss.py:297-355) -----------------------------------------------------------------------------------------------------
  * Label map.  planes [num_planes, plane_height, plane_width] fp32 are the images' target masks concatenated, image b owning the

@@ -67,6 +67,13 @@ OPT_IN_SYMBOLS = {
                                        "tests/test_point_select_gpu.py"),
     "pct_point_match_cost_f32": ([_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float, ctypes.c_float,
                                   _vp, _vp, _vp], _i, "tests/test_match_cost_gpu.py"),
+    # several prediction heads in one launch: the first argument is a host array of device pointers (`head_table`)
+    "pct_point_select_uncertain_many_f32": ([_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp], _i,
+                                            "tests/test_loss_heads_gpu.py"),
+    "pct_point_mask_loss_forward_many_f32": ([_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp], _i,
+                                             "tests/test_loss_heads_gpu.py"),
+    "pct_point_match_cost_many_f32": ([_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, ctypes.c_float,
+                                       ctypes.c_float, _vp, _vp, _vp], _i, "tests/test_loss_heads_gpu.py"),
     "pct_instance_label_map_f32": ([_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp], _i, "tests/test_embedding_loss_gpu.py"),
     "pct_discriminative_loss_forward_f32": ([_vp, _vp] + [_i] * 5 + [ctypes.c_float] * 5 + [_vp] * 5, _i,
                                             "tests/test_embedding_loss_gpu.py"),

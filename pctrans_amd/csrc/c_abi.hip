@@ -510,6 +510,75 @@ int pct_point_match_cost_f32(const float *pred, int batch, int num_query, int he
                                       static_cast<hipStream_t>(stream));
 }
 
+// The head table of the *_many entries: PCT_OK when 0 < num_heads <= PCT_POINT_MAX_HEADS entries are all present and 4-byte
+// aligned.  num_heads == 0 is the callers' own early return.
+static int point_heads_status(const float *const *preds, int num_heads)
+{
+  if (num_heads < 0 || num_heads > PCT_POINT_MAX_HEADS || !preds) return PCT_ERR_BAD_ARG;
+  uintptr_t bits = 0;
+  for (int h = 0; h < num_heads; ++h) {
+    if (!preds[h]) return PCT_ERR_BAD_ARG;
+    bits |= (uintptr_t)preds[h];
+  }
+  return (bits & 3u) ? PCT_ERR_ALIGNMENT : PCT_OK;
+}
+
+int pct_point_select_uncertain_many_f32(const float *const *preds, int num_heads, const int32_t *src_index, int num_pred_planes,
+                                        int height, int width, const float *cand_coords, int num_pairs, int num_cand, int num_keep,
+                                        float *out_coords, int out_row_points, int32_t *out_index, void *stream)
+{
+  if (num_heads < 0 || num_heads > PCT_POINT_MAX_HEADS || num_pred_planes < 0 || height <= 0 || width <= 0 || num_pairs < 0 ||
+      num_cand < 0 || num_keep < 0 || num_keep > num_cand || out_row_points < num_keep)
+    return PCT_ERR_BAD_ARG;
+  if (num_heads == 0 || num_pairs == 0 || num_keep == 0) return PCT_OK;
+  if (!preds || !cand_coords || !out_coords || num_pred_planes == 0) return PCT_ERR_BAD_ARG;
+  if (!src_index && num_pairs > num_pred_planes) return PCT_ERR_BAD_ARG;
+  if (const int rc = point_heads_status(preds, num_heads); rc != PCT_OK) return rc;
+  if ((((uintptr_t)src_index | (uintptr_t)out_index) & 3u) || (((uintptr_t)cand_coords | (uintptr_t)out_coords) & 7u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_select_many(preds, num_heads, src_index, num_pred_planes, height, width, cand_coords, num_pairs, num_cand,
+                                       num_keep, out_coords, out_row_points, out_index, static_cast<hipStream_t>(stream));
+}
+
+int pct_point_mask_loss_forward_many_f32(const float *const *preds, int num_heads, const int32_t *src_index, int num_pred_planes,
+                                         int height, int width, const float *tgt, const int32_t *tgt_index, int num_tgt_planes,
+                                         int tgt_height, int tgt_width, const float *coords, int num_pairs, int num_points, float *x,
+                                         float *t, float *sums, void *stream)
+{
+  if (num_heads < 0 || num_heads > PCT_POINT_MAX_HEADS || num_pred_planes < 0 || num_tgt_planes < 0 || height <= 0 || width <= 0 ||
+      tgt_height <= 0 || tgt_width <= 0 || num_pairs < 0 || num_points < 0)
+    return PCT_ERR_BAD_ARG;
+  if (num_heads == 0 || num_pairs == 0 || num_points == 0) return PCT_OK;
+  if (!preds || !tgt || !coords || !x || !t || !sums || num_pred_planes == 0 || num_tgt_planes == 0) return PCT_ERR_BAD_ARG;
+  if ((!src_index && num_pairs > num_pred_planes) || (!tgt_index && num_pairs > num_tgt_planes)) return PCT_ERR_BAD_ARG;
+  if (const int rc = point_heads_status(preds, num_heads); rc != PCT_OK) return rc;
+  if ((((uintptr_t)src_index | (uintptr_t)tgt | (uintptr_t)tgt_index | (uintptr_t)x | (uintptr_t)t | (uintptr_t)sums) & 3u) ||
+      ((uintptr_t)coords & 7u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_loss_forward_many(preds, num_heads, src_index, num_pred_planes, height, width, tgt, tgt_index,
+                                             num_tgt_planes, tgt_height, tgt_width, coords, num_pairs, num_points, x, t, sums,
+                                             static_cast<hipStream_t>(stream));
+}
+
+int pct_point_match_cost_many_f32(const float *const *preds, int num_heads, int batch, int num_query, int height, int width,
+                                  const float *tgt, int num_tgt_planes, int tgt_height, int tgt_width, const int32_t *tgt_start,
+                                  const int32_t *tgt_count, int max_targets, const float *coords, int num_points, float cost_mask,
+                                  float cost_dice, void *workspace, float *cost, void *stream)
+{
+  if (num_heads < 0 || num_heads > PCT_POINT_MAX_HEADS || batch < 0 || num_query < 0 || height <= 0 || width <= 0 ||
+      num_tgt_planes < 0 || tgt_height <= 0 || tgt_width <= 0 || max_targets < 0 || num_points < 0)
+    return PCT_ERR_BAD_ARG;
+  if (num_heads == 0 || batch == 0 || num_query == 0 || max_targets == 0 || num_points == 0) return PCT_OK;
+  if (!preds || (!tgt && num_tgt_planes > 0) || !tgt_start || !tgt_count || !coords || !workspace || !cost) return PCT_ERR_BAD_ARG;
+  if (const int rc = point_heads_status(preds, num_heads); rc != PCT_OK) return rc;
+  if ((((uintptr_t)tgt | (uintptr_t)tgt_start | (uintptr_t)tgt_count | (uintptr_t)cost) & 3u) || ((uintptr_t)coords & 7u) ||
+      ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_point_match_cost_many(preds, num_heads, batch, num_query, height, width, tgt, num_tgt_planes, tgt_height,
+                                           tgt_width, tgt_start, tgt_count, max_targets, coords, num_points, cost_mask, cost_dice,
+                                           workspace, cost, static_cast<hipStream_t>(stream));
+}
+
 int pct_instance_label_map_f32(const float *planes, int num_planes, int plane_height, int plane_width, const int32_t *plane_start,
                                const int32_t *plane_count, int batch, int height, int width, int32_t *labels, void *stream)
 {

@@ -201,6 +201,17 @@ int launch_point_select(const float *pred, const int *src_index, int num_pred, i
 int launch_point_match_cost(const float *pred, int B, int Q, int H, int W, const float *tgt, int num_tgt, int Ht, int Wt,
                             const int *tgt_start, const int *tgt_count, int Gmax, const float *coords, int P, float cost_mask,
                             float cost_dice, void *workspace, float *cost, hipStream_t stream);
+// the same for 0 < num_heads <= PCT_POINT_MAX_HEADS predictions in one launch: `preds` a host array of device pointers, copied
+// into a by-value kernel argument; every per-head array carries a leading [num_heads] dimension
+int launch_point_select_many(const float *const *preds, int num_heads, const int *src_index, int num_pred, int H, int W,
+                             const float *cand_coords, int K, int S, int num_keep, float *out_coords, int out_row_points,
+                             int *out_index, hipStream_t stream);
+int launch_point_loss_forward_many(const float *const *preds, int num_heads, const int *src_index, int num_pred, int H, int W,
+                                   const float *tgt, const int *tgt_index, int num_tgt, int Ht, int Wt, const float *coords, int K,
+                                   int P, float *x, float *t, float *sums, hipStream_t stream);
+int launch_point_match_cost_many(const float *const *preds, int num_heads, int B, int Q, int H, int W, const float *tgt, int num_tgt,
+                                 int Ht, int Wt, const int *tgt_start, const int *tgt_count, int Gmax, const float *coords, int P,
+                                 float cost_mask, float cost_dice, void *workspace, float *cost, hipStream_t stream);
 
 // ---- pixel-embedding loss (embedding_loss.hip; include/pctrans_hip_train.h).  PCT_ERR_UNSUPPORTED before any launch for a
 // geometry the kernels do not cover ---------------------------------------------------------------------------------------

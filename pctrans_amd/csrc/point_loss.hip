@@ -3,7 +3,9 @@
 // sums and the scatter of their gradient that loss/matcher.py and loss/maskformer_criterion.py otherwise run as grid_sample
 // forward / backward plus elementwise and reduce launches, the choice of the most uncertain of the oversampled candidates that
 // the criterion otherwise makes with a gather, topk, gather and cat, and the matcher's cost matrices that it otherwise forms
-// from two gathers with a chain of elementwise launches and three einsum.
+// from two gathers with a chain of elementwise launches and three einsum.  The selection, the loss forward and the cost pass also
+// exist for several prediction heads in one launch (pct_point_select_uncertain_many_f32, pct_point_mask_loss_forward_many_f32,
+// pct_point_match_cost_many_f32): the same per-workgroup bodies, the head taken from a grid dimension (HeadPlanes below).
 //
 // Sampling is F.grid_sample(input, 2c - 1, "bilinear", "zeros", align_corners=False): x = c_x * W - 0.5 (one fma),
 // y = c_y * H - 0.5, taps at floor and floor + 1, weights (1 - tx)(1 - ty) .. tx ty, a tap outside the plane adds nothing.
@@ -104,15 +106,26 @@ __global__ __launch_bounds__(PL_GATHER_BLOCK) void point_sample_kernel(const flo
   out[(size_t)k * P + p] = v;
 }
 
+// The prediction planes of the heads of a *_many launch: a by-value kernel argument (128 bytes of the kernarg segment, read
+// with a scalar load at a uniform index), so that nothing is uploaded.  A *_many kernel takes its head from a grid dimension,
+// moves every per-head array to that head's slice and runs the body of its single-head sibling: the same instructions on the
+// same values, so the same bits.
+constexpr int PL_MAX_HEADS = 16;           // include/pctrans_hip_train.h: PCT_POINT_MAX_HEADS
+static_assert(PL_MAX_HEADS == PCT_POINT_MAX_HEADS, "the header's limit");
+
+struct HeadPlanes {
+  const float *p[PL_MAX_HEADS];
+};
+
 // one workgroup per pair: every thread a fixed subset of the points in ascending order, then a fixed tree over the lanes and
 // the waves in ascending order
-__global__ __launch_bounds__(PL_FWD_BLOCK) void point_loss_forward_kernel(
+__device__ __forceinline__ void point_loss_forward_body(
     const float *__restrict__ pred, const int *__restrict__ src_index, const int num_pred, const int H, const int W,
     const float *__restrict__ tgt, const int *__restrict__ tgt_index, const int num_tgt, const int Ht, const int Wt,
-    const float2 *__restrict__ coords, const int P, float *__restrict__ xs, float *__restrict__ ts, float *__restrict__ sums)
+    const float2 *__restrict__ coords, const int P, float *__restrict__ xs, float *__restrict__ ts, float *__restrict__ sums,
+    const int k)
 {
   __shared__ float part[PL_FWD_BLOCK / 64][4];
-  const int k = blockIdx.x;
   const int sp = src_index ? src_index[k] : k, tp = tgt_index ? tgt_index[k] : k;
   const bool ok = (unsigned)sp < (unsigned)num_pred && (unsigned)tp < (unsigned)num_tgt;
   const float *pp = pred + (size_t)(ok ? sp : 0) * H * W, *tq = tgt + (size_t)(ok ? tp : 0) * Ht * Wt;
@@ -149,6 +162,27 @@ __global__ __launch_bounds__(PL_FWD_BLOCK) void point_loss_forward_kernel(
     for (int w = 0; w < PL_FWD_BLOCK / 64; ++w) a += part[w][threadIdx.x];
     sums[(size_t)k * 4 + threadIdx.x] = a;
   }
+}
+
+__global__ __launch_bounds__(PL_FWD_BLOCK) void point_loss_forward_kernel(
+    const float *__restrict__ pred, const int *__restrict__ src_index, const int num_pred, const int H, const int W,
+    const float *__restrict__ tgt, const int *__restrict__ tgt_index, const int num_tgt, const int Ht, const int Wt,
+    const float2 *__restrict__ coords, const int P, float *__restrict__ xs, float *__restrict__ ts, float *__restrict__ sums)
+{
+  point_loss_forward_body(pred, src_index, num_pred, H, W, tgt, tgt_index, num_tgt, Ht, Wt, coords, P, xs, ts, sums, blockIdx.x);
+}
+
+// grid (pair, head): the index vectors are [heads, K], coords [heads, K, P, 2], x, t [heads, K, P], sums [heads, K, 4]
+__global__ __launch_bounds__(PL_FWD_BLOCK) void point_loss_forward_many_kernel(
+    const HeadPlanes heads, const int *__restrict__ src_index, const int num_pred, const int H, const int W,
+    const float *__restrict__ tgt, const int *__restrict__ tgt_index, const int num_tgt, const int Ht, const int Wt,
+    const float2 *__restrict__ coords, const int K, const int P, float *__restrict__ xs, float *__restrict__ ts,
+    float *__restrict__ sums)
+{
+  const size_t row0 = (size_t)blockIdx.y * K;
+  point_loss_forward_body(heads.p[blockIdx.y], src_index ? src_index + row0 : nullptr, num_pred, H, W, tgt,
+                          tgt_index ? tgt_index + row0 : nullptr, num_tgt, Ht, Wt, coords + row0 * P, P, xs + row0 * P,
+                          ts + row0 * P, sums + row0 * 4, blockIdx.x);
 }
 
 __global__ __launch_bounds__(PL_BWD_BLOCK) void point_loss_backward_kernel(
@@ -225,11 +259,10 @@ __global__ __launch_bounds__(PL_BWD_BLOCK) void point_loss_backward_kernel(
 // 3. Ballots of key < key_t and key == key_t per round and wave, the scan of their counts, and for candidate s with `lb` lower
 //    and `eb` equal keys before it:  selected = lower or (equal and eb < rank),  position = lb + min(eb, rank).
 template <int IPT>
-__global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_kernel(const float *__restrict__ pred,
-                                                                       const int *__restrict__ src_index, const int num_pred,
-                                                                       const int H, const int W, const float2 *__restrict__ cand,
-                                                                       const int S, const int num_keep, float2 *__restrict__ out,
-                                                                       const int out_row_points, int *__restrict__ out_index)
+__device__ __forceinline__ void point_select_body(const float *__restrict__ pred, const int *__restrict__ src_index,
+                                                  const int num_pred, const int H, const int W, const float2 *__restrict__ cand,
+                                                  const int S, const int num_keep, float2 *__restrict__ out,
+                                                  const int out_row_points, int *__restrict__ out_index, const int k)
 {
   constexpr int WAVES = PL_SELECT_BLOCK / 64, CELLS = IPT * WAVES;
   static_assert(CELLS <= PL_SELECT_BLOCK && IPT * PL_SELECT_BLOCK <= PL_SELECT_MAX_CAND, "one scan cell per thread");
@@ -238,7 +271,7 @@ __global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_kernel(const flo
   __shared__ unsigned cell[2][PL_SELECT_BLOCK];                            // lower / equal keys per (round, wave), then before it
   __shared__ unsigned wave_sum[2][WAVES];
   __shared__ unsigned pick[2];                                             // the chosen bin and the rank inside it
-  const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int plane = src_index ? src_index[k] : k;
   float2 *orow = out + (size_t)k * out_row_points;
   int *irow = out_index ? out_index + (size_t)k * num_keep : nullptr;
@@ -373,6 +406,29 @@ __global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_kernel(const flo
   }
 }
 
+template <int IPT>
+__global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_kernel(const float *__restrict__ pred,
+                                                                       const int *__restrict__ src_index, const int num_pred,
+                                                                       const int H, const int W, const float2 *__restrict__ cand,
+                                                                       const int S, const int num_keep, float2 *__restrict__ out,
+                                                                       const int out_row_points, int *__restrict__ out_index)
+{
+  point_select_body<IPT>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index, blockIdx.x);
+}
+
+// grid (pair, head): src_index [heads, K], cand [heads, K, S], out [heads, K, out_row_points], out_index [heads, K, num_keep]
+template <int IPT>
+__global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_many_kernel(
+    const HeadPlanes heads, const int *__restrict__ src_index, const int num_pred, const int H, const int W,
+    const float2 *__restrict__ cand, const int K, const int S, const int num_keep, float2 *__restrict__ out,
+    const int out_row_points, int *__restrict__ out_index)
+{
+  const size_t row0 = (size_t)blockIdx.y * K;
+  point_select_body<IPT>(heads.p[blockIdx.y], src_index ? src_index + row0 : nullptr, num_pred, H, W, cand + row0 * S, S, num_keep,
+                         out + row0 * out_row_points, out_row_points, out_index ? out_index + row0 * num_keep : nullptr,
+                         blockIdx.x);
+}
+
 // Matcher cost matrices (pct_point_match_cost_f32): cost[b, q, g] of Point_HungarianMatcher._batched_costs from the planes, the
 // point samples never in memory.  Three P-long contractions per (q, g) on v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 sums):
 //     ce  = sum_p softplus(-x) t + sum_p softplus(x) (1 - t)      (two non-negative products into ONE accumulator: nothing cancels)
@@ -428,14 +484,15 @@ __host__ __device__ inline MatchCostPlan match_cost_plan(const int B, const int 
   return m;
 }
 
-__global__ __launch_bounds__(MC_BLOCK, 2) void match_cost_partial_kernel(
+__device__ __forceinline__ void match_cost_partial_body(
     const float *__restrict__ pred, const float *__restrict__ tgt, const int *__restrict__ tgt_start,
     const int *__restrict__ tgt_count, const float2 *__restrict__ coords, const int Q, const int H, const int W, const int num_tgt,
-    const int Ht, const int Wt, const int Gmax, const int P, const MatchCostPlan plan, float *__restrict__ ws)
+    const int Ht, const int Wt, const int Gmax, const int P, const MatchCostPlan plan, float *__restrict__ ws, const int chunk,
+    const unsigned group, const int b)
 {
   __shared__ Taps taps[MC_SUB];
   __shared__ float ts[MC_SUB * MC_TS];
-  const int chunk = blockIdx.x, qgrp = blockIdx.y / plan.ggroups, ggrp = blockIdx.y - qgrp * plan.ggroups, b = blockIdx.z;
+  const int qgrp = group / plan.ggroups, ggrp = group - qgrp * plan.ggroups;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, kh = lane >> 5;
   const int start = tgt_start[b];
   const int count = max(0, min(tgt_count[b], Gmax)) - ggrp * MC_GGROUP;    // targets of this group that the image has
@@ -520,10 +577,30 @@ __global__ __launch_bounds__(MC_BLOCK, 2) void match_cost_partial_kernel(
   if (ggrp == 0 && kh == 0) wsb[2 * Qp * Gp + (long long)qgrp * MC_QGROUP + wave * 32 + col] = s2;
 }
 
-__global__ __launch_bounds__(256) void match_cost_finish_kernel(const float *__restrict__ ws, const int *__restrict__ tgt_count,
-                                                                const int Q, const int Gmax, const int P, const long long total,
-                                                                const MatchCostPlan plan, const float cost_mask,
-                                                                const float cost_dice, float *__restrict__ cost)
+__global__ __launch_bounds__(MC_BLOCK, 2) void match_cost_partial_kernel(
+    const float *__restrict__ pred, const float *__restrict__ tgt, const int *__restrict__ tgt_start,
+    const int *__restrict__ tgt_count, const float2 *__restrict__ coords, const int Q, const int H, const int W, const int num_tgt,
+    const int Ht, const int Wt, const int Gmax, const int P, const MatchCostPlan plan, float *__restrict__ ws)
+{
+  match_cost_partial_body(pred, tgt, tgt_start, tgt_count, coords, Q, H, W, num_tgt, Ht, Wt, Gmax, P, plan, ws, blockIdx.x,
+                          blockIdx.y, blockIdx.z);
+}
+
+// grid z = head * B + image: coords [heads, B, P], one workspace of the single-head size per head; `plan` is the plan of B images
+__global__ __launch_bounds__(MC_BLOCK, 2) void match_cost_partial_many_kernel(
+    const HeadPlanes heads, const float *__restrict__ tgt, const int *__restrict__ tgt_start, const int *__restrict__ tgt_count,
+    const float2 *__restrict__ coords, const int B, const int Q, const int H, const int W, const int num_tgt, const int Ht,
+    const int Wt, const int Gmax, const int P, const MatchCostPlan plan, float *__restrict__ ws)
+{
+  const int head = blockIdx.z / (unsigned)B, b = blockIdx.z - head * B;
+  match_cost_partial_body(heads.p[head], tgt, tgt_start, tgt_count, coords + (size_t)head * B * P, Q, H, W, num_tgt, Ht, Wt, Gmax, P,
+                          plan, ws + (size_t)head * B * plan.chunks * plan.per_chunk, blockIdx.x, blockIdx.y, b);
+}
+
+__device__ __forceinline__ void match_cost_finish_body(const float *__restrict__ ws, const int *__restrict__ tgt_count, const int Q,
+                                                       const int Gmax, const int P, const long long total,
+                                                       const MatchCostPlan &plan, const float cost_mask, const float cost_dice,
+                                                       float *__restrict__ cost)
 {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -545,6 +622,25 @@ __global__ __launch_bounds__(256) void match_cost_finish_kernel(const float *__r
     c = cost_mask * (ce / (float)P) + cost_dice * dice;
   }
   cost[i] = c;
+}
+
+__global__ __launch_bounds__(256) void match_cost_finish_kernel(const float *__restrict__ ws, const int *__restrict__ tgt_count,
+                                                                const int Q, const int Gmax, const int P, const long long total,
+                                                                const MatchCostPlan plan, const float cost_mask,
+                                                                const float cost_dice, float *__restrict__ cost)
+{
+  match_cost_finish_body(ws, tgt_count, Q, Gmax, P, total, plan, cost_mask, cost_dice, cost);
+}
+
+// grid y = head: `total` elements of cost and one workspace of the single-head size per head
+__global__ __launch_bounds__(256) void match_cost_finish_many_kernel(const float *__restrict__ ws, const int *__restrict__ tgt_count,
+                                                                     const int B, const int Q, const int Gmax, const int P,
+                                                                     const long long total, const MatchCostPlan plan,
+                                                                     const float cost_mask, const float cost_dice,
+                                                                     float *__restrict__ cost)
+{
+  match_cost_finish_body(ws + (size_t)blockIdx.y * B * plan.chunks * plan.per_chunk, tgt_count, Q, Gmax, P, total, plan, cost_mask,
+                         cost_dice, cost + (size_t)blockIdx.y * total);
 }
 
 // what the kernels cover: 32-bit offsets inside a plane, a one-dimensional grid, and for the losses a band that fits LDS
@@ -638,6 +734,62 @@ int launch_point_select(const float *pred, const int *src_index, int num_pred, i
     point_select_kernel<40><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
   else
     point_select_kernel<64><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
+  return (int)hipGetLastError();
+}
+
+// ---- the same for several prediction heads in one launch: the C ABI has checked 0 < num_heads <= PL_MAX_HEADS and the entries
+static HeadPlanes head_planes(const float *const *preds, int num_heads)
+{
+  HeadPlanes hp;
+  for (int h = 0; h < PL_MAX_HEADS; ++h) hp.p[h] = h < num_heads ? preds[h] : nullptr;
+  return hp;
+}
+
+int launch_point_select_many(const float *const *preds, int num_heads, const int *src_index, int num_pred, int H, int W,
+                             const float *cand_coords, int K, int S, int num_keep, float *out_coords, int out_row_points,
+                             int *out_index, hipStream_t stream)
+{
+  if ((long long)H * W >= 0x7fffffffLL || S > PL_SELECT_MAX_CAND) return PCT_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)K, (unsigned)num_heads), block(PL_SELECT_BLOCK);
+  const HeadPlanes hp = head_planes(preds, num_heads);
+  const float2 *cand = reinterpret_cast<const float2 *>(cand_coords);
+  float2 *out = reinterpret_cast<float2 *>(out_coords);
+  if (S <= 16 * PL_SELECT_BLOCK)
+    point_select_many_kernel<16><<<grid, block, 0, stream>>>(hp, src_index, num_pred, H, W, cand, K, S, num_keep, out, out_row_points, out_index);
+  else if (S <= 40 * PL_SELECT_BLOCK)
+    point_select_many_kernel<40><<<grid, block, 0, stream>>>(hp, src_index, num_pred, H, W, cand, K, S, num_keep, out, out_row_points, out_index);
+  else
+    point_select_many_kernel<64><<<grid, block, 0, stream>>>(hp, src_index, num_pred, H, W, cand, K, S, num_keep, out, out_row_points, out_index);
+  return (int)hipGetLastError();
+}
+
+int launch_point_loss_forward_many(const float *const *preds, int num_heads, const int *src_index, int num_pred, int H, int W,
+                                   const float *tgt, const int *tgt_index, int num_tgt, int Ht, int Wt, const float *coords, int K,
+                                   int P, float *x, float *t, float *sums, hipStream_t stream)
+{
+  if (const int rc = point_loss_geometry_status(H, W, Ht, Wt, K); rc != PCT_OK) return rc;
+  point_loss_forward_many_kernel<<<dim3((unsigned)K, (unsigned)num_heads), dim3(PL_FWD_BLOCK), 0, stream>>>(
+      head_planes(preds, num_heads), src_index, num_pred, H, W, tgt, tgt_index, num_tgt, Ht, Wt,
+      reinterpret_cast<const float2 *>(coords), K, P, x, t, sums);
+  return (int)hipGetLastError();
+}
+
+int launch_point_match_cost_many(const float *const *preds, int num_heads, int B, int Q, int H, int W, const float *tgt, int num_tgt,
+                                 int Ht, int Wt, const int *tgt_start, const int *tgt_count, int Gmax, const float *coords, int P,
+                                 float cost_mask, float cost_dice, void *workspace, float *cost, hipStream_t stream)
+{
+  if (const int rc = match_cost_geometry_status(B, Q, H, W, Ht, Wt, Gmax, P); rc != PCT_OK) return rc;
+  if ((long long)num_heads * B > 65535) return PCT_ERR_UNSUPPORTED;         // the grid's z holds (head, image)
+  const MatchCostPlan plan = match_cost_plan(B, Q, Gmax, P);                // of ONE head: the order of every sum is the single call's
+  float *ws = static_cast<float *>(workspace);
+  match_cost_partial_many_kernel<<<dim3((unsigned)plan.chunks, (unsigned)(plan.qgroups * plan.ggroups), (unsigned)(num_heads * B)),
+                                   dim3(MC_BLOCK), 0, stream>>>(head_planes(preds, num_heads), tgt, tgt_start, tgt_count,
+                                                                reinterpret_cast<const float2 *>(coords), B, Q, H, W, num_tgt, Ht,
+                                                                Wt, Gmax, P, plan, ws);
+  if (const int rc = (int)hipGetLastError(); rc != 0) return rc;
+  const long long total = (long long)B * Q * Gmax;
+  match_cost_finish_many_kernel<<<dim3((unsigned)((total + 255) / 256), (unsigned)num_heads), dim3(256), 0, stream>>>(
+      ws, tgt_count, B, Q, Gmax, P, total, plan, cost_mask, cost_dice, cost);
   return (int)hipGetLastError();
 }
 

@@ -153,6 +153,11 @@ class SetCriterion(nn.Module):
         # pctrans_amd/embedding_loss.py where their conditions hold (device tensors, target masks of one size, fp32 contiguous
         # embedding, covered geometry), the code below otherwise.  A plain attribute; process default from PCT_EMB_LOSS
         self.emb_loss = _embedding_loss.default()
+        # "each": loss_masks head by head, as the loops of forward reach them.  "batched": where every head meets the conditions
+        # of the "hip" loss path, the selection, the loss and its backward of ALL heads run as one launch each before the loops
+        # (point_loss.*_many), with the random numbers the per-head calls would draw; anything else runs head by head.  A plain
+        # attribute; process default from PCT_LOSS_HEADS
+        self.loss_heads = _point_loss.heads_default()
         self._target_planes = None
         self._emb_plane_index = None
 
@@ -210,6 +215,56 @@ class SetCriterion(nn.Module):
                     coords = torch.cat([coords, torch.rand(K, num_random, 2, device=pred.device)], dim=1)
         loss_mask, loss_dice = _point_loss.point_mask_losses(pred, src, planes, tgt, coords, num_masks)
         return {"loss_mask": loss_mask, "loss_dice": loss_dice}
+
+    def _loss_masks_batched(self, outputs, targets, num_masks):
+        """loss_masks of the final prediction and every auxiliary head at once, in the order forward's loops reach them: the
+        final prediction with indices_list[-1], then auxiliary head i with indices_list[i].  -> a list of {"loss_mask",
+        "loss_dice"}, one per head, or None (and no random number drawn) when a condition of the batched path does not hold."""
+        if not ("masks" in self.losses and self.point_loss == "hip" and torch.is_tensor(outputs.get("pred_masks"))):
+            return None
+        aux = outputs.get("aux_outputs", [])
+        if len(outputs["indices_list"]) < len(aux) or not all(torch.is_tensor(a.get("pred_masks")) for a in aux):
+            return None
+        preds = [outputs["pred_masks"]] + [a["pred_masks"] for a in aux]
+        indices = [outputs["indices_list"][-1]] + [outputs["indices_list"][i] for i in range(len(aux))]
+        pred = preds[0]
+        if not all(p.is_cuda and p.dtype == torch.float32 and p.dim() == 4 and p.is_contiguous() for p in preds):
+            return None
+        got = self._hip_target_planes(targets, pred)
+        if got is None or not _point_loss.loss_many_supported(preds, got[0]):
+            return None
+        planes, starts = got
+        dev, Q = pred.device, pred.shape[1]
+        K = sum(int(s.shape[0]) for s, _ in indices[0])
+        if K == 0 or any(sum(int(s.shape[0]) for s, _ in ind) != K or len(ind) != len(indices[0]) for ind in indices):
+            return None
+        num_sampled = int(self.num_points * self.oversample_ratio)
+        num_uncertain = int(self.importance_sample_ratio * self.num_points)
+        num_random = self.num_points - num_uncertain
+        if num_uncertain > 0 and not (self.point_select == "hip" and 0 < num_sampled <= _point_loss.MAX_CANDIDATES
+                                      and num_uncertain <= num_sampled):
+            return None
+        if num_uncertain < 0 or num_random < 0 or num_sampled < 0:
+            return None
+        heads = len(preds)
+        offs = torch.tensor([[b * Q for ind in indices for b, (s, _) in enumerate(ind) for _ in range(int(s.shape[0]))],
+                             [starts[b] for ind in indices for b, (_, t) in enumerate(ind) for _ in range(int(t.shape[0]))]],
+                            dtype=torch.int64).to(dev, non_blocking=True)
+        src = (torch.cat([s.to(dev) for ind in indices for s, _ in ind]) + offs[0]).view(heads, K)
+        tgt = (torch.cat([t.to(dev) for ind in indices for _, t in ind]) + offs[1]).view(heads, K)
+        with torch.no_grad():
+            # per head, in order: torch.rand(K, 3 P, 2) then torch.rand(K, num_random, 2), as the per-head calls draw them
+            candidates, fresh = _point_loss.draw_head_coords(heads, K, num_sampled, num_random, dev)
+            if num_uncertain > 0:
+                coords = torch.empty(heads, K, self.num_points, 2, device=dev)
+                _point_loss.select_uncertain_points_many(preds, src, candidates, num_uncertain, out=coords, with_index=False)
+                if num_random > 0:
+                    coords[:, :, num_uncertain:] = fresh
+            else:
+                coords = fresh
+            del candidates
+        loss_mask, loss_dice = _point_loss.point_mask_losses_many(preds, src, planes, tgt, coords, num_masks)
+        return [{"loss_mask": loss_mask[h], "loss_dice": loss_dice[h]} for h in range(heads)]
 
     def loss_masks(self, outputs, targets, indices, num_masks):
         assert "pred_masks" in outputs
@@ -332,6 +387,9 @@ class SetCriterion(nn.Module):
             self.matcher.check()               # device-side assignments: infeasible cost matrices surface here
         num_masks = torch.clamp(num_masks / world, min=1).item()
 
+        # loss_heads == "batched": the mask losses of all heads, computed once; the loops below take theirs from here
+        batched = self._loss_masks_batched(outputs, targets, num_masks) if self.loss_heads == "batched" else None
+
         losses = {}
         for loss in self.losses:
             if loss == "embedding":
@@ -340,6 +398,8 @@ class SetCriterion(nn.Module):
                 losses.update(self.loss_refpoints(outputs, targets, indices, num_masks))
             elif loss == "sem":
                 losses.update(self.loss_sem(outputs, targets))
+            elif loss == "masks" and batched is not None:
+                losses.update(batched[0])
             else:
                 losses.update(self.get_loss(loss, outputs, targets, indices, num_masks))
 
@@ -350,7 +410,10 @@ class SetCriterion(nn.Module):
                     if "reid" in loss or loss == "sem":
                         continue
                     if not (loss == "embedding" or loss == "refpoints"):
-                        l_dict = self.get_loss(loss, aux_outputs, targets, indices, num_masks)
+                        if loss == "masks" and batched is not None:
+                            l_dict = batched[1 + i]
+                        else:
+                            l_dict = self.get_loss(loss, aux_outputs, targets, indices, num_masks)
                         losses.update({k + f"_{i}": v for k, v in l_dict.items()})
                     if i != 0:
                         l_dict = self.loss_refpoints(outputs["aux_reference_points"][i - 1], targets, indices,

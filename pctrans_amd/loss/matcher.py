@@ -48,6 +48,10 @@ class Point_HungarianMatcher(nn.Module):
         # where it applies (CUDA fp32 contiguous pred_masks, target masks of one size on the same device); no point samples, no
         # einsum.  A plain attribute; process default from PCT_MATCH_COST
         self.match_cost = _point_loss.match_cost_default()
+        # acts only with match_cost = "hip" in forward_many.  "each": one cost pass per prediction.  "batched": the cost passes of
+        # all predictions are ONE call (point_loss.match_costs_many) whose output goes to the assignment as it is: no torch.cat of
+        # the cost tensors.  The same random points in the same order.  A plain attribute; process default from PCT_LOSS_HEADS
+        self.cost_heads = _point_loss.heads_default()
         self._target_planes = None         # (key, fp32 planes [sum G, Ht, Wt], device starts, device counts, the masks)
 
     def _match_target_planes(self, targets, like):
@@ -194,6 +198,17 @@ class Point_HungarianMatcher(nn.Module):
         if not (self.batch_images and self.device_lsap and same and bs > 0 and len(sizes) == 1 and 0 < max(counts) <= min(num_queries, 512)
                 and num_queries <= 1024):
             return [self.memory_efficient_forward(o, targets) for o in outputs_list]
+        if self.cost_heads == "batched" and self.match_cost == "hip":
+            preds = [o["pred_masks"] for o in outputs_list]
+            got = self._match_target_planes(targets, pred)
+            if (all(p.dtype == torch.float32 and p.dim() == 4 and p.is_contiguous() for p in preds) and got is not None
+                    and _point_loss.match_costs_many_supported(preds, got[0], self.num_points, max(counts))):
+                # today's order: head by head, one torch.rand(1, P, 2) per image
+                coords = torch.cat([torch.rand(1, self.num_points, 2, device=pred.device) for _ in range(len(preds) * bs)])
+                cost = _point_loss.match_costs_many(preds, got[0], got[1], got[2], coords.view(len(preds), bs, self.num_points, 2),
+                                                    self.cost_mask, self.cost_dice, max(counts))
+                flat = self._assign_padded(cost.view(len(preds) * bs, num_queries, max(counts)), counts * len(preds))
+                return [flat[k * bs:(k + 1) * bs] for k in range(len(preds))]
         costs = [self._batched_costs(o, targets)[0] for o in outputs_list]
         flat = self._assign_padded(torch.cat(costs), counts * len(outputs_list))
         return [flat[k * bs:(k + 1) * bs] for k in range(len(outputs_list))]

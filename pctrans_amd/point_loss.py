@@ -10,7 +10,14 @@ and `Point_HungarianMatcher.point_sample` are "torch" unless set to "hip" (proce
 no topk); it acts inside the "hip" loss path when `SetCriterion.point_select` is "hip" (process default: PCT_POINT_SELECT).
 `match_costs` is the matcher's whole cost pass (`pct_point_match_cost_f32`: both gathers, BCE, dice and the three contractions
 in one kernel plus a small finishing one); `Point_HungarianMatcher.match_cost` is "torch" unless set to "hip" (process default:
-PCT_MATCH_COST)."""
+PCT_MATCH_COST).
+
+The `*_many` functions give the selection, the loss and the cost pass a head dimension (`pct_point_select_uncertain_many_f32`,
+`pct_point_mask_loss_forward_many_f32`, `pct_point_match_cost_many_f32`): the decoder's prediction heads, separate tensors of one
+geometry, go through ONE launch each, their addresses in a small table passed with the launch; per head the bits are those of the
+single-head call.  They act when `SetCriterion.loss_heads` / `Point_HungarianMatcher.cost_heads` is "batched" (process default:
+PCT_LOSS_HEADS, "each")."""
+import ctypes
 import os
 
 import torch
@@ -27,6 +34,7 @@ MATCH_POINTS_PER_PASS = 128   # MC_MAX_CHUNKS, MC_WANT_GROUPS): the workspace fo
 MATCH_MAX_CHUNKS = 32
 MATCH_WANT_GROUPS = 512
 MATCH_MAX_BATCH = 65535
+MAX_HEADS = 16        # heads of one *_many launch (include/pctrans_hip_train.h: PCT_POINT_MAX_HEADS); more go in groups
 
 
 def default():
@@ -51,6 +59,15 @@ def match_cost_default():
     v = os.environ.get("PCT_MATCH_COST") or "torch"
     if v not in ("hip", "torch"):
         raise RuntimeError("PCT_MATCH_COST must be 'hip' or 'torch', got %r" % v)
+    return v
+
+
+def heads_default():
+    """Process default of `SetCriterion.loss_heads` / `Point_HungarianMatcher.cost_heads`: PCT_LOSS_HEADS = each | batched
+    (default each)."""
+    v = os.environ.get("PCT_LOSS_HEADS") or "each"
+    if v not in ("each", "batched"):
+        raise RuntimeError("PCT_LOSS_HEADS must be 'each' or 'batched', got %r" % v)
     return v
 
 
@@ -294,3 +311,230 @@ def point_mask_losses(pred_masks, src_idx, tgt_planes, tgt_index, coords, num_ma
         zero = pred_masks.sum() * 0
         return zero, zero.clone()
     return PointMaskLossFunction.apply(pred_masks, src_index, tgt_planes.detach(), tgt_index, coords, float(num_masks))
+
+
+# ---- several prediction heads in one launch ---------------------------------------------------------------------------------
+
+def _heads_alike(preds):
+    """A non-empty sequence of tensors of one shape, dtype and device."""
+    return (isinstance(preds, (list, tuple)) and len(preds) > 0 and all(torch.is_tensor(p) for p in preds)
+            and all(p.shape == preds[0].shape and p.dtype == preds[0].dtype and p.device == preds[0].device for p in preds))
+
+
+def _head_table(preds):
+    """The host array of device pointers the *_many entries take."""
+    return (ctypes.c_void_p * len(preds))(*[p.data_ptr() for p in preds])
+
+
+def _head_groups(num_heads):
+    return [(h0, min(h0 + MAX_HEADS, num_heads)) for h0 in range(0, num_heads, MAX_HEADS)]
+
+
+def _index_many(idx, heads, n, dev):
+    if idx is None:
+        return None
+    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(idx.shape) != (heads, n):
+        raise RuntimeError("index must be [%d, %d] plane numbers, got %s" % (heads, n, tuple(idx.shape)))
+    return idx
+
+
+def _part(t, h0, h1):
+    return None if t is None else t[h0:h1].data_ptr()
+
+
+def draw_head_coords(num_heads, num_pairs, num_sampled, num_random, device):
+    """The random numbers of `num_heads` per-head `loss_masks` calls, drawn ahead: per head, in order, torch.rand(K, num_sampled, 2)
+    then (num_random > 0) torch.rand(K, num_random, 2), into slices of two preallocated tensors.  The generator ends where the
+    per-head calls leave it.  -> (candidates [heads, K, num_sampled, 2], fresh [heads, K, num_random, 2])."""
+    cand = torch.empty((num_heads, num_pairs, num_sampled, 2), dtype=torch.float32, device=device)
+    fresh = torch.empty((num_heads, num_pairs, max(num_random, 0), 2), dtype=torch.float32, device=device)
+    for h in range(num_heads):
+        torch.rand(num_pairs, num_sampled, 2, out=cand[h])
+        if num_random > 0:
+            torch.rand(num_pairs, num_random, 2, out=fresh[h])
+    return cand, fresh
+
+
+def select_many_supported(preds, cand_coords, num_keep):
+    """Heads of one shape, dtype and device that each pass `select_supported` with their candidates [heads, K, S, 2]."""
+    return (_heads_alike(preds) and torch.is_tensor(cand_coords) and cand_coords.dim() == 4
+            and cand_coords.shape[0] == len(preds) and cand_coords.is_contiguous()
+            and all(select_supported(p, cand_coords[h], num_keep) for h, p in enumerate(preds)))
+
+
+def select_uncertain_points_many(preds, src_index, cand_coords, num_keep, out=None, with_index=True):
+    """`select_uncertain_points` of every head in one launch (pct_point_select_uncertain_many_f32; more than MAX_HEADS heads in
+    groups).  preds: a sequence of [..., H, W] fp32 device tensors of one shape; src_index int [heads, K] or None; cand_coords
+    [heads, K, S, 2]; out None or fp32 contiguous [heads, K, P >= num_keep, 2].  -> (coords, index [heads, K, num_keep] or None);
+    head h holds the bits of select_uncertain_points(preds[h], src_index[h], cand_coords[h], ...).  No gradient."""
+    preds = list(preds)
+    if not preds or not all(torch.is_tensor(p) and p.is_cuda for p in preds):
+        raise RuntimeError("Not implemented on the CPU")
+    num_keep = int(num_keep)
+    cand_coords = cand_coords.detach()
+    if not select_many_supported(preds, cand_coords, num_keep):
+        raise RuntimeError("select_uncertain_points_many needs contiguous fp32 device planes of one shape and candidates "
+                           "[heads, K, S <= %d, 2], 0 <= num_keep <= S" % MAX_CANDIDATES)
+    dev = preds[0].device
+    H, W = preds[0].shape[-2:]
+    heads, K, S = len(preds), int(cand_coords.shape[1]), int(cand_coords.shape[2])
+    src = _index_many(src_index, heads, K, dev)
+    if out is None:
+        out = torch.empty((heads, K, num_keep, 2), dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.float32 and out.dim() == 4 and out.is_contiguous()
+              and tuple(out.shape[:2]) == (heads, K) and out.shape[2] >= num_keep and out.shape[3] == 2):
+        raise RuntimeError("out must be contiguous fp32 [%d, %d, >= %d, 2] on the planes' device" % (heads, K, num_keep))
+    index = torch.empty((heads, K, num_keep), dtype=torch.int32, device=dev) if with_index else None
+    for h0, h1 in _head_groups(heads):
+        with torch.cuda.device(dev), _timing.timed("point_select many", out):
+            rc = _lib.lib().pct_point_select_uncertain_many_f32(
+                _head_table(preds[h0:h1]), h1 - h0, _part(src, h0, h1), preds[0].numel() // (H * W), H, W,
+                cand_coords[h0:h1].data_ptr(), K, S, num_keep, out[h0:h1].data_ptr(), int(out.shape[2]), _part(index, h0, h1),
+                torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "point_select_uncertain_many")
+    return out, index
+
+
+def loss_many_supported(preds, tgt_planes):
+    """Heads of one shape, dtype and device that each pass `loss_supported`."""
+    return _heads_alike(preds) and all(loss_supported(p, tgt_planes) for p in preds)
+
+
+def point_mask_loss_forward_many(preds, src_index, tgt_planes, tgt_index, coords):
+    """-> (x [heads, K, P], t [heads, K, P], sums [heads, K, 4]) of pct_point_mask_loss_forward_many_f32; src_index, tgt_index
+    int32 [heads, K] on the device, coords [heads, K, P, 2]."""
+    if not preds[0].is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    dev = preds[0].device
+    H, W = preds[0].shape[-2:]
+    Ht, Wt = tgt_planes.shape[-2:]
+    heads, K, P = len(preds), int(coords.shape[1]), int(coords.shape[2])
+    src, tgt = _index_many(src_index, heads, K, dev), _index_many(tgt_index, heads, K, dev)
+    x = torch.empty((heads, K, P), dtype=torch.float32, device=dev)
+    t = torch.empty((heads, K, P), dtype=torch.float32, device=dev)
+    sums = (torch.zeros if P == 0 else torch.empty)((heads, K, 4), dtype=torch.float32, device=dev)
+    for h0, h1 in _head_groups(heads):
+        with torch.cuda.device(dev), _timing.timed("point_loss forward many", x):
+            rc = _lib.lib().pct_point_mask_loss_forward_many_f32(
+                _head_table(preds[h0:h1]), h1 - h0, _part(src, h0, h1), preds[0].numel() // (H * W), H, W, tgt_planes.data_ptr(),
+                _part(tgt, h0, h1), tgt_planes.numel() // (Ht * Wt), Ht, Wt, coords[h0:h1].data_ptr(), K, P, x[h0:h1].data_ptr(),
+                t[h0:h1].data_ptr(), sums[h0:h1].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "point_mask_loss_forward_many")
+    return x, t, sums
+
+
+class PointMaskLossManyFunction(torch.autograd.Function):
+    """(pred_masks of every head, each [B, Q, H, W]) -> (loss_mask [heads], loss_dice [heads]).  Saves per head what
+    PointMaskLossFunction saves, stacked; the backward is ONE call of the single-head backward entry on heads * K pairs (it never
+    reads a prediction), its compact planes placed into each head's zero gradient."""
+
+    @staticmethod
+    def forward(ctx, src_index, tgt_planes, tgt_index, coords, num_masks, *preds):
+        x, t, sums = point_mask_loss_forward_many(preds, src_index, tgt_planes, tgt_index, coords)
+        P = coords.shape[2]
+        loss_mask = sums[:, :, 0].sum(1) / P / num_masks
+        loss_dice = (1 - (2 * sums[:, :, 1] + 1) / (sums[:, :, 2] + sums[:, :, 3] + 1)).sum(1) / num_masks
+        ctx.save_for_backward(x, t, coords, sums, src_index)
+        ctx.num_masks, ctx.shape, ctx.dtype = float(num_masks), tuple(preds[0].shape), preds[0].dtype
+        return loss_mask, loss_dice
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mask, grad_dice):
+        x, t, coords, sums, src_index = ctx.saved_tensors
+        heads, K, P = x.shape
+        H, W = ctx.shape[-2:]
+        needs = ctx.needs_input_grad[5:]
+        if not any(needs):
+            return (None,) * (5 + heads)
+        num = 2 * sums[:, :, 1] + 1
+        den = sums[:, :, 2] + sums[:, :, 3] + 1
+        gd = (grad_dice.float() / ctx.num_masks)[:, None]
+        alpha = (grad_mask.float() / (P * ctx.num_masks))[:, None].expand(heads, K)
+        beta = gd * num / (den * den)
+        gamma = 2 * gd / den
+        planes = point_mask_loss_backward(x.view(heads * K, P), t.view(heads * K, P), coords.view(heads * K, P, 2),
+                                          alpha.reshape(-1), beta.reshape(-1), gamma.reshape(-1), H, W).view(heads, K, H, W)
+        rows = src_index.long()
+        grads = []
+        for h in range(heads):
+            if not needs[h]:
+                grads.append(None)
+                continue
+            grad = torch.zeros(ctx.shape, dtype=torch.float32, device=x.device)
+            grad.view(-1, H, W)[rows[h]] = planes[h]                      # matched planes are distinct: a placement
+            grads.append(grad.to(ctx.dtype))
+        return (None,) * 5 + tuple(grads)
+
+
+def point_mask_losses_many(preds, src_index, tgt_planes, tgt_index, coords, num_masks):
+    """`point_mask_losses` of every head with one forward launch and one backward launch.  preds: a sequence of [B, Q, H, W] fp32
+    contiguous device tensors of one shape (each differentiable); src_index, tgt_index [heads, K]; tgt_planes [sum G, Ht, Wt]
+    shared by the heads; coords [heads, K, P, 2].  -> (loss_mask [heads], loss_dice [heads]); head h equals
+    point_mask_losses(preds[h], src_index[h], tgt_planes, tgt_index[h], coords[h], num_masks) up to the order of its K-term sum,
+    and its gradient bit for bit."""
+    preds = list(preds)
+    if not loss_many_supported(preds, tgt_planes):
+        raise RuntimeError("point_mask_losses_many needs contiguous fp32 device planes of one shape, predictions at most %d wide"
+                           % MAX_WIDTH)
+    dev = preds[0].device
+    coords = coords.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if coords.dim() != 4 or coords.shape[0] != len(preds) or coords.shape[3] != 2:
+        raise RuntimeError("coords must be [heads, K, P, 2]")
+    heads, K = len(preds), int(coords.shape[1])
+    src_index, tgt_index = _index_many(src_index, heads, K, dev), _index_many(tgt_index, heads, K, dev)
+    if src_index is None or tgt_index is None:
+        raise RuntimeError("point_mask_losses_many needs src_index and tgt_index [heads, K]")
+    if K == 0 or coords.shape[2] == 0:
+        zero = torch.stack([p.sum() * 0 for p in preds])
+        return zero, zero.clone()
+    return PointMaskLossManyFunction.apply(src_index, tgt_planes.detach(), tgt_index, coords, float(num_masks), *preds)
+
+
+def match_costs_many_supported(preds, tgt_planes, num_points=1, max_targets=1):
+    """Heads of one shape, dtype and device that each pass `match_cost_supported`, a group of heads times the images within the
+    launch grid."""
+    return (_heads_alike(preds) and all(match_cost_supported(p, tgt_planes, num_points, max_targets) for p in preds)
+            and min(len(preds), MAX_HEADS) * preds[0].shape[0] <= MATCH_MAX_BATCH)
+
+
+def match_cost_many_workspace_bytes(num_heads, batch, num_query, max_targets, num_points):
+    """The workspace formula of the header: the single-head size, planned for `batch` images, once per head."""
+    return num_heads * match_cost_workspace_bytes(batch, num_query, max_targets, num_points)
+
+
+def match_costs_many(preds, tgt_planes, starts, counts, coords, cost_mask, cost_dice, max_targets=None):
+    """`match_costs` of every head in one call (pct_point_match_cost_many_f32; more than MAX_HEADS heads in groups).  preds: a
+    sequence of [B, Q, H, W] fp32 contiguous device tensors of one shape; coords [heads, B, P, 2], head h's rows at [h].
+    -> cost [heads, B, Q, max_targets] fp32; cost[h] holds the bits of match_costs(preds[h], ..., coords[h], ...).  No gradient."""
+    preds = list(preds)
+    if not preds or not all(torch.is_tensor(p) and p.is_cuda for p in preds):
+        raise RuntimeError("Not implemented on the CPU")
+    dev = preds[0].device
+    starts = starts.to(device=dev, dtype=torch.int32).contiguous()
+    counts = counts.to(device=dev, dtype=torch.int32).contiguous()
+    gmax = int(counts.max()) if max_targets is None else int(max_targets)
+    coords = coords.detach().to(device=dev, dtype=torch.float32).contiguous()
+    heads = len(preds)
+    if coords.dim() != 4 or coords.shape[3] != 2 or tuple(coords.shape[:2]) != (heads, preds[0].shape[0]):
+        raise RuntimeError("coords must be [heads, B, P, 2]")
+    P = int(coords.shape[2])
+    if not match_costs_many_supported(preds, tgt_planes, P, gmax):
+        raise RuntimeError("match_costs_many needs contiguous fp32 device planes, preds [B, Q, H, W] of one shape, at least one "
+                           "point and target")
+    B, Q, H, W = preds[0].shape
+    if tuple(starts.shape) != (B,) or tuple(counts.shape) != (B,):
+        raise RuntimeError("starts and counts must be vectors of %d entries" % B)
+    Ht, Wt = tgt_planes.shape[-2:]
+    cost = torch.empty((heads, B, Q, gmax), dtype=torch.float32, device=dev)
+    per_head = match_cost_workspace_bytes(B, Q, gmax, P) // 4
+    ws = torch.empty(min(heads, MAX_HEADS) * per_head, dtype=torch.float32, device=dev)     # groups run one after the other
+    for h0, h1 in _head_groups(heads):
+        with torch.cuda.device(dev), _timing.timed("point_match_cost many", cost):
+            rc = _lib.lib().pct_point_match_cost_many_f32(
+                _head_table(preds[h0:h1]), h1 - h0, B, Q, H, W, tgt_planes.data_ptr(), int(tgt_planes.shape[0]), Ht, Wt,
+                starts.data_ptr(), counts.data_ptr(), gmax, coords[h0:h1].data_ptr(), P, float(cost_mask), float(cost_dice),
+                ws.data_ptr(), cost[h0:h1].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc, "point_match_cost_many")
+    return cost

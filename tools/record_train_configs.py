@@ -67,6 +67,8 @@ def build(c):
         model.criterion.point_select = "hip"
     if c.get("hip_match_cost"):
         model.criterion.matcher.match_cost = "hip"
+    if c.get("batched_heads"):
+        model.criterion.loss_heads = model.criterion.matcher.cost_heads = "batched"
     if c.get("hip_emb_loss"):
         model.criterion.emb_loss = "hip"
     if c.get("hip_reid_dice"):
@@ -103,6 +105,9 @@ def selected_configs(argv):
                         if v.get("hip_point_loss")})
     if "--hip-match-cost" in argv:          # and every selected config again with the matcher's cost matrices from the fused kernel
         configs.update({k + " + HIP match cost": dict(v, hip_match_cost=True) for k, v in list(configs.items())})
+    if "--batched-heads" in argv:           # and the configs with all three on the device again with every head in one launch
+        configs.update({k + " + batched heads": dict(v, batched_heads=True) for k, v in list(configs.items())
+                        if v.get("hip_point_loss") and v.get("hip_point_select") and v.get("hip_match_cost")})
     if "--hip-emb-loss" in argv:            # and every selected config again with the pixel-embedding loss on the device
         configs.update({k + " + HIP embedding loss": dict(v, hip_emb_loss=True) for k, v in list(configs.items())})
     if "--hip-attn-train" in argv:          # and every selected config again with the cross-attention's HIP training path
@@ -161,7 +166,7 @@ def main():
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
     flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select",
-                                                "--hip-match-cost", "--hip-emb-loss", "--hip-attn-train", "--hip-reid-dice")]
+                                                "--hip-match-cost", "--batched-heads", "--hip-emb-loss", "--hip-attn-train", "--hip-reid-dice")]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
