@@ -211,8 +211,9 @@ PCT_API int pct_instance_label_map_f32(const float *planes, int num_planes, int 
  *   loss = (alpha sum_b var + beta sum_b dist + gama sum_b reg) / batch,   an image without instances adding 0
  * `loss`: one float on the device.  `status`: one int32 on the device, the number of labels outside 0 .. num_labels; such pixels
  * contribute nothing (they count as background) and nothing synchronises.
- * `table` [batch, num_labels + 1, 68] fp32, fully overwritten, is what the backward needs, per label: [0] n_g, [1] the coefficient
- * c_g = alpha / (batch num_id n_g), [2] sum_p (r_p - delta_v)^2, [3] 0, [4 .. 36) mu_g, [36 .. 68) the vector
+ * `table` [batch, num_labels + 1, 4 + 2 nch] fp32 with nch = 32, 64 or 128 channel slots for channels <= 32, <= 64, <= 128 (68 floats
+ * up to 32 channels), fully overwritten, is what the backward needs, per label: [0] n_g, [1] the coefficient
+ * c_g = alpha / (batch num_id n_g), [2] sum_p (r_p - delta_v)^2, [3] 0, [4 .. 4 + nch) mu_g, [4 + nch .. 4 + 2 nch) the vector
  *   T_g = -c_g S_g / n_g + (beta d dist / d mu_g + gama d reg / d mu_g) / (batch n_g),   S_g = sum_p 2 (r_p - delta_v)(e_p - mu_g) / r_p
  * (everything that reaches a pixel through its centroid; terms with r_p = 0, coinciding centroids and a zero centroid have
  * gradient 0, as torch's norm backward makes them).  Channels past `channels`, absent labels and row 0 are zero.
@@ -223,10 +224,10 @@ PCT_API int pct_instance_label_map_f32(const float *planes, int num_planes, int 
  * atomic, nothing allocated, no host synchronisation: results are bit-identical from call to call and the call may be recorded
  * into a HIP graph.
  * `workspace`: caller-owned, 16-byte aligned, at least
- *   4 * batch * (chunks * (34 * 32 * (num_labels / 32 + 1) + 1) + 4 * ceil(num_labels / 32)) bytes,
+ *   4 * batch * (chunks * ((nch + 2) * 32 * (num_labels / 32 + 1) + 1) + 4 * ceil(num_labels / 32)) bytes   (nch + 2 = 34 up to 32 channels),
  *   subs = ceil(height * width / 256), passes = ceil(subs / 64), chunks = ceil(subs / passes)
  * Status: a non-positive size or count or a missing pointer PCT_ERR_BAD_ARG; misaligned pointer PCT_ERR_ALIGNMENT.
- * Covered: channels <= 32, num_labels <= 1024, height * width < 2^31 - 1, batch <= 65535; anything else PCT_ERR_UNSUPPORTED and
+ * Covered: channels <= 128 (in tiles of 32 channels: one workgroup of the sums per channel tile), num_labels <= 1024, height * width < 2^31 - 1, batch <= 65535; anything else PCT_ERR_UNSUPPORTED and
  * callers keep their torch formulation. */
 PCT_API int pct_discriminative_loss_forward_f32(const float *embedding, const int32_t *labels, int batch, int channels, int height,
                                                 int width, int num_labels, float delta_v, float delta_d, float alpha, float beta,

@@ -22,6 +22,12 @@
 // in ascending pixel order; the chunks are added in ascending order.  The count is an integer sum of the B operands a lane forms
 // anyway; sum (r - delta_v)^2 a lane's running sum over its pixels (even pixels in lanes kh = 0, odd in kh = 1, added at the end).
 // Background (label 0) and labels outside [0, L] belong to no tile: row 0 of the table is zero.
+//
+// More than 32 channels (the model's pixel embedding has CONVS_DIM = 128): the channels go in tiles of 32, one workgroup of passes
+// A and B per (chunk, channel tile, label tile, image), each staging its own 32 rows of es -- a channel's sum is the same fmaf chain
+// as before, and pass B forms r_p over ALL channels (pixel_weight) in every channel tile.  The channel tiles are 1, 2 or 4 (nch =
+// 32, 64, 128 channel slots): a slot of the workspace is nch + 2 floats, a row of the table 4 + 2 nch (mu_g at 4, T_g at 4 + nch).
+// Up to 32 channels that is the layout and the arithmetic of the single-tile kernel, bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,21 +40,24 @@ namespace {
 constexpr int EL_SUB = 256;               // pixels of one pass
 constexpr int EL_ES = EL_SUB + 2;         // row stride of es in words
 constexpr int EL_MAX_CHUNKS = 64;         // of the pixels of an image: bounds the workspace
-constexpr int EL_MAX_E = 32;
+constexpr int EL_MAX_E = 128;             // four channel tiles
+constexpr int EL_CT = 32;                 // channels of one tile: the rows of the MFMA
 constexpr int EL_MAX_L = 1024;
-constexpr int EL_SLOT = 34;               // floats of one label of one chunk: 32 channel sums, the count (int), sum (r - dv)^2
-constexpr int EL_ROW = 68;                // floats of one label of the table
-constexpr int EL_N = 0, EL_C = 1, EL_Q = 2, EL_MU = 4, EL_T = 36;      // count, c_g, sum (r - dv)^2, mu_g[32], T_g[32] (S_g before C)
+constexpr int EL_SLOT = 34;               // floats of one label of one chunk at nch = 32: nch channel sums, the count (int), sum (r - dv)^2
+constexpr int EL_ROW = 68;                // floats of one label of the table at nch = 32: 4 + 2 nch
+constexpr int EL_N = 0, EL_C = 1, EL_Q = 2, EL_MU = 4;      // count, c_g, sum (r - dv)^2, mu_g[nch]; then T_g[nch] (S_g before C)
 constexpr int EL_CBLOCK = 256;            // pass C: 32 labels x 8 slices of the other labels
+static_assert(EL_SLOT == EL_CT + 2 && EL_ROW == 4 + 2 * EL_CT, "the single-tile layout");
 
 typedef float el_f16 __attribute__((ext_vector_type(16)));
 
 struct EmbLossPlan {
   int passes, chunks, tiles, lblocks;     // passes of EL_SUB pixels per chunk; tiles of 32 labels over 0 .. L; blocks of pass C
+  int ctiles, nch, slot, row;             // channel tiles (1, 2, 4), channel slots 32 ctiles, floats of a workspace slot / table row
   long long partial, bad, part;           // offsets (floats) of the three regions of the workspace, `partial` = 0
 };
 
-inline EmbLossPlan emb_loss_plan(const int B, const long long P, const int L)
+inline EmbLossPlan emb_loss_plan(const int B, const long long P, const int L, const int E)
 {
   EmbLossPlan m;
   const long long subs = (P + EL_SUB - 1) / EL_SUB;
@@ -56,8 +65,12 @@ inline EmbLossPlan emb_loss_plan(const int B, const long long P, const int L)
   m.chunks = (int)((subs + m.passes - 1) / m.passes);
   m.tiles = L / 32 + 1;
   m.lblocks = (L + 31) / 32;
+  m.ctiles = E <= 32 ? 1 : E <= 64 ? 2 : 4;
+  m.nch = EL_CT * m.ctiles;
+  m.slot = m.nch + 2;
+  m.row = 4 + 2 * m.nch;
   m.partial = 0;
-  m.bad = (long long)B * m.chunks * m.tiles * 32 * EL_SLOT;
+  m.bad = (long long)B * m.chunks * m.tiles * 32 * m.slot;
   m.part = m.bad + (long long)B * m.chunks;
   return m;
 }
@@ -81,11 +94,12 @@ __global__ __launch_bounds__(64) void sums_kernel(const float *__restrict__ emb,
                                                   const float *__restrict__ table, const int E, const int P, const int L,
                                                   const float delta_v, const EmbLossPlan plan, float *__restrict__ ws)
 {
-  __shared__ float es[EL_MAX_E * EL_ES];
+  __shared__ float es[EL_CT * EL_ES];
   __shared__ float qs[EL_SUB];
   __shared__ int ls[EL_SUB];
-  const int chunk = blockIdx.x, tile = blockIdx.y, b = blockIdx.z;
+  const int chunk = blockIdx.x % plan.chunks, ct = blockIdx.x / plan.chunks, tile = blockIdx.y, b = blockIdx.z;
   const int lane = threadIdx.x, col = lane & 31, kh = lane >> 5;
+  const int c0 = ct * EL_CT, ce = min(EL_CT, E - c0);                       // this workgroup's channels c0 .. c0 + ce (ce may be <= 0)
   const float *eb = emb + (size_t)b * E * P;
   const int *lb = labels + (size_t)b * P;
   const int g0 = tile * 32;
@@ -122,21 +136,21 @@ __global__ __launch_bounds__(64) void sums_kernel(const float *__restrict__ emb,
       if ((unsigned)(g - g0) < 32u) {
         const float *e = eb + (p0 + pix);
         if (PASS_B) {
-          const float *mu = table + ((size_t)b * (L + 1) + g) * EL_ROW + EL_MU;
+          const float *mu = table + ((size_t)b * (L + 1) + g) * plan.row + EL_MU;
           float r;
           const float w = pixel_weight(e, (size_t)P, mu, E, delta_v, r);
-          for (int c = 0; c < E; ++c) es[c * EL_ES + pix] = w * (e[(size_t)c * P] - mu[c]);
+          for (int c = 0; c < ce; ++c) es[c * EL_ES + pix] = w * (e[(size_t)(c0 + c) * P] - mu[c0 + c]);
           qs[pix] = (r - delta_v) * (r - delta_v);
         } else {
-          for (int c = 0; c < E; ++c) es[c * EL_ES + pix] = e[(size_t)c * P];
+          for (int c = 0; c < ce; ++c) es[c * EL_ES + pix] = e[(size_t)(c0 + c) * P];
         }
       } else {
-        for (int c = 0; c < E; ++c) es[c * EL_ES + pix] = 0.f;
+        for (int c = 0; c < ce; ++c) es[c * EL_ES + pix] = 0.f;
         if (PASS_B) qs[pix] = 0.f;
       }
     }
     __syncthreads();
-    const bool row_ok = col < E;
+    const bool row_ok = col < ce;
 #pragma unroll 4
     for (int s = 0; s < EL_SUB / 2; ++s) {
       const int pix = 2 * s + kh;
@@ -149,19 +163,19 @@ __global__ __launch_bounds__(64) void sums_kernel(const float *__restrict__ emb,
   }
 
   // acc[r] = D[row 8 (r / 4) + 4 kh + r % 4][column col]: row = channel, column = label of the tile
-  float *slot = ws + (((size_t)b * plan.chunks + chunk) * plan.tiles * 32 + g0 + col) * EL_SLOT;
+  float *slot = ws + (((size_t)b * plan.chunks + chunk) * plan.tiles * 32 + g0 + col) * plan.slot;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int row = 8 * (r / 4) + 4 * kh + r % 4;
-    if (row < E) slot[row] = acc[r];
+    if (row < ce) slot[c0 + row] = acc[r];
   }
   cnt += __shfl_xor(cnt, 32, 64);                                           // even pixels + odd pixels
   qsum += __shfl_xor(qsum, 32, 64);
-  if (kh == 0) {
-    slot[32] = __int_as_float(cnt);
-    slot[33] = qsum;
+  if (kh == 0 && ct == 0) {                                                 // (every channel tile counts the same: the first writes)
+    slot[plan.nch] = __int_as_float(cnt);
+    slot[plan.nch + 1] = qsum;
   }
-  if (!PASS_B && tile == 0) {
+  if (!PASS_B && tile == 0 && ct == 0) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
     if (lane == 0) reinterpret_cast<int *>(ws + plan.bad)[(size_t)b * plan.chunks + chunk] = bad;
@@ -177,24 +191,25 @@ __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ 
 {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  const int k = (int)(i % EL_SLOT);
-  const long long bg = i / EL_SLOT;
+  const int nch = plan.nch, EL_T = EL_MU + nch;
+  const int k = (int)(i % plan.slot);
+  const long long bg = i / plan.slot;
   const int g = (int)(bg % (L + 1)), b = (int)(bg / (L + 1));
-  const size_t per_chunk = (size_t)plan.tiles * 32 * EL_SLOT;
-  const float *w = ws + (size_t)b * plan.chunks * per_chunk + (size_t)g * EL_SLOT;
-  float *row = table + (size_t)bg * EL_ROW;
+  const size_t per_chunk = (size_t)plan.tiles * 32 * plan.slot;
+  const float *w = ws + (size_t)b * plan.chunks * per_chunk + (size_t)g * plan.slot;
+  float *row = table + (size_t)bg * plan.row;
   float sum = 0.f;
   int n = 0;
-  const bool has_sum = g > 0 && (k < E || (MODE == 1 && k == 33));
+  const bool has_sum = g > 0 && (k < E || (MODE == 1 && k == nch + 1));
   for (int ch = 0; ch < plan.chunks; ++ch, w += per_chunk) {
     if (has_sum) sum += w[k];
-    if (MODE == 0 && g > 0) n += __float_as_int(w[32]);
+    if (MODE == 0 && g > 0) n += __float_as_int(w[nch]);
   }
   if (MODE == 0) {
-    if (k < 32) {
+    if (k < nch) {
       row[EL_MU + k] = (has_sum && n > 0) ? sum / (float)n : 0.f;
       row[EL_T + k] = 0.f;
-    } else if (k == 32) {
+    } else if (k == nch) {
       row[EL_N] = (float)n;
       row[EL_C] = 0.f;
     } else {
@@ -202,19 +217,21 @@ __global__ __launch_bounds__(256) void combine_kernel(const float *__restrict__ 
       row[3] = 0.f;
     }
   } else {
-    if (k < 32) row[EL_T + k] = has_sum ? sum : 0.f;
-    else if (k == 33) row[EL_Q] = has_sum ? sum : 0.f;
+    if (k < nch) row[EL_T + k] = has_sum ? sum : 0.f;
+    else if (k == nch + 1) row[EL_Q] = has_sum ? sum : 0.f;
   }
 }
 
 // Pass C.  Thread (il, s) = (tid / 8, tid % 8): label i = 32 blockIdx.x + il + 1 against the labels j = 1 + s, 9 + s, ...; the
 // eight slices are added by a butterfly over the lanes (the same sum in every lane).  Only present labels (count > 0) enter.
+template <int NCH>
 __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__ table, const int B, const int E, const int L,
                                                              const float delta_d, const float alpha, const float beta,
                                                              const float gama, const EmbLossPlan plan, float *__restrict__ ws)
 {
   __shared__ int s_count[EL_CBLOCK / 64];
   __shared__ float s_part[EL_CBLOCK / 64][3];
+  constexpr int EL_ROW = 4 + 2 * NCH, EL_T = EL_MU + NCH;                   // this instance's table row
   const int b = blockIdx.y, tid = threadIdx.x, il = tid >> 3, s = tid & 7, lane = tid & 63, wave = tid >> 6;
   float *tb = table + (size_t)b * (L + 1) * EL_ROW;
 
@@ -234,9 +251,9 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
   const float n_i = valid ? row[EL_N] : 0.f;
   const bool here = n_i > 0.f;
 
-  float mu[EL_MAX_E], acc[EL_MAX_E];
+  float mu[NCH], acc[NCH];
 #pragma unroll
-  for (int c = 0; c < EL_MAX_E; ++c) {
+  for (int c = 0; c < NCH; ++c) {
     mu[c] = (c < E && here) ? row[EL_MU + c] : 0.f;
     acc[c] = 0.f;
   }
@@ -245,9 +262,9 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
     for (int j = 1 + s; j <= L; j += 8) {
       const float *rj = tb + (size_t)j * EL_ROW;
       if (!here || j == i || !(rj[EL_N] > 0.f)) continue;
-      float d2 = 0.f, diff[EL_MAX_E];
+      float d2 = 0.f, diff[NCH];
 #pragma unroll
-      for (int c = 0; c < EL_MAX_E; ++c) {
+      for (int c = 0; c < NCH; ++c) {
         diff[c] = 0.f;
         if (c < E) {
           diff[c] = mu[c] - rj[EL_MU + c];
@@ -259,7 +276,7 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
       if (d > 0.f && h > 0.f) {
         const float k = h / d;
 #pragma unroll
-        for (int c = 0; c < EL_MAX_E; ++c)
+        for (int c = 0; c < NCH; ++c)
           if (c < E) acc[c] = fmaf(k, diff[c], acc[c]);
       }
     }
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
     for (int m = 1; m <= 4; m <<= 1) {
       dist += __shfl_xor(dist, m, 64);
 #pragma unroll
-      for (int c = 0; c < EL_MAX_E; ++c)
+      for (int c = 0; c < NCH; ++c)
         if (c < E) acc[c] += __shfl_xor(acc[c], m, 64);
     }
   }
@@ -276,7 +293,7 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
   if (here && s == 0) {
     float m2 = 0.f;
 #pragma unroll
-    for (int c = 0; c < EL_MAX_E; ++c)
+    for (int c = 0; c < NCH; ++c)
       if (c < E) m2 = fmaf(mu[c], mu[c], m2);
     const float norm = sqrtf(m2), fB = (float)B, fid = (float)num_id;
     var_i = row[EL_Q] / n_i;
@@ -288,7 +305,7 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
     const float inv = 1.f / (fB * n_i);
     row[EL_C] = c_i;
 #pragma unroll
-    for (int c = 0; c < EL_MAX_E; ++c)
+    for (int c = 0; c < NCH; ++c)
       if (c < E) row[EL_T + c] = -c_i * row[EL_T + c] / n_i + (kd * acc[c] + kr * mu[c]) * inv;
   }
   // the workgroup's three sums: a butterfly inside each wave, the waves in ascending order
@@ -360,7 +377,8 @@ __global__ __launch_bounds__(64) void finish_kernel(const float *__restrict__ ws
 __global__ __launch_bounds__(256) void emb_loss_backward_kernel(const float *__restrict__ emb, const int *__restrict__ labels,
                                                                 const float *__restrict__ table,
                                                                 const float *__restrict__ grad_out, const int E, const int P,
-                                                                const int L, const float delta_v, float *__restrict__ grad)
+                                                                const int L, const int nch, const float delta_v,
+                                                                float *__restrict__ grad)
 {
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
@@ -371,8 +389,8 @@ __global__ __launch_bounds__(256) void emb_loss_backward_kernel(const float *__r
     for (int c = 0; c < E; ++c) grad[at + (size_t)c * P] = 0.f;
     return;
   }
-  const float *row = table + ((size_t)b * (L + 1) + g) * EL_ROW;
-  const float *mu = row + EL_MU, *T = row + EL_T;
+  const float *row = table + ((size_t)b * (L + 1) + g) * (4 + 2 * nch);
+  const float *mu = row + EL_MU, *T = row + EL_MU + nch;
   const float go = *grad_out;
   float r;
   const float k = row[EL_C] * pixel_weight(emb + at, (size_t)P, mu, E, delta_v, r);
@@ -413,12 +431,6 @@ int emb_loss_geometry_status(int B, int E, int h, int w, int L)
   return PCT_OK;
 }
 
-long long emb_loss_workspace_floats(int B, int h, int w, int L)
-{
-  const EmbLossPlan plan = emb_loss_plan(B, (long long)h * w, L);
-  return plan.part + 4LL * B * plan.lblocks;
-}
-
 int launch_instance_label_map(const float *planes, int num_planes, int Ht, int Wt, const int *start, const int *count, int B, int h,
                               int w, int *labels, hipStream_t stream)
 {
@@ -435,10 +447,10 @@ int launch_emb_loss_forward(const float *emb, const int *labels, int B, int E, i
 {
   if (const int rc = emb_loss_geometry_status(B, E, h, w, L); rc != PCT_OK) return rc;
   const int P = h * w;
-  const EmbLossPlan plan = emb_loss_plan(B, P, L);
+  const EmbLossPlan plan = emb_loss_plan(B, P, L, E);
   float *ws = static_cast<float *>(workspace);
-  const dim3 grid((unsigned)plan.chunks, (unsigned)plan.tiles, (unsigned)B);
-  const long long total = (long long)B * (L + 1) * EL_SLOT;
+  const dim3 grid((unsigned)(plan.chunks * plan.ctiles), (unsigned)plan.tiles, (unsigned)B);       // at most 64 x 4 in x
+  const long long total = (long long)B * (L + 1) * plan.slot;
   const dim3 cgrid((unsigned)((total + 255) / 256));
   sums_kernel<false><<<grid, dim3(64), 0, stream>>>(emb, labels, table, E, P, L, delta_v, plan, ws);
   if (const int rc = (int)hipGetLastError(); rc != 0) return rc;
@@ -448,8 +460,10 @@ int launch_emb_loss_forward(const float *emb, const int *labels, int B, int E, i
   if (const int rc = (int)hipGetLastError(); rc != 0) return rc;
   combine_kernel<1><<<cgrid, dim3(256), 0, stream>>>(ws, E, L, total, plan, table);
   if (const int rc = (int)hipGetLastError(); rc != 0) return rc;
-  centroid_kernel<<<dim3((unsigned)plan.lblocks, (unsigned)B), dim3(EL_CBLOCK), 0, stream>>>(table, B, E, L, delta_d, alpha, beta,
-                                                                                           gama, plan, ws);
+  const dim3 pgrid((unsigned)plan.lblocks, (unsigned)B);
+  if (plan.nch == 32) centroid_kernel<32><<<pgrid, dim3(EL_CBLOCK), 0, stream>>>(table, B, E, L, delta_d, alpha, beta, gama, plan, ws);
+  else if (plan.nch == 64) centroid_kernel<64><<<pgrid, dim3(EL_CBLOCK), 0, stream>>>(table, B, E, L, delta_d, alpha, beta, gama, plan, ws);
+  else centroid_kernel<128><<<pgrid, dim3(EL_CBLOCK), 0, stream>>>(table, B, E, L, delta_d, alpha, beta, gama, plan, ws);
   if (const int rc = (int)hipGetLastError(); rc != 0) return rc;
   finish_kernel<<<dim3(1), dim3(64), 0, stream>>>(ws, B, alpha, beta, gama, plan, loss, status);
   return (int)hipGetLastError();
@@ -460,8 +474,9 @@ int launch_emb_loss_backward(const float *emb, const int *labels, const float *t
 {
   if (const int rc = emb_loss_geometry_status(B, E, h, w, L); rc != PCT_OK) return rc;
   const int P = h * w;
+  const int nch = emb_loss_plan(B, P, L, E).nch;
   emb_loss_backward_kernel<<<dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, stream>>>(emb, labels, table, grad_out, E,
-                                                                                                    P, L, delta_v, grad_emb);
+                                                                                                    P, L, nch, delta_v, grad_emb);
   return (int)hipGetLastError();
 }
 

@@ -12,12 +12,12 @@ import torch
 
 from . import _lib, _timing
 
-MAX_CHANNELS = 32     # csrc/embedding_loss.hip: EL_MAX_E
+MAX_CHANNELS = 128    # csrc/embedding_loss.hip: EL_MAX_E (channel tiles of 32: 1, 2 or 4 of them)
 MAX_LABELS = 1024     # EL_MAX_L, the LSAP kernel's declared target limit
 PIXELS_PER_PASS = 256   # EL_SUB
 MAX_CHUNKS = 64       # EL_MAX_CHUNKS
-SLOT = 34             # EL_SLOT
-TABLE_ROW = 68        # EL_ROW
+SLOT = 34             # EL_SLOT: floats of a workspace slot up to 32 channels (`channel_slots(E) + 2` in general)
+TABLE_ROW = 68        # EL_ROW: floats of a table row up to 32 channels (`table_row(E)` in general)
 UNSUPPORTED = -4      # PCT_ERR_UNSUPPORTED
 
 
@@ -44,9 +44,20 @@ def chunks(pixels):
     return passes, -(-subs // passes)
 
 
-def workspace_bytes(batch, pixels, num_labels):
+def channel_slots(channels):
+    """nch of include/pctrans_hip_train.h: 32, 64 or 128 channel slots for up to 32, 64, 128 channels."""
+    return 32 if channels <= 32 else 64 if channels <= 64 else 128
+
+
+def table_row(channels):
+    """Floats of one label's row of the table: n_g, c_g, sum (r - delta_v)^2, 0, mu_g[nch], T_g[nch]."""
+    return 4 + 2 * channel_slots(channels)
+
+
+def workspace_bytes(batch, pixels, num_labels, channels=32):
     """The workspace formula of include/pctrans_hip_train.h."""
-    return 4 * batch * (chunks(pixels)[1] * (SLOT * 32 * (num_labels // 32 + 1) + 1) + 4 * -(-num_labels // 32))
+    slot = channel_slots(channels) + 2
+    return 4 * batch * (chunks(pixels)[1] * (slot * 32 * (num_labels // 32 + 1) + 1) + 4 * -(-num_labels // 32))
 
 
 def instance_label_map(planes, starts, counts, size):
@@ -74,7 +85,7 @@ def instance_label_map(planes, starts, counts, size):
 
 
 def discriminative_loss_forward(embedding, labels, num_labels, delta_v, delta_d, alpha, beta, gama):
-    """-> (loss [] fp32, table [B, num_labels + 1, TABLE_ROW] fp32, status [] int32) of pct_discriminative_loss_forward_f32."""
+    """-> (loss [] fp32, table [B, num_labels + 1, table_row(E)] fp32, status [] int32) of pct_discriminative_loss_forward_f32."""
     if not embedding.is_cuda:
         raise RuntimeError("Not implemented on the CPU")
     dev = embedding.device
@@ -82,8 +93,8 @@ def discriminative_loss_forward(embedding, labels, num_labels, delta_v, delta_d,
     L = int(num_labels)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     status = torch.empty((), dtype=torch.int32, device=dev)
-    table = torch.empty((B, L + 1, TABLE_ROW), dtype=torch.float32, device=dev)
-    ws = torch.empty(workspace_bytes(B, h * w, L) // 4, dtype=torch.float32, device=dev)
+    table = torch.empty((B, L + 1, table_row(E)), dtype=torch.float32, device=dev)
+    ws = torch.empty(workspace_bytes(B, h * w, L, E) // 4, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev), _timing.timed("discriminative_loss forward", loss):
         rc = _lib.lib().pct_discriminative_loss_forward_f32(
             embedding.data_ptr(), labels.data_ptr(), B, E, h, w, L, float(delta_v), float(delta_d), float(alpha), float(beta),

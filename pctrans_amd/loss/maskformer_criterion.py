@@ -151,7 +151,7 @@ class SetCriterion(nn.Module):
         self.point_select = _point_loss.select_default()
         # "torch": loss_embedding as written below.  "hip": the label map and the loss on the device kernels of
         # pctrans_amd/embedding_loss.py where their conditions hold (device tensors, target masks of one size, fp32 contiguous
-        # embedding, covered geometry), the code below otherwise.  A plain attribute; process default from PCT_EMB_LOSS
+        # embedding -- a channels-last one is copied --, covered geometry), the code below otherwise.  A plain attribute; process default from PCT_EMB_LOSS
         self.emb_loss = _embedding_loss.default()
         # "each": loss_masks head by head, as the loops of forward reach them.  "batched": where every head meets the conditions
         # of the "hip" loss path, the selection, the loss and its backward of ALL heads run as one launch each before the loops
@@ -287,8 +287,12 @@ class SetCriterion(nn.Module):
 
     def _loss_embedding_hip(self, emb, targets, alpha, beta, gama):
         """loss_embedding on the device kernels: the label map from the cached target planes, the loss with L = the largest
-        target count.  No host synchronisation.  None when the conditions do not hold."""
+        target count.  No host synchronisation.  None when the conditions do not hold.  The pixel decoder hands its maps over
+        channels-last (dense, not contiguous): the kernels read [B, E, h, w] planes, so such a map is copied once, inside autograd."""
         counts = [int(t["masks"].shape[0]) for t in targets]
+        if (torch.is_tensor(emb) and emb.is_cuda and emb.dtype == torch.float32 and emb.dim() == 4 and not emb.is_contiguous()
+                and emb.shape[1] <= _embedding_loss.MAX_CHANNELS):
+            emb = emb.contiguous()
         if not counts or len(counts) != emb.shape[0] or not _embedding_loss.supported(emb, max(counts)):
             return None
         got = self._hip_target_planes(targets, emb)

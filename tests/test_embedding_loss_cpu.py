@@ -82,7 +82,7 @@ def test_argument_validation_returns_status_codes_without_a_launch():
     assert fwd(p, p, 2, 8, 4, 4, 3, 0.5, 3.0, 1.0, 1.0, 0.001, p, None, p, p, None) == BAD
     assert fwd(p, p, 2, 8, 4, 4, 3, 0.5, 3.0, 1.0, 1.0, 0.001, p + 4, p, p, p, None) == ALIGN        # workspace: 16 bytes
     assert fwd(p, p, 2, 8, 4, 4, 3, 0.5, 3.0, 1.0, 1.0, 0.001, p, p, p + 2, p, None) == ALIGN
-    assert fwd(p, p, 2, 33, 4, 4, 3, 0.5, 3.0, 1.0, 1.0, 0.001, p, p, p, p, None) == UNSUP
+    assert fwd(p, p, 2, 129, 4, 4, 3, 0.5, 3.0, 1.0, 1.0, 0.001, p, p, p, p, None) == UNSUP
     assert fwd(p, p, 2, 8, 4, 4, 1025, 0.5, 3.0, 1.0, 1.0, 0.001, p, p, p, p, None) == UNSUP
     assert fwd(p, p, 2, 8, 65536, 65536, 3, 0.5, 3.0, 1.0, 1.0, 0.001, p, p, p, p, None) == UNSUP
     # (emb, labels, table, grad_out, B, E, h, w, L, delta_v, grad, stream)
@@ -90,7 +90,7 @@ def test_argument_validation_returns_status_codes_without_a_launch():
     assert bwd(p, p, p, p, 2, 8, 4, 0, 3, 0.5, p, None) == BAD
     assert bwd(p, p, p, None, 2, 8, 4, 4, 3, 0.5, p, None) == BAD
     assert bwd(p, p, p, p, 2, 8, 4, 4, 3, 0.5, p + 1, None) == ALIGN
-    assert bwd(p, p, p, p, 2, 33, 4, 4, 3, 0.5, p, None) == UNSUP
+    assert bwd(p, p, p, p, 2, 129, 4, 4, 3, 0.5, p, None) == UNSUP
     assert bwd(p, p, p, p, 2, 8, 4, 4, 1025, 0.5, p, None) == UNSUP
 
 

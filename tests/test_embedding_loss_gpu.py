@@ -243,20 +243,96 @@ def test_graph_capture_replays_the_eager_bits():
 
 
 def test_unsupported_geometry_status_codes():
-    emb = torch.zeros(1, 33, 4, 4, device=DEV)
+    emb = torch.zeros(1, 129, 4, 4, device=DEV)
     lab = torch.zeros(1, 4, 4, dtype=torch.int32, device=DEV)
     buf = torch.zeros(1 << 16, device=DEV)
     st = torch.zeros((), dtype=torch.int32, device=DEV)
     lib, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
     args = (0.5, 3.0, 1.0, 1.0, 0.001, buf.data_ptr(), buf.data_ptr(), buf.data_ptr(), st.data_ptr(), stream)
-    assert lib.pct_discriminative_loss_forward_f32(emb.data_ptr(), lab.data_ptr(), 1, 33, 4, 4, 3, *args) == embedding_loss.UNSUPPORTED
+    assert lib.pct_discriminative_loss_forward_f32(emb.data_ptr(), lab.data_ptr(), 1, 129, 4, 4, 3, *args) == embedding_loss.UNSUPPORTED
     assert lib.pct_discriminative_loss_forward_f32(emb.data_ptr(), lab.data_ptr(), 1, 32, 4, 4, 1025, *args) == embedding_loss.UNSUPPORTED
-    assert lib.pct_discriminative_loss_backward_f32(emb.data_ptr(), lab.data_ptr(), buf.data_ptr(), buf.data_ptr(), 1, 33, 4, 4, 3,
+    assert lib.pct_discriminative_loss_backward_f32(emb.data_ptr(), lab.data_ptr(), buf.data_ptr(), buf.data_ptr(), 1, 129, 4, 4, 3,
                                                     0.5, buf.data_ptr(), stream) == embedding_loss.UNSUPPORTED
     assert not embedding_loss.supported(emb, 3) and not embedding_loss.supported(emb[:, :32].contiguous(), 1025)
     assert embedding_loss.supported(emb[:, :32].contiguous(), 1024)
     with pytest.raises(RuntimeError):
         embedding_loss.discriminative_loss(emb, lab, 3)
+
+
+@pytest.mark.parametrize("E,h,w,L", [(33, 19, 17, 5), (64, 19, 17, 33), (80, 19, 17, 5), (96, 16, 16, 3), (128, 32, 32, 6), (128, 19, 17, 33)])
+def test_more_than_32_channels_against_float64(E, h, w, L):
+    """The channels in tiles of 32 (two tiles at 33 .. 64, four above, the last ones partly or wholly empty at 33, 80 and 96: at
+    80 the fourth tile starts past the last channel and must write nothing): 128 is
+    the width of the model's own pixel embedding (CONVS_DIM), which the criterion hands to this loss.  Same reference and bounds as
+    the narrow cases; 19 x 17 pixels are two passes with a ragged end."""
+    name = "near and far centroids"
+    emb, lab = R.family(name, E, h, w, L)
+    want, wgrad = R.loss64(emb, lab, L, **R.PARAMS)
+    lb, gb = R.bounds(emb, lab, L, **R.PARAMS)
+    loss, grad, status = _run(emb, lab, L)
+    err = abs(float(loss) - want)
+    excess = float(((grad.cpu().double() - wgrad).abs() - gb).max())
+    print("E=%d %dx%d L=%d: loss %.9g err %.3g bound %.3g; gradient excess over its bound %.3g (largest bound %.3g)"
+          % (E, h, w, L, want, err, lb, excess, float(gb.max())))
+    assert err <= lb and excess <= 0 and int(status) == 0
+    again = _run(emb, lab, L)
+    assert torch.equal(loss, again[0]) and torch.equal(grad, again[1])
+    outside = (R.clean_labels(lab, L) == 0)[:, None].expand_as(grad)
+    assert float(grad.cpu()[outside].abs().max() if outside.any() else 0.0) == 0.0
+
+
+@pytest.mark.parametrize("E", [40, 80, 128])
+def test_guard_bands_of_the_wide_layouts(E):
+    """test_guard_bands at 64 and 128 channel slots: the workspace slot is nch + 2 floats and the table row 4 + 2 nch there, and
+    at 80 channels the fourth channel tile is empty.  The margins around every output stay as they were."""
+    h, w, L, B = 13, 11, 33, 2
+    emb, lab = R.family("near and far centroids", E, h, w, L)
+    emb, lab = emb.to(DEV), lab.to(DEV)
+    lib, stream = _lib.lib(), torch.cuda.current_stream().cuda_stream
+    fb, ib = -7.25, -77
+    ws_buf, ws = _guarded((embedding_loss.workspace_bytes(B, h * w, L, E) // 4,), torch.float32, fb)
+    tb_buf, table = _guarded((B, L + 1, embedding_loss.table_row(E)), torch.float32, fb)
+    lo_buf, loss = _guarded((), torch.float32, fb)
+    st_buf, status = _guarded((), torch.int32, ib)
+    gr_buf, grad = _guarded((B, E, h, w), torch.float32, fb)
+    assert ws.data_ptr() % 16 == 0 and embedding_loss.table_row(E) == 4 + 2 * (64 if E <= 64 else 128)
+    rc = lib.pct_discriminative_loss_forward_f32(emb.data_ptr(), lab.data_ptr(), B, E, h, w, L, 0.5, 3.0, 1.0, 1.0, 0.001,
+                                                 ws.data_ptr(), table.data_ptr(), loss.data_ptr(), status.data_ptr(), stream)
+    assert rc == 0
+    go = torch.ones((), device=DEV)
+    rc = lib.pct_discriminative_loss_backward_f32(emb.data_ptr(), lab.data_ptr(), table.data_ptr(), go.data_ptr(), B, E, h, w, L,
+                                                  0.5, grad.data_ptr(), stream)
+    assert rc == 0
+    torch.cuda.synchronize()
+    for buf, fill in ((ws_buf, fb), (tb_buf, fb), (lo_buf, fb), (st_buf, ib), (gr_buf, fb)):
+        assert _margins_untouched(buf, fill)
+    want = _run(emb.cpu(), lab.cpu(), L)
+    assert torch.equal(loss, want[0]) and torch.equal(grad, want[1]) and int(status) == 0
+    assert not bool((table == fb).any())                                   # the table is fully overwritten
+
+
+def test_set_criterion_copies_a_channels_last_embedding(monkeypatch):
+    """The pixel decoder hands its 128-channel map over channels-last: dense, not contiguous.  With emb_loss = "hip" the
+    criterion copies it, the kernels get [B, E, h, w] planes, and the gradient comes back through the copy to the map itself."""
+    g = torch.Generator().manual_seed(11)
+    emb = torch.randn(2, 128, 13, 18, generator=g)
+    targets = _targets([(50, 70)] * 2, (7, 40))
+    labels = R.label_map_reference([t["masks"] for t in targets], (13, 18)).cpu()
+    want, wgrad = R.loss64(emb, labels, 40)
+    lb, gb = R.bounds(emb, labels, 40)
+    calls = []
+    real = embedding_loss.discriminative_loss
+    monkeypatch.setattr(embedding_loss, "discriminative_loss",
+                        lambda *a, **k: calls.append((a[2], a[0].is_contiguous())) or real(*a, **k))
+    x = emb.to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    assert not x.is_contiguous() and x.is_leaf
+    loss = _criterion("hip").loss_embedding(x, targets)["loss_emb"]
+    loss.backward()
+    assert calls == [(40, True)]                                           # the device path ran, on a contiguous copy
+    assert abs(float(loss) - want) <= lb
+    assert x.grad is not None and x.grad.shape == x.shape
+    assert float(((x.grad.cpu().double() - wgrad).abs() - gb).max()) <= 0
+    assert int(loss.status) == 0
 
 
 def test_the_largest_covered_label_count():

@@ -27,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from pctrans_amd.arch import maskformer as mfm  # noqa: E402
 from pctrans_amd.arch.resnet import ResNet  # noqa: E402
 from pctrans_amd.config import get_cfg  # noqa: E402
+import train_switches  # noqa: E402  (tests/)
 
 CONFIGS = {
     "configs[2] CVPPP-PCTrans.yaml": dict(dataset="CVPPP", N=2, H=448, W=448, Q=100, G=20),
@@ -53,26 +54,9 @@ def build(c):
         targets.append({"masks": masks, "labels": torch.ones(G, dtype=torch.long, device="cuda"),
                         "fg_masks": (masks.sum(0) > 0).float(), "center_points": centers})
     opt = torch.optim.AdamW(model.parameters(), lr=1e-4, weight_decay=0.05)
-    if c.get("hip_mask_head"):
-        for m in model.modules():
-            if hasattr(m, "dmh_train"):
-                m.dmh_train = "hip"
-    if c.get("hip_attn_train"):
-        for m in model.modules():
-            if hasattr(m, "attn_train"):
-                m.attn_train = "hip"
-    if c.get("hip_point_loss"):
-        model.criterion.point_loss = model.criterion.matcher.point_sample = "hip"
-    if c.get("hip_point_select"):
-        model.criterion.point_select = "hip"
-    if c.get("hip_match_cost"):
-        model.criterion.matcher.match_cost = "hip"
-    if c.get("batched_heads"):
-        model.criterion.loss_heads = model.criterion.matcher.cost_heads = "batched"
-    if c.get("hip_emb_loss"):
-        model.criterion.emb_loss = "hip"
-    if c.get("hip_reid_dice"):
-        model.sem_seg_head.predictor.reid_dice = "hip"
+    for s in train_switches.SWITCHES:             # the switches' table of the tests: one place says how each is set
+        if s["config_key"] is not None and c.get(s["config_key"]):
+            train_switches.set_switch(model, s["name"], True)
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -165,8 +149,8 @@ def main():
     the same fragility).  `--rounds R` repeats the whole list R times, so that flag-off and flag-on steps alternate on one
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
-    flags = [a for a in sys.argv[1:] if a in ("--graph-front", "--graph-decoder", "--hip-mask-head", "--hip-point-loss", "--hip-point-select",
-                                                "--hip-match-cost", "--batched-heads", "--hip-emb-loss", "--hip-attn-train", "--hip-reid-dice")]
+    known = ["--graph-front", "--graph-decoder"] + [s["flag"] for s in train_switches.SWITCHES if s["flag"] is not None]
+    flags = [a for a in sys.argv[1:] if a in known]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
         name = sys.argv[sys.argv.index("--only") + 1]
