@@ -201,6 +201,8 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_reid.h"
 /* instance targets from label maps (the trainer's target preparation), behind pctrans_amd.targets.prepare_instance_targets */
 #include "pctrans_hip_targets.h"
+/* the backward of the fused MSDeformAttn front-end, behind MSDeformAttn.train_front = "hip" */
+#include "pctrans_hip_msda_train.h"
 
 /* ---- fused residual add + LayerNorm:  out = LayerNorm(x + y) * gamma + beta  over the last dimension ----------
  * Replaces the `x + dropout(y)` / `nn.LayerNorm` pairs of the encoder and decoder layers in eval mode

@@ -139,6 +139,14 @@ TARGETS_SYMBOLS = {
                                     "tests/test_targets_gpu.py"),
 }
 
+# Entry point of the backward of the fused MSDeformAttn front-end (include/pctrans_hip_msda_train.h; pctrans_amd/msda_train.py,
+# reached with MSDeformAttn.train_front = "hip").  A table of its own, as the targets': name -> (argtypes, restype, the test
+# module that checks the entry against float64)
+MSDA_TRAIN_SYMBOLS = {
+    "pct_ms_deform_attn_fused_backward_f32": ([_vp] * 4 + [ctypes.c_longlong] + [_vp] * 3 + [_i] * 8 + [_vp] * 5, _i,
+                                              "tests/test_msda_fused_train_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -157,7 +165,8 @@ def lib():
     l = ctypes.CDLL(LIB_PATH)
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
-            + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())]:
+            + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
+            + list(MSDA_TRAIN_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

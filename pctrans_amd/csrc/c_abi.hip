@@ -364,6 +364,36 @@ int pct_ms_deform_attn_backward_f64(const double *value, const int64_t *spatial_
                                grad_value, grad_sampling_loc, grad_attn_weight, stream);
 }
 
+int pct_ms_deform_attn_fused_backward_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
+                                          const float *ref_points, long long ref_batch_stride, const float *offsets,
+                                          const float *attn_logits, const float *grad_output, int batch, int spatial_size,
+                                          int num_heads, int channels, int num_levels, int num_query, int num_point,
+                                          int im2col_step, void *workspace, float *grad_value, float *grad_offsets,
+                                          float *grad_logits, void *stream)
+{
+  const int rc = check_common(value, spatial_shapes, level_start, offsets, attn_logits, batch, spatial_size, num_heads, channels,
+                              num_levels, num_query, num_point, im2col_step, sizeof(float), sizeof(float));
+  if (rc != PCT_OK) return rc;
+  if (batch == 0 || num_query == 0) return PCT_OK;
+  if (!ref_points || ref_batch_stride < 0 || !grad_output || !workspace || !grad_value || !grad_offsets || !grad_logits)
+    return PCT_ERR_BAD_ARG;
+  const long long LP = (long long)num_levels * num_point;
+  if (LP > 64 || LP % 4 || num_point % 2) return PCT_ERR_UNSUPPORTED;
+  if ((((uintptr_t)ref_points | (uintptr_t)grad_output | (uintptr_t)grad_value) & 3u) ||
+      (((uintptr_t)offsets | (uintptr_t)attn_logits | (uintptr_t)workspace | (uintptr_t)grad_offsets | (uintptr_t)grad_logits) & 15u))
+    return PCT_ERR_ALIGNMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long records = (long long)batch * num_query * num_heads;
+  float *loc = static_cast<float *>(workspace), *w = loc + records * LP * 2;     // LP % 4 == 0: w is 16-byte aligned too
+  int st = pct::launch_msda_fused_expand(attn_logits, offsets, ref_points, ref_batch_stride, spatial_shapes, records, num_heads,
+                                         num_query, num_levels, num_point, loc, w, s);
+  if (st != 0) return abi_status(st);
+  st = pct::launch_msda_backward<float>({value, spatial_shapes, level_start, loc, w, grad_output, batch, spatial_size, num_heads,
+                                         channels, num_levels, num_query, num_point, grad_value, grad_offsets, grad_logits, s});
+  if (st != 0) return st;
+  return abi_status(pct::launch_msda_fused_fold(w, spatial_shapes, records, num_levels, num_point, grad_offsets, grad_logits, s));
+}
+
 int pct_dynamic_mask_head_forward(const float *mask_feat, const float *ref_points, const float *params, int batch,
                                   int channels, int num_query, int height, int width, int stride, int rel_coord,
                                   int target_h, int target_w, int out_dtype, void *up_logits,

@@ -104,6 +104,16 @@ hipError_t zero_fill(void *ptr, size_t bytes, hipStream_t stream);   // msda_bac
 void set_msda_bwd_kernel_choice(int c);  // a MsdaBwdKernel; anything else: follow PCT_MSDA_BWD_KERNEL
 int msda_bwd_last_kernel();
 
+// ---- backward of the fused front-end (msda_fused_backward.hip; include/pctrans_hip_msda_train.h): the two kernels around
+// launch_msda_backward<float>.  R = N * Lq * M records.  expand: offsets, logits, reference points -> locations [R][L * P][2]
+// and softmax weights [R][L * P]; fold, in place on the routed backward's grad_loc / grad_attn: -> grad_offsets, grad_logits.
+// Every tensor but ref 16-byte aligned.  PCT_NOT_COVERED: L * P above 64 or no multiple of 4, an odd P, 2^37 records or more ----
+int launch_msda_fused_expand(const float *logits, const float *offsets, const float *ref, long long ref_batch_stride,
+                             const int64_t *shapes, long long R, int M, int Lq, int L, int P, float *loc, float *w,
+                             hipStream_t stream);
+int launch_msda_fused_fold(const float *w, const int64_t *shapes, long long R, int L, int P, float *grad_offsets,
+                           float *grad_logits, hipStream_t stream);
+
 // ---- once per device, outside any stream capture (pct_prepare_device) ---------------------------------------------------
 unsigned *win_queue_slot(hipStream_t stream);      // msda_win_common.hpp: a launch's set of per-XCD work-item counters
 int prepare_win_queue_device();

@@ -19,6 +19,7 @@ from torch.nn.init import constant_, xavier_uniform_
 
 from .... import MultiScaleDeformableAttention as MSDA
 from .... import fused_ops
+from .... import msda_train
 from ..functions import MSDeformAttnFunction, ms_deform_attn_core_pytorch
 
 _ALLOW_CPU_REFERENCE = False
@@ -48,6 +49,10 @@ class MSDeformAttn(nn.Module):
                           "8 half channels) maps best onto the 16-byte lane loads of the gfx950 kernel.")
 
         self.im2col_step = 128
+        # "hip": when a gradient is required, the fused front-end with its device backward (pctrans_amd/msda_train.py) instead
+        # of the torch chain of softmax, location arithmetic and MSDeformAttnFunction; "torch": that chain.  A plain attribute
+        # (process default: PCT_MSDA_TRAIN), not part of the state dict
+        self.train_front = msda_train.default()
 
         self.d_model = d_model
         self.n_levels = n_levels
@@ -85,6 +90,16 @@ class MSDeformAttn(nn.Module):
                 and self.d_model // self.n_heads == 16 and self.n_points in (4, 8) and self.n_heads <= 16
                 and value.shape[1] * value.shape[2] * value.shape[3] * 4 < 2 ** 31 - 1)   # per image: batches beyond 2 GiB are chunked in the library
 
+    def _train_front_applies(self, value, reference_points, offsets, logits):
+        """train_front == "hip" takes the call: a gradient is wanted and flows into value, offsets or logits, the reference
+        points are 2-d, and the operands are what the Function covers (fp32 on the device outside autocast, reference points
+        that need no gradient, the fused forward's geometry).  Everything else keeps the torch chain."""
+        if self.train_front != "hip" or not torch.is_grad_enabled() or reference_points.shape[-1] != 2:
+            return False
+        if not (value.requires_grad or offsets.requires_grad or logits.requires_grad):
+            return False
+        return msda_train.covered(value, reference_points, offsets, logits)
+
     def forward_add_norm(self, query, reference_points, input_flatten, input_spatial_shapes,
                          input_level_start_index, input_padding_mask, residual, norm, query_pos=None):
         """norm(residual + self(query + query_pos, ...)) -- the encoder layer's `src2 = self_attn(with_pos_embed(src,
@@ -104,6 +119,8 @@ class MSDeformAttn(nn.Module):
         """query (N, Lq, C); reference_points (N, Lq, n_levels, 2|4) in [0,1]; input_flatten (N, sum H_l*W_l, C);
         input_spatial_shapes (n_levels, 2) as (H_l, W_l); input_level_start_index (n_levels,);
         input_padding_mask (N, sum H_l*W_l) True = padding.  Returns (N, Lq, C)."""
+        if self.train_front not in ("hip", "torch"):
+            raise ValueError("MSDeformAttn.train_front must be 'hip' or 'torch', got %r" % (self.train_front,))
         N, Len_q, _ = query.shape
         N, Len_in, _ = input_flatten.shape
         # the reference's check (ops/modules/ms_deform_attn.py:95) compares on the device and therefore blocks the host on
@@ -149,6 +166,16 @@ class MSDeformAttn(nn.Module):
             N, Len_q, self.n_heads, self.n_levels, self.n_points, 2)
         attention_weights = self.attention_weights(query).view(
             N, Len_q, self.n_heads, self.n_levels * self.n_points)
+        if self._train_front_applies(value, reference_points, sampling_offsets, attention_weights):
+            # the eval path's one launch as an autograd Function: no sampling_locations tensor, no softmax output, and a
+            # backward that hands back the gradients of value and of the two Linear outputs directly
+            output = msda_train.ms_deform_attn_fused_train(
+                value.contiguous(), input_spatial_shapes, input_level_start_index, reference_points,
+                sampling_offsets.contiguous(), attention_weights.contiguous(), self.im2col_step)
+            output = self.output_proj(output)
+            if _norm is not None:
+                output = _norm(_residual + output)
+            return output
         attention_weights = F.softmax(attention_weights, -1).view(
             N, Len_q, self.n_heads, self.n_levels, self.n_points)
         if reference_points.shape[-1] == 2:

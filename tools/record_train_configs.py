@@ -57,6 +57,11 @@ def build(c):
     for s in train_switches.SWITCHES:             # the switches' table of the tests: one place says how each is set
         if s["config_key"] is not None and c.get(s["config_key"]):
             train_switches.set_switch(model, s["name"], True)
+    if c.get("hip_msda_train"):                   # hand-written like the graph flags: not (yet) in the tests' table
+        from pctrans_amd.pixel_decoder.ops.modules import MSDeformAttn
+        for m in model.modules():
+            if isinstance(m, MSDeformAttn):
+                m.train_front = "hip"
     if c.get("graph_decoder"):
         from pctrans_amd.graph import graph_training_decoder
         graph_training_decoder(model, vol)
@@ -80,6 +85,8 @@ def selected_configs(argv):
         configs.update({k + " + graphed backbone / pixel decoder": dict(v, graph_front=True) for k, v in CONFIGS.items()})
     if "--graph-decoder" in argv:
         configs.update({k + " + graphed decoder core": dict(v, graph_decoder=True) for k, v in CONFIGS.items()})
+    if "--hip-msda-train" in argv:          # every selected config again with the encoder's fused MSDeformAttn front-end and its backward
+        configs.update({k + " + HIP MSDeformAttn front": dict(v, hip_msda_train=True) for k, v in list(configs.items())})
     if "--hip-mask-head" in argv:           # every selected config again with the mask head's HIP training path
         configs.update({k + " + HIP mask head": dict(v, hip_mask_head=True) for k, v in list(configs.items())})
     if "--hip-point-loss" in argv:          # and again with the point-sampled losses and the matcher's gather on the device
@@ -149,7 +156,7 @@ def main():
     the same fragility).  `--rounds R` repeats the whole list R times, so that flag-off and flag-on steps alternate on one
     machine; a child that fails ends the recording there with its exit status."""
     import subprocess
-    known = ["--graph-front", "--graph-decoder"] + [s["flag"] for s in train_switches.SWITCHES if s["flag"] is not None]
+    known = ["--graph-front", "--graph-decoder", "--hip-msda-train"] + [s["flag"] for s in train_switches.SWITCHES if s["flag"] is not None]
     flags = [a for a in sys.argv[1:] if a in known]
     configs = selected_configs(flags)
     if "--only" in sys.argv:
