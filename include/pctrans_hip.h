@@ -199,6 +199,9 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_attn_train.h"
 /* the mask side of the query-contrast loss in training, behind MultiScaleMaskedTransformerDecoder.reid_dice = "hip" */
 #include "pctrans_hip_reid.h"
+/* its query side and the per-item reduction of both, behind MultiScaleMaskedTransformerDecoder.reid_query = "hip" and
+ * SetCriterion.contrast_loss = "hip" */
+#include "pctrans_hip_reid_query.h"
 /* instance targets from label maps (the trainer's target preparation), behind pctrans_amd.targets.prepare_instance_targets */
 #include "pctrans_hip_targets.h"
 /* the backward of the fused MSDeformAttn front-end, behind MSDeformAttn.train_front = "hip" */

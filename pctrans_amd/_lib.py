@@ -130,6 +130,17 @@ REID_SYMBOLS = {
     "pct_reid_dice_rows_backward_f32": ([_vp] * 6 + [_i] * 5 + [_vp] * 3, _i, "tests/test_reid_dice_gpu.py"),
 }
 
+# Entry points of the query side of the query-contrast loss and of the per-item reduction of both sides
+# (include/pctrans_hip_reid_query.h; pctrans_amd/reid_query.py, reached with MultiScaleMaskedTransformerDecoder.reid_query = "hip"
+# and SetCriterion.contrast_loss = "hip").  A table of its own, as the mask side's: name -> (argtypes, restype, the test module
+# that checks the entry against float64)
+REID_QUERY_SYMBOLS = {
+    "pct_reid_nearest_positive_f32": ([_vp, _vp] + [_i] * 4 + [_vp, _vp], _i, "tests/test_reid_query_gpu.py"),
+    "pct_reid_query_rows_forward_f32": ([_vp] * 3 + [_i] * 4 + [_vp] * 4, _i, "tests/test_reid_query_gpu.py"),
+    "pct_reid_query_rows_backward_f32": ([_vp] * 7 + [_i] * 4 + [_vp] * 3, _i, "tests/test_reid_query_gpu.py"),
+    "pct_contrast_loss_rows_f32": ([_vp] * 4 + [_i] * 3 + [ctypes.c_float] + [_vp] * 3, _i, "tests/test_reid_query_gpu.py"),
+}
+
 # Entry points of the instance targets from label maps (include/pctrans_hip_targets.h; pctrans_amd/targets.py:
 # prepare_instance_targets, MaskFormer.prepare_instance_targets).  A table of its own, as the re-id loss's: name -> (argtypes,
 # restype, the test module that checks the entry -- against the torch formulation: the outputs are exact)
@@ -166,7 +177,7 @@ def lib():
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
-            + list(MSDA_TRAIN_SYMBOLS.items())]:
+            + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

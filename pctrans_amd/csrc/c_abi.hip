@@ -673,6 +673,56 @@ int pct_reid_dice_rows_backward_f32(const float *logits, const int32_t *image_st
                                         workspace, grad_logits, static_cast<hipStream_t>(stream));
 }
 
+int pct_reid_nearest_positive_f32(const float *query, const int32_t *pos, int num_query, int batch, int channels, int max_pos,
+                                  int32_t *nearest, void *stream)
+{
+  if (num_query <= 0 || batch <= 0 || channels <= 0 || max_pos <= 0) return PCT_ERR_BAD_ARG;
+  if (!query || !pos || !nearest) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)query & 15u) || (((uintptr_t)pos | (uintptr_t)nearest) & 3u)) return PCT_ERR_ALIGNMENT;
+  return pct::launch_reid_nearest_positive(query, pos, num_query, batch, channels, max_pos, nearest,
+                                           static_cast<hipStream_t>(stream));
+}
+
+int pct_reid_query_rows_forward_f32(const float *query, const int32_t *image_start, const int32_t *key, int num_query, int batch,
+                                    int channels, int num_rows, float *norm, float *dots, float *cosines, void *stream)
+{
+  if (num_query <= 0 || batch <= 0 || channels <= 0 || num_rows < 0) return PCT_ERR_BAD_ARG;
+  if (num_rows == 0) return PCT_OK;
+  if (!query || !image_start || !key || !norm || !dots || !cosines) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)query & 15u) ||
+      (((uintptr_t)image_start | (uintptr_t)key | (uintptr_t)norm | (uintptr_t)dots | (uintptr_t)cosines) & 3u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_reid_query_rows_forward(query, image_start, key, num_query, batch, channels, num_rows, norm, dots, cosines,
+                                             static_cast<hipStream_t>(stream));
+}
+
+int pct_reid_query_rows_backward_f32(const float *query, const int32_t *image_start, const int32_t *key, const float *norm,
+                                     const float *cosines, const float *grad_dots, const float *grad_cosines, int num_query,
+                                     int batch, int channels, int num_rows, void *workspace, float *grad_query, void *stream)
+{
+  if (num_query <= 0 || batch <= 0 || channels <= 0 || num_rows < 0) return PCT_ERR_BAD_ARG;
+  if (!query || !image_start || !workspace || !grad_query) return PCT_ERR_BAD_ARG;
+  if (num_rows > 0 && (!key || !norm || !cosines || !grad_dots || !grad_cosines)) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)query | (uintptr_t)workspace | (uintptr_t)grad_query) & 15u) ||
+      (((uintptr_t)image_start | (uintptr_t)key | (uintptr_t)norm | (uintptr_t)cosines | (uintptr_t)grad_dots |
+        (uintptr_t)grad_cosines) & 3u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_reid_query_rows_backward(query, image_start, key, norm, cosines, grad_dots, grad_cosines, num_query, batch,
+                                              channels, num_rows, workspace, grad_query, static_cast<hipStream_t>(stream));
+}
+
+int pct_contrast_loss_rows_f32(const float *rows, const int32_t *image_of, const int32_t *key, const int32_t *owner, int num_rows,
+                               int num_query, int batch, float inv_temperature, float *loss, float *coef, void *stream)
+{
+  if (num_rows < 0 || num_query <= 0 || batch <= 0 || !(inv_temperature > 0.f)) return PCT_ERR_BAD_ARG;
+  if (num_rows == 0) return PCT_OK;
+  if (!rows || !image_of || !key || !owner || !loss || !coef) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)rows | (uintptr_t)image_of | (uintptr_t)key | (uintptr_t)owner | (uintptr_t)loss | (uintptr_t)coef) & 3u)
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_contrast_loss_rows(rows, image_of, key, owner, num_rows, num_query, batch, inv_temperature, loss, coef,
+                                        static_cast<hipStream_t>(stream));
+}
+
 int pct_instance_targets_census(const void *labels, int dtype, int batch, int height, int width, int ignore_label, void *workspace,
                                 int32_t *ids, int32_t *pixels, float *centres, int32_t *num, int32_t *status, void *stream)
 {

@@ -241,6 +241,18 @@ int launch_reid_dice_backward(const float *logits, const int *image_start, const
                               const float *grad_dice, int N, int Q, int h, int w, int I, void *workspace, float *grad_logits,
                               hipStream_t stream);
 
+// ---- query side of the query-contrast loss and the per-item reduction of both sides (reid_query.hip;
+// include/pctrans_hip_reid_query.h).  PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover ---------------
+int launch_reid_nearest_positive(const float *query, const int *pos, int Q, int N, int C, int max_pos, int *nearest,
+                                 hipStream_t stream);
+int launch_reid_query_rows_forward(const float *query, const int *image_start, const int *key, int Q, int N, int C, int I,
+                                   float *norm, float *dots, float *cosines, hipStream_t stream);
+int launch_reid_query_rows_backward(const float *query, const int *image_start, const int *key, const float *norm,
+                                    const float *cosines, const float *grad_dots, const float *grad_cosines, int Q, int N, int C,
+                                    int I, void *workspace, float *grad_query, hipStream_t stream);
+int launch_contrast_loss_rows(const float *rows, const int *image_of, const int *key, const int *owner, int I, int Q, int N,
+                              float inv_temperature, float *loss, float *coef, hipStream_t stream);
+
 // ---- instance targets from label maps (instance_targets.hip; include/pctrans_hip_targets.h).  dtype: 0 uint8, 1 int16, 2 int32,
 // 3 int64, 4 float32.  PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover -------------------------
 int instance_targets_geometry_status(int dtype, int N, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED

@@ -14,6 +14,7 @@ from torch import nn
 
 from .. import embedding_loss as _embedding_loss
 from .. import point_loss as _point_loss
+from .. import reid_query as _reid_query
 from .. import targets as _targets
 from .point_features import get_uncertain_point_coords_with_randomness, point_sample
 
@@ -158,6 +159,11 @@ class SetCriterion(nn.Module):
         # (point_loss.*_many), with the random numbers the per-head calls would draw; anything else runs head by head.  A plain
         # attribute; process default from PCT_LOSS_HEADS
         self.loss_heads = _point_loss.heads_default()
+        # "torch": loss_reid_query / loss_reid_mask reduce their items with _contrast_softplus.  "hip": where the items carry
+        # their rows [I, Q] from the device paths (query_contrast: reid_query / reid_dice = "hip"), one launch per loss gives every
+        # item's loss and its coefficients (pctrans_amd/reid_query.py: contrast_loss_rows); the code below otherwise.  A plain
+        # attribute; process default from PCT_CONTRAST_LOSS
+        self.contrast_loss = _reid_query.contrast_default()
         self._target_planes = None
         self._emb_plane_index = None
 
@@ -322,13 +328,27 @@ class SetCriterion(nn.Module):
             gt.append(torch.argmax((down[:, 0] > 0).to(torch.int16), dim=0))
         return {"loss_emb": discriminative_loss(emb, torch.stack(gt), alpha=alpha, beta=beta, gama=gama)}
 
+    def _contrast_rows_hip(self, bt, temperature):
+        """The items' losses [I] from the device reduction, or None: the switch is off, the items carry no rows (they came from
+        the torch chain) or the kernel does not cover them."""
+        if self.contrast_loss not in ("torch", "hip"):
+            raise ValueError("SetCriterion.contrast_loss must be 'torch' or 'hip', got %r" % (self.contrast_loss,))
+        if self.contrast_loss != "hip" or not all(k in bt for k in ("rows", "image", "key", "owner")):
+            return None
+        if not _reid_query.contrast_supported(bt["rows"], bt["image"], bt["key"], bt["owner"]):
+            return None
+        return _reid_query.contrast_loss_rows(bt["rows"], bt["image"], bt["key"], bt["owner"], temperature)
+
     def loss_reid_query(self, outputs, targets, indices, num_masks):
         items = outputs["pred_qd_query"]
         if len(items) == 0:
             return {"loss_reid_query": 0, "loss_reid_query_aux": 0}
         bt = getattr(items, "batched", None)
         if bt is not None:                       # all items at once (query_contrast.ContrastItems)
-            contras = _contrast_softplus(bt["contrast"] / 2.0, bt["n_pos"]).sum()
+            contras = self._contrast_rows_hip(bt, 2.0)
+            if contras is None:
+                contras = _contrast_softplus(bt["contrast"] / 2.0, bt["n_pos"])
+            contras = contras.sum()
             sq = torch.abs(bt["aux_consin"] - bt["aux_label"]) ** 2
             aux = ((sq[bt["aux_rows"]] * bt["aux_valid"]).sum(1) / bt["aux_count"]).sum()
             return {"loss_reid_query": contras / len(items), "loss_reid_query_aux": aux / len(items)}
@@ -344,7 +364,10 @@ class SetCriterion(nn.Module):
             return {"loss_reid_mask": 0}
         bt = getattr(items, "batched", None)
         if bt is not None:
-            return {"loss_reid_mask": _contrast_softplus(bt["contrast"] / 0.5, bt["n_pos"]).sum() / len(items)}
+            contras = self._contrast_rows_hip(bt, 0.5)
+            if contras is None:
+                contras = _contrast_softplus(bt["contrast"] / 0.5, bt["n_pos"])
+            return {"loss_reid_mask": contras.sum() / len(items)}
         contras = 0
         for it in items:
             contras = contras + _contrast_logsumexp(it["contrast"].permute(1, 0) / 0.5, it["label"].unsqueeze(0))

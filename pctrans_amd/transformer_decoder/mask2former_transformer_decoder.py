@@ -35,6 +35,7 @@ from .. import attention_train
 from .. import dynamic_mask_head as dmh
 from .. import fused_ops
 from .. import reid_dice
+from .. import reid_query
 from ..layers import CachedLinear, Conv2d, c2_xavier_fill, get_norm
 from .attention import MultiheadAttention
 from .position_encoding import PositionEmbeddingSine
@@ -384,6 +385,10 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         # mask side of the query-contrast loss: "torch" (dice_for of all queries, then the items' rows) or "hip" (the items' rows
         # alone with a HIP backward, pctrans_amd/reid_dice.py).  A plain attribute; process default from PCT_REID_DICE
         self.reid_dice = reid_dice.default()
+        # query side of the same loss: "torch" (the [N, Q, Q] cosine table, gathers, einsum and F.normalize of
+        # query_contrast.py) or "hip" (the nearest-positive table and the items' Gram rows with a HIP backward,
+        # pctrans_amd/reid_query.py).  A plain attribute; process default from PCT_REID_QUERY
+        self.reid_query = reid_query.default()
         self.mask_out_stride = 4
         self.rel_coord = rel_coord
         ch = self.dynamic_mask_channels
@@ -454,8 +459,12 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             if self.reid_dice not in ("torch", "hip"):
                 raise ValueError("MultiScaleMaskedTransformerDecoder.reid_dice must be 'torch' or 'hip', got %r"
                                  % (self.reid_dice,))
+            if self.reid_query not in ("torch", "hip"):
+                raise ValueError("MultiScaleMaskedTransformerDecoder.reid_query must be 'torch' or 'hip', got %r"
+                                 % (self.reid_query,))
             contrast_items_query, contrast_items_mask = query_contrast_items(output, predictions_mask[-1], indices_list[-1],
-                                                                             mask_dice=self.reid_dice)
+                                                                             mask_dice=self.reid_dice,
+                                                                             reid_query=self.reid_query)
 
         out = {
             "pred_masks": predictions_mask[-1],
