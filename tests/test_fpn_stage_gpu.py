@@ -186,6 +186,43 @@ def test_graph_replay_equals_the_eager_call_bit_for_bit():
     assert torch.equal(static, eager)
 
 
+@pytest.mark.parametrize("layout", ["nchw", "tokens"])
+@pytest.mark.parametrize("norm", ["BN", "FrozenBN"])
+def test_eps_of_the_norm_decides_where_the_running_variance_is_tiny(norm, layout):
+    """running_var per channel from {0, 1e-8, 1e-4, 1} and eps = 1e-3 on both norms: on three channels in four eps decides the
+    scale, and a kernel that used the default 1e-5 instead would be off by up to sqrt(1e-3 / 1e-5) = 10.  Same rule as above."""
+    from pctrans_amd import fused_ops
+    N, Cin, H, W = 2, 64, 5, 33
+    g = torch.Generator().manual_seed(91)
+    x = torch.randn(N, Cin, 2 * H, 2 * W, generator=g).cuda()
+    tokens = torch.randn(N, 3 + H * W + 2, 128, generator=g).cuda()
+    enc = tokens[:, 3:3 + H * W].transpose(1, 2).reshape(N, 128, H, W)
+    if layout == "nchw":
+        enc = enc.contiguous()
+    lat, outc = _convs(norm, Cin, 13)
+    values = torch.tensor([0.0, 1e-8, 1e-4, 1.0])
+    with torch.no_grad():
+        for c in (lat, outc):
+            c.norm.running_var.copy_(values[torch.randint(0, 4, (128,), generator=g)])
+            c.norm.eps = 1e-3
+            assert len(torch.unique(c.norm.running_var)) == 4
+    lat, outc = lat.cuda(), outc.cuda()
+    ref = _stage64(x, enc, lat, outc)
+    with torch.no_grad():
+        want = _stage_torch(x, enc, lat, outc)
+        assert fused_ops.fpn_stage_supported(x, enc, lat, outc)
+        got = fused_ops.fpn_stage(x, enc, lat, outc)
+    torch.cuda.synchronize()
+    e_torch, e_hip = float((want.double().cpu() - ref).abs().max()), float((got.double().cpu() - ref).abs().max())
+    fig = {"e_torch": e_torch, "e_hip": e_hip, "max_ref": float(ref.abs().max()),
+           "bound": 2 * e_torch + 2.0 ** -22 * float(ref.abs().max())}
+    _FIGURES["smallvar_%dx%dx%dx%d_%s_%s" % (N, Cin, H, W, norm, layout)] = fig
+    print(norm, layout, fig)
+    assert e_hip <= fig["bound"], fig
+    b = outc.norm.bias[ZERO_GAMMA].clamp(min=0)                      # gamma = 0: relu(beta) in every pixel of that channel
+    assert bool((got[:, ZERO_GAMMA] == b).all())
+
+
 # ------------------------------------------------------------------------------------------------------- the module ----
 _CH = {"res2": 16, "res3": 24, "res4": 32, "res5": 40}
 _STRIDE = {"res2": 4, "res3": 8, "res4": 16, "res5": 32}

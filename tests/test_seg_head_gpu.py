@@ -89,9 +89,23 @@ def _err(got, ref):
     return float((got.double().cpu() - ref).abs().max())
 
 
-def _check(N, H, W, gamma_zero, channels_last=False):
+def _small_variances(seg, eps=1e-3):
+    """running_var per channel from {0, 1e-8, 1e-4, 1} and the modules' eps at 1e-3 on both BatchNorms: on three channels in
+    four eps decides the scale, and a kernel that used the default 1e-5 instead would be off by up to sqrt(1e-3 / 1e-5) = 10."""
+    g = torch.Generator().manual_seed(77)
+    values = torch.tensor([0.0, 1e-8, 1e-4, 1.0])
+    with torch.no_grad():
+        for b in seg:
+            b[1].running_var.copy_(values[torch.randint(0, 4, (b[1].num_features,), generator=g)].to(b[1].running_var.device))
+            b[1].eps = eps
+            assert len(torch.unique(b[1].running_var)) == 4
+
+
+def _check(N, H, W, gamma_zero, channels_last=False, small_variances=False):
     from pctrans_amd import fused_ops
     seg, logits = _head(100 + H * W, gamma_zero=gamma_zero)
+    if small_variances:
+        _small_variances(seg)
     g = torch.Generator().manual_seed(N * 1000 + H * 31 + W)
     x = torch.randn(N, 128, H, W, generator=g).to(torch.bfloat16).cuda()
     if channels_last:
@@ -108,7 +122,8 @@ def _check(N, H, W, gamma_zero, channels_last=False):
     assert got1.dtype == torch.bfloat16 and got1.shape == want1.shape and got1.stride() == x.stride()
     fig = {"block1": {"e_torch": _err(want1, ref1), "e_hip": _err(got1, ref1), "ulp": _ulp(ref1)},
            "head": {"e_torch": _err(want, ref), "e_hip": _err(got, ref), "ulp": _ulp(ref)}}
-    _FIGURES["%dx%dx%d%s%s" % (N, H, W, "_nhwc" if channels_last else "", "_gamma0" if gamma_zero else "")] = fig
+    tags = ("_nhwc" if channels_last else "") + ("_gamma0" if gamma_zero else "") + ("_smallvar" if small_variances else "")
+    _FIGURES["%dx%dx%d%s" % (N, H, W, tags)] = fig
     print(N, H, W, channels_last, gamma_zero, fig)
     assert fig["block1"]["e_hip"] <= fig["block1"]["e_torch"] + fig["block1"]["ulp"], fig
     assert fig["head"]["e_hip"] <= 2 * fig["head"]["e_torch"] + fig["head"]["ulp"], fig
@@ -192,3 +207,9 @@ def test_head_and_first_block_are_as_close_to_float64_as_the_torch_chain(N, H, W
 @pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
 def test_a_channel_with_gamma_zero(channels_last):
     _check(1, 17, 23, True, channels_last)
+
+
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+def test_eps_of_the_module_decides_where_the_running_variance_is_tiny(channels_last):
+    """BatchNorm with running_var in {0, 1e-8, 1e-4, 1} and eps = 1e-3 on both blocks, under the same rule as every other case."""
+    _check(2, 17, 23, False, channels_last, small_variances=True)
