@@ -204,6 +204,8 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_reid_query.h"
 /* instance targets from label maps (the trainer's target preparation), behind pctrans_amd.targets.prepare_instance_targets */
 #include "pctrans_hip_targets.h"
+/* validation metrics from label maps (SBD, AJI, F1, PQ), behind pctrans_amd.metrics and MaskFormer.validation_metrics */
+#include "pctrans_hip_metrics.h"
 /* the backward of the fused MSDeformAttn front-end, behind MSDeformAttn.train_front = "hip" */
 #include "pctrans_hip_msda_train.h"
 

@@ -158,6 +158,14 @@ MSDA_TRAIN_SYMBOLS = {
                                               "tests/test_msda_fused_train_gpu.py"),
 }
 
+# Entry points of the validation metrics from label maps (include/pctrans_hip_metrics.h; pctrans_amd/metrics.py,
+# MaskFormer.validation_metrics).  A table of its own, as the targets': name -> (argtypes, restype, the test module that checks
+# the entry -- against the literal per-mask definitions: the integer outputs are exact)
+METRICS_SYMBOLS = {
+    "pct_label_overlap": ([_vp, _i, _vp, _i, _vp] + [_i] * 3 + [_vp] * 8, _i, "tests/test_metrics_gpu.py"),
+    "pct_label_metrics": ([_vp] * 5 + [_i] + [_vp] * 3, _i, "tests/test_metrics_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -177,7 +185,7 @@ def lib():
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
-            + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items())]:
+            + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from .. import metrics as _metrics
 from .. import postprocess as post
 from .. import targets as _targets
 from ..loss import Point_HungarianMatcher, SetCriterion
@@ -161,6 +162,21 @@ class MaskFormer(nn.Module):
         return _targets.prepare_instance_targets(
             label_maps, points_num=predictor.points_num, semantic_loss_on=predictor.sem_loss_on,
             instance_discriminative=instance_discriminative, ignore_label=ignore_label, device=next(self.parameters()).device)
+
+    @torch.no_grad()
+    def validation_metrics(self, volume, gt_labels, fg=None):
+        """The reference trainer's validation step for one batch (connectomics/engine/trainer.py:398-450 for CVPPP, :497-573 for
+        BBBC) without its host copies: the eval forward, then pctrans_amd.metrics.instance_metrics for `self.dataset_name` on
+        the label maps `forward` returns -- with `postprocess == "hip"` those of post.instance_labels, still on the device --
+        against `gt_labels` [N, H, W].  `fg`: the trainer's foreground map (the prediction is scored as `labels * fg`).
+        -> Metrics (a dict of [N] tensors with `.status`), carrying the scored label maps as `.labels`.  Call in eval mode."""
+        if self.training:
+            raise RuntimeError("validation_metrics runs the eval forward: call model.eval() first")
+        labels, _ = self.forward(volume)
+        gt_labels = gt_labels.to(labels.device)
+        out = _metrics.instance_metrics(labels, gt_labels, self.dataset_name, None if fg is None else fg.to(labels.device))
+        out.labels = labels
+        return out
 
     def forward(self, volume, targets=None, train=False):
         features = self.backbone(volume)

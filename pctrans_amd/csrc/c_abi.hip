@@ -752,6 +752,34 @@ int pct_instance_targets_planes(const void *labels, int dtype, int batch, int he
                                              masks, planes, fg, static_cast<hipStream_t>(stream));
 }
 
+int pct_label_overlap(const void *pred, int pred_dtype, const void *gt, int gt_dtype, const uint8_t *fg, int batch, int height,
+                      int width, void *workspace, int32_t *values, int32_t *areas, int32_t *num, int32_t *range, int32_t *table,
+                      int32_t *status, void *stream)
+{
+  if (height <= 0 || width <= 0) return PCT_ERR_BAD_ARG;
+  const int rc = pct::label_metrics_geometry_status(pred_dtype, gt_dtype, batch, height, width);
+  if (rc != PCT_OK) return rc;
+  if (!pred || !gt || !workspace || !values || !areas || !num || !range || !table || !status) return PCT_ERR_BAD_ARG;
+  static const uintptr_t elem[5] = {1, 2, 4, 8, 4};
+  if (((uintptr_t)pred & (elem[pred_dtype] - 1)) || ((uintptr_t)gt & (elem[gt_dtype] - 1)) ||
+      (((uintptr_t)values | (uintptr_t)areas | (uintptr_t)num | (uintptr_t)range | (uintptr_t)status) & 3u) ||
+      (((uintptr_t)workspace | (uintptr_t)table) & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_label_overlap(pred, pred_dtype, gt, gt_dtype, fg, batch, height, width, workspace, values, areas, num, range,
+                                   table, status, static_cast<hipStream_t>(stream));
+}
+
+int pct_label_metrics(const int32_t *values, const int32_t *areas, const int32_t *num, const int32_t *range, const int32_t *table,
+                      int batch, double *metrics, int32_t *counts, void *stream)
+{
+  if (batch <= 0 || batch > 65535) return PCT_ERR_UNSUPPORTED;
+  if (!values || !areas || !num || !range || !table || !metrics || !counts) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)values | (uintptr_t)areas | (uintptr_t)num | (uintptr_t)range | (uintptr_t)table | (uintptr_t)counts) & 3u) ||
+      ((uintptr_t)metrics & 7u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_label_metrics(values, areas, num, range, table, batch, metrics, counts, static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

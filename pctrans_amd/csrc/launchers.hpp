@@ -262,6 +262,15 @@ int launch_instance_targets_planes(const void *labels, int dtype, int N, int H, 
                                    long long total_planes, int max_count, int *starts, uint8_t *masks, float *planes, uint8_t *fg,
                                    hipStream_t stream);
 
+// ---- validation metrics from label maps (label_metrics.hip; include/pctrans_hip_metrics.h).  dtype codes as the instance targets'.
+// PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover ----------------------------------------------------
+int label_metrics_geometry_status(int pred_dtype, int gt_dtype, int N, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
+int launch_label_overlap(const void *pred, int pred_dtype, const void *gt, int gt_dtype, const uint8_t *fg, int N, int H, int W,
+                         void *workspace, int *values, int *areas, int *num, int *range, int *table, int *status,
+                         hipStream_t stream);
+int launch_label_metrics(const int *values, const int *areas, const int *num, const int *range, const int *table, int N,
+                         double *metrics, int *counts, hipStream_t stream);
+
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
 int launch_instance_masks(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, unsigned *bits,
