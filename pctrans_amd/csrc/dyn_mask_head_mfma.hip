@@ -2,19 +2,22 @@
 //
 //   A  dmh_logits_mfma_kernel : the 3-layer per-query MLP  (mask2former_transformer_decoder.py:699-719)
 //        x0 = relu(W0[q] . [rel_x, rel_y, feat] + b0[q]),  x1 = relu(W1[q] . x0 + b1[q]),  logit = W2[q] . x1 + b2[q]
-//      as chained v_mfma_f32_16x16x16_bf16.  One MFMA tile = 2 queries x 8 hidden rows (M = 16) by 16 pixels (N = 16);
-//      layer 0 contracts over the 16 feature channels (K = 16 exactly), layer 1 over the 16 hidden rows of the query
-//      pair with a block-diagonal W1.  The accumulator layout of layer 0 (lane (g, px) holds rows 4g..4g+3) IS the
-//      B-operand layout of a K = 16 MFMA (lane (g, px) supplies k = 4g..4g+3), so x0 goes from accumulator registers to
-//      operand registers with a relu and a bf16 pack -- no LDS, no shuffles.  The two relative-coordinate inputs and
-//      the biases enter as the fp32 initial accumulator (more accurate than the reference's bf16 conv inputs), layer 2
-//      (8 MACs) is a 4-FMA partial dot per lane plus one cross-group add.  Feature fragments of a wave's 8 pixel tiles
+//      as chained bf16 MFMAs (csrc/dmh_common.hpp, DmhPair::tiles).  One MFMA tile = 2 queries x 8 hidden rows (M = 16) by
+//      16 pixels (N = 16); layer 0 contracts over the 16 feature channels and the twelve exact coordinate slots (one
+//      16x16x32), layer 1 over the 16 hidden rows of the query pair with a block-diagonal W1, layer 2 over the same rows
+//      with w2 in rows 0, 4, 8, 12.  The accumulator layout of a layer (lane (g, px) holds rows 4g..4g+3) IS the B-operand
+//      layout of a K = 16 MFMA (lane (g, px) supplies k = 4g..4g+3), so x0 and x1 go from accumulator registers to operand
+//      registers with a bf16 pack and a relu -- no LDS, no shuffles.  The relative-coordinate term and the biases are fp32
+//      (more accurate than the reference's bf16 conv inputs): the per-query constant b0 + wx rx + wy ry is the initial
+//      accumulator, the per-pixel part goes through the matrix core exactly.  Feature fragments of a wave's 8 pixel tiles
 //      stay in registers across all query pairs; per-pair weights are fetched once per pair.
 //   B  dmh_resize_kernel : bilinear x2 upsample (align_corners = False) of the bf16 logit planes + the boolean
 //      attention mask  sigmoid(resize to (th, tw)) < 0.5   (:689-695), a pure streaming pass through an LDS row band.
 //
-// Under autocast the reference's convolutions take bf16 inputs/weights with fp32 accumulation and emit bf16; here the
-// hidden activations are likewise rounded to bf16 between layers 0 and 1 and the logits are stored as bf16.
+// Rounding points (tests/test_dmh_exact_gpu.py holds this path and the one-launch kernel to them bit for bit): under
+// autocast the reference's convolutions take bf16 inputs/weights with fp32 accumulation and emit bf16; here the features,
+// W0's feature weights, x0, W1, x1, w2 and the logits are rounded to bf16 (the fp32-VALU kernel of dyn_mask_head.hip rounds
+// only the logits), the upsampled output is bf16, and the mask byte is bf16(sigmoid(bf16(v))) < 0.5, i.e. bf16(v) < -2^-8.
 #include "dmh_common.hpp"
 #include "launchers.hpp"
 
