@@ -205,6 +205,22 @@ def check(code, what):
         raise RuntimeError("%s failed: %s (code %d)" % (what, msg, code))
 
 
+def env_switch(name, default="torch"):
+    """Process default of an opt-in device path: the environment variable `name` = hip | torch, `default` where it is unset or
+    empty.  Every module's `default()` is this."""
+    v = os.environ.get(name) or default
+    if v not in ("hip", "torch"):
+        raise RuntimeError("%s must be 'hip' or 'torch', got %r" % (name, v))
+    return v
+
+
+def chunk_plan(pixels, per_pass, max_chunks):
+    """(passes of `per_pass` pixels per chunk, chunks of an image): csrc/launchers.hpp's chunk_plan, for the workspace sizes."""
+    subs = -(-pixels // per_pass)
+    passes = -(-subs // max_chunks)
+    return passes, -(-subs // passes)
+
+
 _PREPARED = set()
 
 

@@ -4,7 +4,6 @@
 concatenation, no [N, heads, Q, S] tensor in forward or backward; it keeps the five operands, `out` and `lse` for the backward
 and nothing else.  CrossAttentionLayer takes it when a gradient is required and its `attn_train` switch is "hip"
 (PCT_ATTN_TRAIN); otherwise it uses the torch chain of transformer_decoder/attention.py."""
-import os
 
 import torch
 
@@ -19,10 +18,7 @@ MAX_KEYS = 1024
 
 def default():
     """Process default of CrossAttentionLayer's `attn_train` switch: PCT_ATTN_TRAIN = hip | torch (default torch)."""
-    v = os.environ.get("PCT_ATTN_TRAIN") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_ATTN_TRAIN must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_ATTN_TRAIN")
 
 
 def _mask_ok(attn_mask, N, Q, S, device):

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "launchers.hpp"
+#include "wave_reduce.hpp"
 
 namespace pct {
 
@@ -60,9 +61,9 @@ struct EmbLossPlan {
 inline EmbLossPlan emb_loss_plan(const int B, const long long P, const int L, const int E)
 {
   EmbLossPlan m;
-  const long long subs = (P + EL_SUB - 1) / EL_SUB;
-  m.passes = (int)((subs + EL_MAX_CHUNKS - 1) / EL_MAX_CHUNKS);
-  m.chunks = (int)((subs + m.passes - 1) / m.passes);
+  const ChunkPlan cp = chunk_plan(P, EL_SUB, EL_MAX_CHUNKS);
+  m.passes = cp.passes;
+  m.chunks = cp.chunks;
   m.tiles = L / 32 + 1;
   m.lblocks = (L + 31) / 32;
   m.ctiles = E <= 32 ? 1 : E <= 64 ? 2 : 4;
@@ -176,8 +177,7 @@ __global__ __launch_bounds__(64) void sums_kernel(const float *__restrict__ emb,
     slot[plan.nch + 1] = qsum;
   }
   if (!PASS_B && tile == 0 && ct == 0) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
+    bad = wave_sum(bad);
     if (lane == 0) reinterpret_cast<int *>(ws + plan.bad)[(size_t)b * plan.chunks + chunk] = bad;
   }
 }
@@ -237,8 +237,7 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
 
   int present = 0;
   for (int g = 1 + tid; g <= L; g += EL_CBLOCK) present += tb[(size_t)g * EL_ROW + EL_N] > 0.f ? 1 : 0;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) present += __shfl_xor(present, m, 64);
+  present = wave_sum(present);
   if (lane == 0) s_count[wave] = present;
   __syncthreads();
   int num_id = 0;
@@ -309,12 +308,9 @@ __global__ __launch_bounds__(EL_CBLOCK) void centroid_kernel(float *__restrict__
       if (c < E) row[EL_T + c] = -c_i * row[EL_T + c] / n_i + (kd * acc[c] + kr * mu[c]) * inv;
   }
   // the workgroup's three sums: a butterfly inside each wave, the waves in ascending order
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    var_i += __shfl_xor(var_i, m, 64);
-    dist_i += __shfl_xor(dist_i, m, 64);
-    reg_i += __shfl_xor(reg_i, m, 64);
-  }
+  var_i = wave_sum(var_i);
+  dist_i = wave_sum(dist_i);
+  reg_i = wave_sum(reg_i);
   if (lane == 0) {
     s_part[wave][0] = var_i;
     s_part[wave][1] = dist_i;
@@ -365,8 +361,7 @@ __global__ __launch_bounds__(64) void finish_kernel(const float *__restrict__ ws
   const int *badp = reinterpret_cast<const int *>(ws + plan.bad);
   int bad = 0;
   for (long long k = lane; k < (long long)B * plan.chunks; k += 64) bad += badp[k];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
+  bad = wave_sum(bad);
   if (lane == 0) {
     const float fB = (float)B;
     *loss = alpha * tv / fB + beta * td / fB + gama * tr / fB;

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "launchers.hpp"
+#include "wave_reduce.hpp"
 
 namespace pct {
 
@@ -61,7 +62,7 @@ __device__ inline float ip_load(const unsigned short *p, size_t i) { return __ui
 
 __device__ inline int ip_block_sum(int v, int *scratch)     // 256 threads; the sum, in thread 0
 {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
   __syncthreads();
   return scratch[0] + scratch[1] + scratch[2] + scratch[3];
@@ -170,8 +171,7 @@ __global__ __launch_bounds__(256) void ip_pair_kernel(const unsigned *__restrict
     }
   }
 #pragma unroll
-  for (int k = 0; k < 8; ++k)
-    for (int off = 32; off > 0; off >>= 1) c[k] += __shfl_xor(c[k], off);
+  for (int k = 0; k < 8; ++k) c[k] = wave_sum(c[k]);
   if (lane == 0) {
     int *out = inter + (size_t)n * Q * Q;
 #pragma unroll

@@ -8,12 +8,13 @@
 //                       OR-ed into the image's global bitmap; a value that is negative, above 65 535 or not integral sets
 //                       bit 0 of the image's status word and is otherwise left out
 //   rank_kernel         one workgroup per image: `ignore_label` cleared, the set bits ranked in ascending order -> ids, the kept
-//                       count, table[value] = plane index for the first IT_MAX kept values; more than IT_MAX sets status bit 1
+//                       count, table[value] = plane index for the first LC_MAX kept values; more than LC_MAX sets status bit 1
 //   accumulate_kernel<T> per kept id the pixel count, sum x and sum y: a thread walks 16 consecutive pixels and adds a run of
 //                       equal labels at once (an instance is a blob: most runs are whole strips), LDS integer atomics inside the
 //                       workgroup, 64-bit integer atomic adds of the non-empty entries into the image's totals.  Integer addition
 //                       is associative: the totals are exact and the same from call to call whatever the order
 //   centres_kernel      (sum x / count / W, sum y / count / W) in fp64, rounded to fp32 once
+// What a label value is, the merge of a workgroup's bitmap and the rank step are label_census.hpp's, shared with label_metrics.hip.
 //
 // Planes, two launches: starts_kernel (exclusive prefix sum of the plane counts), then one of
 //   planes_strip_kernel<T>  H * W a multiple of 16: a thread owns 16 consecutive pixels, reads their labels once (once per
@@ -30,26 +31,24 @@
 
 #include <algorithm>
 
+#include "label_census.hpp"    // LC_MAX kept ids per image, LC_VALUES, LC_WORDS, LC_NONE; label_value, census_merge, census_rank
 #include "launchers.hpp"
 
 namespace pct {
 
 namespace {
 
-constexpr int IT_MAX = 512;                     // kept ids per image (the matcher's column limit)
-constexpr int IT_VALUES = 65536;                // label values covered
-constexpr int IT_WORDS = IT_VALUES / 32;        // words of a presence bitmap
 constexpr int IT_BLOCK = 256;
 constexpr int IT_STRIP = 16;                    // consecutive pixels of one thread
 constexpr int IT_PASS = IT_BLOCK * IT_STRIP;    // pixels of one workgroup pass
 constexpr int IT_MAX_CHUNKS = 256;              // workgroups per image of the census kernels
-constexpr unsigned IT_NONE = 0xFFFFu;           // table entry of a value without a plane
 
 // workspace of one image, in bytes: bitmap, totals (count, sum x, sum y: 64-bit each), table (16-bit plane index per value)
 constexpr size_t IT_WS_BITMAP = 0;
-constexpr size_t IT_WS_TOTALS = IT_WS_BITMAP + IT_WORDS * 4;
-constexpr size_t IT_WS_TABLE = IT_WS_TOTALS + (size_t)IT_MAX * 3 * 8;
-constexpr size_t IT_WS_IMAGE = IT_WS_TABLE + (size_t)IT_VALUES * 2;
+constexpr size_t IT_WS_TOTALS = IT_WS_BITMAP + LC_WORDS * 4;
+constexpr size_t IT_WS_TABLE = IT_WS_TOTALS + (size_t)LC_MAX * 3 * 8;
+constexpr size_t IT_WS_IMAGE = IT_WS_TABLE + (size_t)LC_VALUES * 2;
+static_assert(LC_MAX == PCT_TARGETS_MAX_INSTANCES && IT_WS_IMAGE == PCT_TARGETS_WORKSPACE_PER_IMAGE, "the header's limits");
 
 __device__ __forceinline__ unsigned *ws_bitmap(void *ws, int n) { return (unsigned *)((char *)ws + n * IT_WS_IMAGE + IT_WS_BITMAP); }
 __device__ __forceinline__ unsigned long long *ws_totals(void *ws, int n)
@@ -61,32 +60,6 @@ __device__ __forceinline__ unsigned short *ws_table(const void *ws, int n)
   return (unsigned short *)((char *)ws + n * IT_WS_IMAGE + IT_WS_TABLE);
 }
 
-// label value of a pixel, or -1 for a value the tables do not cover (negative, above 65 535, not integral, NaN)
-template <typename T>
-__device__ __forceinline__ int label_value(const T v)
-{
-  const long long w = (long long)v;                                             // (65 535 is no int16 value: compare widened)
-  return (w >= 0 && w < IT_VALUES) ? (int)w : -1;
-}
-template <>
-__device__ __forceinline__ int label_value<float>(const float v)
-{
-  return (v >= 0.f && v <= (float)(IT_VALUES - 1) && v == truncf(v)) ? (int)v : -1;
-}
-
-struct CensusPlan {
-  int passes, chunks;                           // passes of IT_PASS pixels per workgroup; workgroups per image
-};
-
-inline CensusPlan census_plan(const long long P)
-{
-  CensusPlan m;
-  const long long subs = (P + IT_PASS - 1) / IT_PASS;
-  m.passes = (int)((subs + IT_MAX_CHUNKS - 1) / IT_MAX_CHUNKS);
-  m.chunks = (int)((subs + m.passes - 1) / m.passes);
-  return m;
-}
-
 __global__ __launch_bounds__(IT_BLOCK) void init_kernel(void *__restrict__ ws, int *__restrict__ num, int *__restrict__ status)
 {
   const int n = blockIdx.y;
@@ -94,7 +67,7 @@ __global__ __launch_bounds__(IT_BLOCK) void init_kernel(void *__restrict__ ws, i
   unsigned *none = (unsigned *)ws_table(ws, n);
   const int step = gridDim.x * IT_BLOCK, t = blockIdx.x * IT_BLOCK + threadIdx.x;
   for (int i = t; i < (int)(IT_WS_TABLE / 4); i += step) zero[i] = 0u;
-  for (int i = t; i < IT_VALUES / 2; i += step) none[i] = 0xFFFFFFFFu;
+  for (int i = t; i < LC_VALUES / 2; i += step) none[i] = 0xFFFFFFFFu;
   if (t == 0) {
     num[n] = 0;
     status[n] = 0;
@@ -102,13 +75,13 @@ __global__ __launch_bounds__(IT_BLOCK) void init_kernel(void *__restrict__ ws, i
 }
 
 template <typename T>
-__global__ __launch_bounds__(IT_BLOCK) void bitmap_kernel(const T *__restrict__ labels, const int P, const CensusPlan plan,
+__global__ __launch_bounds__(IT_BLOCK) void bitmap_kernel(const T *__restrict__ labels, const int P, const ChunkPlan plan,
                                                           void *__restrict__ ws, int *__restrict__ status)
 {
-  __shared__ unsigned bits[IT_WORDS];
+  __shared__ unsigned bits[LC_WORDS];
   const int n = blockIdx.y;
   const T *lb = labels + (size_t)n * P;
-  for (int i = threadIdx.x; i < IT_WORDS; i += IT_BLOCK) bits[i] = 0u;
+  for (int i = threadIdx.x; i < LC_WORDS; i += IT_BLOCK) bits[i] = 0u;
   __syncthreads();
   bool bad = false;
   int last = -1;
@@ -127,9 +100,7 @@ __global__ __launch_bounds__(IT_BLOCK) void bitmap_kernel(const T *__restrict__ 
     }
   }
   __syncthreads();
-  unsigned *gb = ws_bitmap(ws, n);
-  for (int i = threadIdx.x; i < IT_WORDS; i += IT_BLOCK)
-    if (bits[i]) atomicOr(&gb[i], bits[i]);
+  census_merge<IT_BLOCK>(bits, LC_WORDS, ws_bitmap(ws, n));
   if (bad) atomicOr(&status[n], 1);
 }
 
@@ -137,59 +108,25 @@ __global__ __launch_bounds__(IT_BLOCK) void rank_kernel(void *__restrict__ ws, c
                                                         int *__restrict__ num, int *__restrict__ status)
 {
   __shared__ int first[IT_BLOCK + 1];
-  constexpr int PER = IT_WORDS / IT_BLOCK;                                      // 8 words = 256 values per thread
-  const int n = blockIdx.x, t = threadIdx.x;
-  const unsigned *gb = ws_bitmap(ws, n);
-  unsigned short *table = ws_table(ws, n);
-  unsigned w[PER];
-  int mine = 0;
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    const int word = t * PER + k;
-    w[k] = gb[word];
-    if ((unsigned)ignore_label < (unsigned)IT_VALUES && (ignore_label >> 5) == word) w[k] &= ~(1u << (ignore_label & 31));
-    mine += __popc(w[k]);
-  }
-  first[t + 1] = mine;
-  __syncthreads();
-  if (t == 0) {
-    first[0] = 0;
-    for (int i = 1; i <= IT_BLOCK; ++i) first[i] += first[i - 1];
-  }
-  __syncthreads();
-  int at = first[t];
-  const int total = first[IT_BLOCK];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    unsigned m = w[k];
-    while (m) {
-      const int b = __ffs(m) - 1;
-      m &= m - 1;
-      if (at < IT_MAX) {
-        const int v = (t * PER + k) * 32 + b;
-        ids[n * IT_MAX + at] = v;
-        table[v] = (unsigned short)at;
-      }
-      ++at;
-    }
-  }
-  for (int i = total + t; i < IT_MAX; i += IT_BLOCK) ids[n * IT_MAX + i] = 0;
-  if (t == 0) {
+  const int n = blockIdx.x;
+  const int total = census_rank<IT_BLOCK, false>(ws_bitmap(ws, n), ignore_label, ids, n * LC_MAX, ws_table(ws, n), first, nullptr,
+                                                 nullptr);
+  if (threadIdx.x == 0) {
     num[n] = total;
-    if (total > IT_MAX) atomicOr(&status[n], 2);
+    if (total > LC_MAX) atomicOr(&status[n], 2);
   }
 }
 
 template <typename T>
 __global__ __launch_bounds__(IT_BLOCK) void accumulate_kernel(const T *__restrict__ labels, const int P, const int W,
-                                                              const CensusPlan plan, void *__restrict__ ws)
+                                                              const ChunkPlan plan, void *__restrict__ ws)
 {
-  __shared__ unsigned long long sx[IT_MAX], sy[IT_MAX];
-  __shared__ unsigned cn[IT_MAX];
+  __shared__ unsigned long long sx[LC_MAX], sy[LC_MAX];
+  __shared__ unsigned cn[LC_MAX];
   const int n = blockIdx.y;
   const T *lb = labels + (size_t)n * P;
   const unsigned short *table = ws_table(ws, n);
-  for (int i = threadIdx.x; i < IT_MAX; i += IT_BLOCK) {
+  for (int i = threadIdx.x; i < LC_MAX; i += IT_BLOCK) {
     sx[i] = 0ull;
     sy[i] = 0ull;
     cn[i] = 0u;
@@ -200,11 +137,11 @@ __global__ __launch_bounds__(IT_BLOCK) void accumulate_kernel(const T *__restric
     if (p0 >= P) break;
     const int cnt = (int)min((long long)IT_STRIP, P - p0);
     int y = (int)(p0 / W), x = (int)(p0 - (long long)y * W);
-    unsigned run = IT_NONE, rc = 0u;                                            // the current run: plane index, pixels
+    unsigned run = LC_NONE, rc = 0u;                                            // the current run: plane index, pixels
     unsigned long long rx = 0ull, ry = 0ull;
     for (int k = 0; k < cnt; ++k) {
       const int v = label_value<T>(lb[p0 + k]);
-      const unsigned g = v < 0 ? IT_NONE : (unsigned)table[v];
+      const unsigned g = v < 0 ? LC_NONE : (unsigned)table[v];
       if (g != run) {
         if (rc) {
           atomicAdd(&cn[run], rc);
@@ -215,7 +152,7 @@ __global__ __launch_bounds__(IT_BLOCK) void accumulate_kernel(const T *__restric
         rc = 0u;
         rx = ry = 0ull;
       }
-      if (g != IT_NONE) {
+      if (g != LC_NONE) {
         ++rc;
         rx += (unsigned)x;
         ry += (unsigned)y;
@@ -233,7 +170,7 @@ __global__ __launch_bounds__(IT_BLOCK) void accumulate_kernel(const T *__restric
   }
   __syncthreads();
   unsigned long long *tot = ws_totals(ws, n);
-  for (int i = threadIdx.x; i < IT_MAX; i += IT_BLOCK)
+  for (int i = threadIdx.x; i < LC_MAX; i += IT_BLOCK)
     if (cn[i]) {
       atomicAdd(&tot[i * 3 + 0], (unsigned long long)cn[i]);
       atomicAdd(&tot[i * 3 + 1], sx[i]);
@@ -241,7 +178,7 @@ __global__ __launch_bounds__(IT_BLOCK) void accumulate_kernel(const T *__restric
     }
 }
 
-__global__ __launch_bounds__(IT_MAX) void centres_kernel(void *__restrict__ ws, const int W, const int *__restrict__ num,
+__global__ __launch_bounds__(LC_MAX) void centres_kernel(void *__restrict__ ws, const int W, const int *__restrict__ num,
                                                          int *__restrict__ pixels, float *__restrict__ centres)
 {
   const int n = blockIdx.x, g = threadIdx.x;
@@ -252,9 +189,9 @@ __global__ __launch_bounds__(IT_MAX) void centres_kernel(void *__restrict__ ws, 
     cx = (float)((double)tot[g * 3 + 1] / (double)c / (double)W);
     cy = (float)((double)tot[g * 3 + 2] / (double)c / (double)W);               // (the reference divides both by the width)
   }
-  pixels[n * IT_MAX + g] = (int)c;
-  centres[(n * IT_MAX + g) * 2] = cx;
-  centres[(n * IT_MAX + g) * 2 + 1] = cy;
+  pixels[n * LC_MAX + g] = (int)c;
+  centres[(n * LC_MAX + g) * 2] = cx;
+  centres[(n * LC_MAX + g) * 2 + 1] = cy;
 }
 
 // starts[n] = counts[0] + ... + counts[n - 1]: one workgroup, a thread adds a run of consecutive images
@@ -301,7 +238,7 @@ __global__ __launch_bounds__(IT_BLOCK) void planes_strip_kernel(const T *__restr
   for (int k = 0; k < IT_STRIP; ++k) {
     const T raw = lb[k];
     const int v = label_value<T>(raw);
-    idx[k] = v < 0 ? IT_NONE : (unsigned)table[v];
+    idx[k] = v < 0 ? LC_NONE : (unsigned)table[v];
     if (raw > (T)0) fgw[k >> 2] |= 1u << (8 * (k & 3));
   }
   if (fg && blockIdx.z == 0) *(uint4 *)(fg + (size_t)n * P + p0) = make_uint4(fgw[0], fgw[1], fgw[2], fgw[3]);
@@ -321,7 +258,7 @@ __global__ __launch_bounds__(IT_BLOCK) void planes_strip_kernel(const T *__restr
 }
 
 // the image that owns global plane `plane`: the last n with starts[n] <= plane (images without planes share their successor's
-// start and come before it)
+// start and come before it).  Not row_ranges.hpp's image_of: a 64-bit key and an inclusive upper bound, other instructions
 __device__ __forceinline__ int image_of_plane(const int *__restrict__ starts, const int N, const long long plane)
 {
   int lo = 0, hi = N - 1;
@@ -386,13 +323,13 @@ template <typename T>
 int census_typed(const void *labels, int N, int P, int W, int ignore_label, void *ws, int *ids, int *pixels, float *centres, int *num,
                  int *status, hipStream_t stream)
 {
-  const CensusPlan plan = census_plan(P);
+  const ChunkPlan plan = chunk_plan(P, IT_PASS, IT_MAX_CHUNKS);                 // passes of IT_PASS pixels; workgroups per image
   const T *lb = static_cast<const T *>(labels);
   init_kernel<<<dim3(16, N), IT_BLOCK, 0, stream>>>(ws, num, status);
   bitmap_kernel<T><<<dim3(plan.chunks, N), IT_BLOCK, 0, stream>>>(lb, P, plan, ws, status);
   rank_kernel<<<N, IT_BLOCK, 0, stream>>>(ws, ignore_label, ids, num, status);
   accumulate_kernel<T><<<dim3(plan.chunks, N), IT_BLOCK, 0, stream>>>(lb, P, W, plan, ws);
-  centres_kernel<<<N, IT_MAX, 0, stream>>>(ws, W, num, pixels, centres);
+  centres_kernel<<<N, LC_MAX, 0, stream>>>(ws, W, num, pixels, centres);
   return (int)hipGetLastError();
 }
 

@@ -14,76 +14,50 @@
 //                    compacted indices.  Every lane compares its key with the lane before (lane 0 always starts a run); the
 //                    ballot of run heads gives each head its run length, and the head adds it to T[key] in one atomic
 //   areas_kernel     row and column sums of the table: the pixel count of every value
+// What a label value is, the merge of a workgroup's bitmaps and the rank step are label_census.hpp's, shared with
+// instance_targets.hip.
 // Metrics, one launch of one workgroup per image: see metrics_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "label_census.hpp"    // LC_MAX distinct values per map, LC_VALUES, LC_WORDS, LC_NONE; label_value, census_merge, census_rank
 #include "launchers.hpp"
+#include "wave_reduce.hpp"
 
 namespace pct {
 
 namespace {
 
-constexpr int LM_MAX = 512;                     // distinct values per map (PCT_METRICS_MAX_VALUES)
-constexpr int LM_VALUES = 65536;                // label values covered
-constexpr int LM_WORDS = LM_VALUES / 32;        // words of a presence bitmap
 constexpr int LM_BLOCK = 256;                   // threads of the map kernels = pixels of one workgroup pass
 constexpr int LM_MAX_CHUNKS = 256;              // workgroups per image of the map kernels
-constexpr unsigned LM_NONE = 0xFFFFu;           // index-table entry of a value without an index
 constexpr unsigned LM_NO_KEY = 0xFFFFFFFFu;     // key of a pixel that is in no table cell
-constexpr size_t LM_TABLE = (size_t)LM_MAX * LM_MAX;
+constexpr size_t LM_TABLE = (size_t)LC_MAX * LC_MAX;
 
 // workspace of one image, in bytes: bitmap of side 0, of side 1, index table (16 bit per value) of side 0, of side 1
 constexpr size_t LM_WS_BITMAP = 0;
-constexpr size_t LM_WS_INDEX = LM_WS_BITMAP + 2 * (size_t)LM_WORDS * 4;
-constexpr size_t LM_WS_IMAGE = LM_WS_INDEX + 2 * (size_t)LM_VALUES * 2;
-static_assert(LM_WS_IMAGE == PCT_METRICS_WORKSPACE_PER_IMAGE, "workspace layout and header disagree");
+constexpr size_t LM_WS_INDEX = LM_WS_BITMAP + 2 * (size_t)LC_WORDS * 4;
+constexpr size_t LM_WS_IMAGE = LM_WS_INDEX + 2 * (size_t)LC_VALUES * 2;
+static_assert(LC_MAX == PCT_METRICS_MAX_VALUES && LM_WS_IMAGE == PCT_METRICS_WORKSPACE_PER_IMAGE, "the header's limits");
 
 __device__ __forceinline__ unsigned *ws_bitmap(void *ws, int n, int side)
 {
-  return (unsigned *)((char *)ws + n * LM_WS_IMAGE + LM_WS_BITMAP) + side * LM_WORDS;
+  return (unsigned *)((char *)ws + n * LM_WS_IMAGE + LM_WS_BITMAP) + side * LC_WORDS;
 }
 __device__ __forceinline__ unsigned short *ws_index(const void *ws, int n, int side)
 {
-  return (unsigned short *)((char *)ws + n * LM_WS_IMAGE + LM_WS_INDEX) + side * LM_VALUES;
+  return (unsigned short *)((char *)ws + n * LM_WS_IMAGE + LM_WS_INDEX) + side * LC_VALUES;
 }
 
-// label value of element i of a map of `dtype`, or -1 for a value the tables do not cover (negative, above 65 535, not
-// integral, NaN).  `dtype` is uniform over the launch: the switch costs a scalar branch
+// label_value of element i of a map of `dtype`.  `dtype` is uniform over the launch: the switch costs a scalar branch
 __device__ __forceinline__ int load_label(const void *__restrict__ base, const int dtype, const size_t i)
 {
   switch (dtype) {
-    case 0: return (int)((const uint8_t *)base)[i];
-    case 1: {
-      const int v = (int)((const int16_t *)base)[i];
-      return v >= 0 ? v : -1;
-    }
-    case 2: {
-      const int v = ((const int32_t *)base)[i];
-      return (v >= 0 && v < LM_VALUES) ? v : -1;
-    }
-    case 3: {
-      const long long v = (long long)((const int64_t *)base)[i];
-      return (v >= 0 && v < LM_VALUES) ? (int)v : -1;
-    }
-    default: {
-      const float v = ((const float *)base)[i];
-      return (v >= 0.f && v <= (float)(LM_VALUES - 1) && v == truncf(v)) ? (int)v : -1;
-    }
+    case 0: return label_value(((const uint8_t *)base)[i]);
+    case 1: return label_value(((const int16_t *)base)[i]);
+    case 2: return label_value(((const int32_t *)base)[i]);
+    case 3: return label_value(((const int64_t *)base)[i]);
+    default: return label_value(((const float *)base)[i]);
   }
-}
-
-struct MapPlan {
-  int passes, chunks;                           // passes of LM_BLOCK pixels per workgroup; workgroups per image
-};
-
-inline MapPlan map_plan(const int P)
-{
-  MapPlan m;
-  const int subs = (P + LM_BLOCK - 1) / LM_BLOCK;
-  m.passes = (subs + LM_MAX_CHUNKS - 1) / LM_MAX_CHUNKS;
-  m.chunks = (subs + m.passes - 1) / m.passes;
-  return m;
 }
 
 struct Maps {
@@ -99,19 +73,19 @@ __global__ __launch_bounds__(LM_BLOCK) void init_kernel(void *__restrict__ ws, i
   uint4 *none = (uint4 *)((char *)ws + n * LM_WS_IMAGE + LM_WS_INDEX);
   uint4 *tab = (uint4 *)(table + (size_t)n * LM_TABLE);
   const int step = gridDim.x * LM_BLOCK, t = blockIdx.x * LM_BLOCK + threadIdx.x;
-  for (int i = t; i < (int)(2 * LM_WORDS * 4 / 16); i += step) zero[i] = make_uint4(0u, 0u, 0u, 0u);
-  for (int i = t; i < (int)(2 * LM_VALUES * 2 / 16); i += step) none[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+  for (int i = t; i < (int)(2 * LC_WORDS * 4 / 16); i += step) zero[i] = make_uint4(0u, 0u, 0u, 0u);
+  for (int i = t; i < (int)(2 * LC_VALUES * 2 / 16); i += step) none[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
   for (int i = t; i < (int)(LM_TABLE * 4 / 16); i += step) tab[i] = make_uint4(0u, 0u, 0u, 0u);
   if (t == 0) status[n] = 0;
 }
 
-__global__ __launch_bounds__(LM_BLOCK) void bitmap_kernel(const Maps m, const MapPlan plan, void *__restrict__ ws,
+__global__ __launch_bounds__(LM_BLOCK) void bitmap_kernel(const Maps m, const ChunkPlan plan, void *__restrict__ ws,
                                                           int *__restrict__ status)
 {
-  __shared__ unsigned bits[2][LM_WORDS];
+  __shared__ unsigned bits[2][LC_WORDS];
   const int n = blockIdx.y, lane = threadIdx.x & 63;
   const size_t base = (size_t)n * m.P;
-  for (int i = threadIdx.x; i < 2 * LM_WORDS; i += LM_BLOCK) (&bits[0][0])[i] = 0u;
+  for (int i = threadIdx.x; i < 2 * LC_WORDS; i += LM_BLOCK) (&bits[0][0])[i] = 0u;
   __syncthreads();
   int bad = 0;
   for (int pass = 0; pass < plan.passes; ++pass) {
@@ -130,11 +104,7 @@ __global__ __launch_bounds__(LM_BLOCK) void bitmap_kernel(const Maps m, const Ma
     if (vg >= 0 && (lane == 0 || vg != bg)) atomicOr(&bits[1][vg >> 5], 1u << (vg & 31));
   }
   __syncthreads();
-  unsigned *gb = ws_bitmap(ws, n, 0);                                           // (side 1 follows side 0)
-  for (int i = threadIdx.x; i < 2 * LM_WORDS; i += LM_BLOCK) {
-    const unsigned w = (&bits[0][0])[i];
-    if (w) atomicOr(&gb[i], w);
-  }
+  census_merge<LM_BLOCK>(&bits[0][0], 2 * LC_WORDS, ws_bitmap(ws, n, 0));       // (side 1 follows side 0)
   if (bad) atomicOr(&status[n], bad);
 }
 
@@ -143,66 +113,21 @@ __global__ __launch_bounds__(LM_BLOCK) void rank_kernel(void *__restrict__ ws, i
 {
   __shared__ int first[LM_BLOCK + 1];
   __shared__ int lo, hi;
-  constexpr int PER = LM_WORDS / LM_BLOCK;                                      // 8 words = 256 values per thread
-  const int n = blockIdx.x, side = blockIdx.y, t = threadIdx.x;
-  const unsigned *gb = ws_bitmap(ws, n, side);
-  unsigned short *index = ws_index(ws, n, side);
-  int *out = values + ((size_t)n * 2 + side) * LM_MAX;
-  unsigned w[PER];
-  int mine = 0, mylo = LM_VALUES, myhi = -1;
-  if (t == 0) {
-    lo = LM_VALUES;
-    hi = -1;
-  }
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    w[k] = gb[t * PER + k];
-    mine += __popc(w[k]);
-    if (w[k]) {
-      mylo = min(mylo, (t * PER + k) * 32 + __ffs(w[k]) - 1);
-      myhi = max(myhi, (t * PER + k) * 32 + 31 - __clz(w[k]));
-    }
-  }
-  first[t + 1] = mine;
-  __syncthreads();
-  if (mine) {
-    atomicMin(&lo, mylo);
-    atomicMax(&hi, myhi);
-  }
-  if (t == 0) {
-    first[0] = 0;
-    for (int i = 1; i <= LM_BLOCK; ++i) first[i] += first[i - 1];
-  }
-  __syncthreads();
-  int at = first[t];
-  const int total = first[LM_BLOCK];
-#pragma unroll
-  for (int k = 0; k < PER; ++k) {
-    unsigned b = w[k];
-    while (b) {
-      const int bit = __ffs(b) - 1;
-      b &= b - 1;
-      if (at < LM_MAX) {
-        const int v = (t * PER + k) * 32 + bit;
-        out[at] = v;
-        index[v] = (unsigned short)at;
-      }
-      ++at;
-    }
-  }
-  for (int i = total + t; i < LM_MAX; i += LM_BLOCK) out[i] = 0;
-  if (t == 0) {
+  const int n = blockIdx.x, side = blockIdx.y;
+  const int total = census_rank<LM_BLOCK, true>(ws_bitmap(ws, n, side), -1, values + ((size_t)n * 2 + side) * LC_MAX, 0,
+                                                ws_index(ws, n, side), first, &lo, &hi);
+  if (threadIdx.x == 0) {
     num[n * 2 + side] = total;
     range[(n * 2 + side) * 2] = total ? lo : 0;                                 // (total = 0: every pixel of the map was uncovered)
     range[(n * 2 + side) * 2 + 1] = total ? hi : 0;
     int bitsout = 0;
-    if (total > LM_MAX) bitsout |= side ? PCT_METRICS_STATUS_GT_COUNT : PCT_METRICS_STATUS_PRED_COUNT;
+    if (total > LC_MAX) bitsout |= side ? PCT_METRICS_STATUS_GT_COUNT : PCT_METRICS_STATUS_PRED_COUNT;
     if (hi <= 0) bitsout |= side ? PCT_METRICS_STATUS_EMPTY_GT : PCT_METRICS_STATUS_EMPTY_PRED;
     if (bitsout) atomicOr(&status[n], bitsout);
   }
 }
 
-__global__ __launch_bounds__(LM_BLOCK) void table_kernel(const Maps m, const MapPlan plan, const void *__restrict__ ws,
+__global__ __launch_bounds__(LM_BLOCK) void table_kernel(const Maps m, const ChunkPlan plan, const void *__restrict__ ws,
                                                          int *__restrict__ table)
 {
   const int n = blockIdx.y, lane = threadIdx.x & 63;
@@ -219,7 +144,7 @@ __global__ __launch_bounds__(LM_BLOCK) void table_kernel(const Maps m, const Map
       const int vg = load_label(m.gt, m.gt_dtype, base + i);
       if (vp >= 0 && vg >= 0) {
         const unsigned a = ip[vp], b = ig[vg];
-        if (a != LM_NONE && b != LM_NONE) key = b * LM_MAX + a;                 // a, b < LM_MAX: inside the image's table
+        if (a != LC_NONE && b != LC_NONE) key = b * LC_MAX + a;                 // a, b < LC_MAX: inside the image's table
       }
     }
     const unsigned before = __shfl_up(key, 1);
@@ -233,30 +158,24 @@ __global__ __launch_bounds__(LM_BLOCK) void table_kernel(const Maps m, const Map
   }
 }
 
-__global__ __launch_bounds__(LM_MAX) void areas_kernel(const int *__restrict__ table, const int *__restrict__ num,
+__global__ __launch_bounds__(LC_MAX) void areas_kernel(const int *__restrict__ table, const int *__restrict__ num,
                                                        int *__restrict__ areas)
 {
   const int n = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int nP = min(num[n * 2], LM_MAX), nG = min(num[n * 2 + 1], LM_MAX);
+  const int nP = min(num[n * 2], LC_MAX), nG = min(num[n * 2 + 1], LC_MAX);
   const int *T = table + (size_t)n * LM_TABLE;
-  int *ap = areas + (size_t)n * 2 * LM_MAX, *ag = ap + LM_MAX;
+  int *ap = areas + (size_t)n * 2 * LC_MAX, *ag = ap + LC_MAX;
   int col = 0;
   if (t < nP)
-    for (int g = 0; g < nG; ++g) col += T[g * LM_MAX + t];
+    for (int g = 0; g < nG; ++g) col += T[g * LC_MAX + t];
   ap[t] = col;
   if (t >= nG) ag[t] = 0;
-  for (int g = wave; g < nG; g += LM_MAX / 64) {
+  for (int g = wave; g < nG; g += LC_MAX / 64) {
     int row = 0;
-    for (int p = lane; p < nP; p += 64) row += T[g * LM_MAX + p];
-    for (int off = 32; off; off >>= 1) row += __shfl_xor(row, off);
+    for (int p = lane; p < nP; p += 64) row += T[g * LC_MAX + p];
+    row = wave_sum(row);
     if (lane == 0) ag[g] = row;
   }
-}
-
-__device__ __forceinline__ double wave_max(double v)
-{
-  for (int off = 32; off; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  return v;
 }
 
 // One workgroup of 512 threads per image.  nP, nG: distinct values of the two maps; compact index 0 is the lowest value present
@@ -266,22 +185,22 @@ __device__ __forceinline__ double wave_max(double v)
 //                 foreground pixels of the row that meet predicted foreground (F1's TP)
 //   wave 0        AJI: sequential over the instances, the predictions over the lanes, "taken" as a bit per lane and slot
 //   thread 64     the ordered sums and the remaining columns
-__global__ __launch_bounds__(LM_MAX) void metrics_kernel(const int *__restrict__ values, const int *__restrict__ areas,
+__global__ __launch_bounds__(LC_MAX) void metrics_kernel(const int *__restrict__ values, const int *__restrict__ areas,
                                                          const int *__restrict__ num, const int *__restrict__ range,
                                                          const int *__restrict__ table, double *__restrict__ metrics,
                                                          int *__restrict__ counts)
 {
-  __shared__ int aP[LM_MAX], aG[LM_MAX];
-  __shared__ double termP[LM_MAX], termG[LM_MAX], iouM[LM_MAX];
+  __shared__ int aP[LC_MAX], aG[LC_MAX];
+  __shared__ double termP[LC_MAX], termG[LC_MAX], iouM[LC_MAX];
   __shared__ unsigned long long tp_pixels;
   const int n = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int nP = min(num[n * 2], LM_MAX), nG = min(num[n * 2 + 1], LM_MAX);
+  const int nP = min(num[n * 2], LC_MAX), nG = min(num[n * 2 + 1], LC_MAX);
   const int *T = table + (size_t)n * LM_TABLE;
-  const int p0 = (nP > 0 && values[(size_t)n * 2 * LM_MAX] == 0) ? 1 : 0;
-  const int g0 = (nG > 0 && values[((size_t)n * 2 + 1) * LM_MAX] == 0) ? 1 : 0;
+  const int p0 = (nP > 0 && values[(size_t)n * 2 * LC_MAX] == 0) ? 1 : 0;
+  const int g0 = (nG > 0 && values[((size_t)n * 2 + 1) * LC_MAX] == 0) ? 1 : 0;
   double *out = metrics + (size_t)n * PCT_METRICS_COLUMNS;
-  aP[t] = t < nP ? areas[(size_t)n * 2 * LM_MAX + t] : 0;
-  aG[t] = t < nG ? areas[((size_t)n * 2 + 1) * LM_MAX + t] : 0;
+  aP[t] = t < nP ? areas[(size_t)n * 2 * LC_MAX + t] : 0;
+  aG[t] = t < nG ? areas[((size_t)n * 2 + 1) * LC_MAX + t] : 0;
   termP[t] = termG[t] = iouM[t] = 0.0;
   if (t == 0) tp_pixels = 0ull;
   __syncthreads();
@@ -289,15 +208,15 @@ __global__ __launch_bounds__(LM_MAX) void metrics_kernel(const int *__restrict__
   if (t >= 1 && t < nP) {
     double best = 0.0;
     for (int b = 1; b < nG; ++b) {
-      const int x = T[b * LM_MAX + t];
+      const int x = T[b * LC_MAX + t];
       if (x) best = fmax(best, (double)(2 * x) / (double)(aP[t] + aG[b]));
     }
     termP[t] = best;
   }
-  for (int b = wave; b < nG; b += LM_MAX / 64) {
+  for (int b = wave; b < nG; b += LC_MAX / 64) {
     double best = 0.0, match = 0.0;
     for (int a = lane; a < nP; a += 64) {
-      const int x = T[b * LM_MAX + a];
+      const int x = T[b * LC_MAX + a];
       if (!x) continue;
       if (a >= 1 && b >= 1) best = fmax(best, (double)(2 * x) / (double)(aP[a] + aG[b]));
       if (a >= p0 && b >= g0) {
@@ -310,7 +229,7 @@ __global__ __launch_bounds__(LM_MAX) void metrics_kernel(const int *__restrict__
     if (lane == 0) {
       termG[b] = best;
       iouM[b] = match;
-      if (b >= g0) atomicAdd(&tp_pixels, (unsigned long long)(aG[b] - (p0 ? T[b * LM_MAX] : 0)));
+      if (b >= g0) atomicAdd(&tp_pixels, (unsigned long long)(aG[b] - (p0 ? T[b * LC_MAX] : 0)));
     }
   }
   __syncthreads();
@@ -324,7 +243,7 @@ __global__ __launch_bounds__(LM_MAX) void metrics_kernel(const int *__restrict__
         double bq = -1.0;
         int bi = 0x7FFFFFFF;
         for (int k = 0, a = p0 + lane; a < nP; a += 64, ++k) {
-          const int x = ((taken >> k) & 1u) ? 0 : T[b * LM_MAX + a];
+          const int x = ((taken >> k) & 1u) ? 0 : T[b * LC_MAX + a];
           const double q = x ? (double)x / (double)(aG[b] + aP[a] - x) : 0.0;
           if (q > bq) {
             bq = q;
@@ -341,7 +260,7 @@ __global__ __launch_bounds__(LM_MAX) void metrics_kernel(const int *__restrict__
         }
         const int owner = (bi - p0) & 63, slot = (bi - p0) >> 6;
         const int was = __shfl((int)((taken >> slot) & 1u), owner);
-        const int x = was ? 0 : T[b * LM_MAX + bi];
+        const int x = was ? 0 : T[b * LC_MAX + bi];
         c += x;
         u += was ? aG[b] : aG[b] + aP[bi] - x;
         if (lane == owner) taken |= 1u << slot;
@@ -350,11 +269,8 @@ __global__ __launch_bounds__(LM_MAX) void metrics_kernel(const int *__restrict__
       for (int k = 0, a = p0 + lane; a < nP; a += 64, ++k) {
         if ((taken >> k) & 1u) ++used; else rest += aP[a];
       }
-      for (int off = 32; off; off >>= 1) {
-        rest += __shfl_xor(rest, off);
-        used += __shfl_xor(used, off);
-      }
-      u += rest;
+      u += wave_sum(rest);
+      used = wave_sum(used);
     }
     if (lane == 0) {
       out[4] = u > 0 ? (double)c / (double)u : 0.0;
@@ -418,12 +334,12 @@ int launch_label_overlap(const void *pred, int pred_dtype, const void *gt, int g
   m.pred_dtype = pred_dtype;
   m.gt_dtype = gt_dtype;
   m.P = H * W;
-  const MapPlan plan = map_plan(m.P);
+  const ChunkPlan plan = chunk_plan(m.P, LM_BLOCK, LM_MAX_CHUNKS);               // passes of LM_BLOCK pixels; workgroups per image
   init_kernel<<<dim3(64, N), LM_BLOCK, 0, stream>>>(workspace, table, status);
   bitmap_kernel<<<dim3(plan.chunks, N), LM_BLOCK, 0, stream>>>(m, plan, workspace, status);
   rank_kernel<<<dim3(N, 2), LM_BLOCK, 0, stream>>>(workspace, values, num, range, status);
   table_kernel<<<dim3(plan.chunks, N), LM_BLOCK, 0, stream>>>(m, plan, workspace, table);
-  areas_kernel<<<N, LM_MAX, 0, stream>>>(table, num, areas);
+  areas_kernel<<<N, LC_MAX, 0, stream>>>(table, num, areas);
   return (int)hipGetLastError();
 }
 
@@ -431,7 +347,7 @@ int launch_label_metrics(const int *values, const int *areas, const int *num, co
                          double *metrics, int *counts, hipStream_t stream)
 {
   if (N <= 0 || N > 65535) return PCT_ERR_UNSUPPORTED;
-  metrics_kernel<<<N, LM_MAX, 0, stream>>>(values, areas, num, range, table, metrics, counts);
+  metrics_kernel<<<N, LC_MAX, 0, stream>>>(values, areas, num, range, table, metrics, counts);
   return (int)hipGetLastError();
 }
 

@@ -197,6 +197,21 @@ int launch_cross_attention_bwd_f32(const float *q_c, const float *q_s, const flo
 int launch_lsap(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
                 int *status, hipStream_t stream);
 
+// ---- how the loss, target and metric kernels split an image's pixels: workgroups ("chunks", at most max_chunks per image: that
+// bounds a workspace) that each walk `passes` consecutive passes of per_pass pixels.  The Python workspace formulas mirror it
+// (pctrans_amd/_lib.py: chunk_plan) ----------------------------------------------------------------------------------------
+struct ChunkPlan {
+  int passes, chunks;
+};
+inline ChunkPlan chunk_plan(const long long pixels, const int per_pass, const int max_chunks)
+{
+  ChunkPlan m;
+  const long long subs = (pixels + per_pass - 1) / per_pass;
+  m.passes = (int)((subs + max_chunks - 1) / max_chunks);
+  m.chunks = (int)((subs + m.passes - 1) / m.passes);
+  return m;
+}
+
 // ---- point-sampled mask losses (point_loss.hip; include/pctrans_hip_train.h).  An index array may be nullptr (identity);
 // PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover -----------------------------------------
 int launch_point_sample(const float *planes, const int *plane_index, const float *coords, int num_planes, int H, int W, int K,

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "launchers.hpp"
+#include "wave_reduce.hpp"
 
 namespace pct {
 
@@ -149,9 +150,7 @@ __device__ __forceinline__ void point_loss_forward_body(
     s[3] += t;
   }
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s[i] += __shfl_xor(s[i], d, 64);
+  for (int i = 0; i < 4; ++i) s[i] = wave_sum(s[i]);
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
@@ -269,7 +268,7 @@ __device__ __forceinline__ void point_select_body(const float *__restrict__ pred
   __shared__ unsigned hist[256 * PL_SELECT_COPIES];
   __shared__ unsigned total[256];
   __shared__ unsigned cell[2][PL_SELECT_BLOCK];                            // lower / equal keys per (round, wave), then before it
-  __shared__ unsigned wave_sum[2][WAVES];
+  __shared__ unsigned wave_total[2][WAVES];
   __shared__ unsigned pick[2];                                             // the chosen bin and the rank inside it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int plane = src_index ? src_index[k] : k;
@@ -368,13 +367,13 @@ __device__ __forceinline__ void point_select_body(const float *__restrict__ pred
         const unsigned up = __shfl_up(incl[h], d, 64);
         if (lane >= d) incl[h] += up;
       }
-      if (lane == 63) wave_sum[h][wave] = incl[h];
+      if (lane == 63) wave_total[h][wave] = incl[h];
     }
     __syncthreads();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       unsigned before = incl[h] - v[h];
-      for (int w = 0; w < wave; ++w) before += wave_sum[h][w];
+      for (int w = 0; w < wave; ++w) before += wave_total[h][w];
       if (tid < CELLS) cell[h][tid] = before;
     }
   }

@@ -25,12 +25,15 @@
 // Every sum has one order that depends on the shapes alone: two calls on the same operands give the same bits.
 //
 // A key outside [0, Q) (and a row past the Q-th of its image) reads nothing: its operands are zeros, its row of D is 0, it adds
-// nothing to any gradient, and the status word counts it.  image_start is clamped to [0, num_rows] before it indexes anything.
+// nothing to any gradient, and the status word counts it.  image_start is clamped to [0, num_rows] before it indexes anything
+// (row_ranges.hpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "launchers.hpp"
 #include "msda_win_common.hpp"    // func_attr_per_device
+#include "row_ranges.hpp"         // image_rows, row_image: the clamping rules, shared with reid_query.hip
+#include "wave_reduce.hpp"
 
 namespace pct {
 
@@ -51,19 +54,6 @@ constexpr int RD_BWD_MAX_LDS = ((RD_MAX_Q + RD_BWD_PARTS * RD_BWD_ROWS) * RD_BWD
 
 typedef float rd_f16 __attribute__((ext_vector_type(16)));
 
-struct ReidPlan {
-  int passes, chunks;                     // passes of RD_FWD_PIX pixels per chunk; chunks of an image
-};
-
-inline ReidPlan reid_plan(const long long P)
-{
-  ReidPlan m;
-  const long long subs = (P + RD_FWD_PIX - 1) / RD_FWD_PIX;
-  m.passes = (int)((subs + RD_MAX_CHUNKS - 1) / RD_MAX_CHUNKS);
-  m.chunks = (int)((subs + m.passes - 1) / m.passes);
-  return m;
-}
-
 // e = exp(-|z|) never overflows.  expf and the division are the compiler's accurate ones (no fast-math)
 __device__ __forceinline__ float rd_sigmoid(const float z)
 {
@@ -72,45 +62,9 @@ __device__ __forceinline__ float rd_sigmoid(const float z)
   return z >= 0.f ? r : e * r;
 }
 
-// the rows [first, first + rows) of image n, clamped so that they index key[0 .. I) and at most Q of them count
-__device__ __forceinline__ void rd_image_rows(const int *__restrict__ image_start, const int n, const int I, const int Q, int &first,
-                                              int &rows)
-{
-  const long long a = image_start[n], b = image_start[n + 1];
-  const long long f = a < 0 ? 0 : (a > I ? I : a);
-  long long r = b - f;
-  const long long cap = (long long)(I - f) < Q ? (long long)(I - f) : Q;
-  r = r < 0 ? 0 : (r > cap ? cap : r);
-  first = (int)f;
-  rows = (int)r;
-}
-
-// the image of row i: the largest n in [0, N) with image_start[n] <= i (empty images in front of it skipped)
-__device__ __forceinline__ int rd_image_of(const int *__restrict__ image_start, const int N, const int i)
-{
-  int lo = 0, hi = N;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (image_start[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// row i counts: it lies inside its image's clamped range and its key is a query.  -> the image, or -1
-__device__ __forceinline__ int rd_row_image(const int *__restrict__ image_start, const int *__restrict__ key, const int N, const int I,
-                                            const int Q, const int i)
-{
-  const int n = rd_image_of(image_start, N, i);
-  int first, rows;
-  rd_image_rows(image_start, n, I, Q, first, rows);
-  if (i < first || i >= first + rows) return -1;
-  return (unsigned)key[i] < (unsigned)Q ? n : -1;
-}
-
 __global__ __launch_bounds__(256) void reid_fwd_kernel(const float *__restrict__ z, const int *__restrict__ image_start,
                                                        const int *__restrict__ key, const int Q, const int P, const int I,
-                                                       const int N, const ReidPlan plan, float *__restrict__ ws)
+                                                       const int N, const ChunkPlan plan, float *__restrict__ ws)
 {
   __shared__ float xs[RD_FWD_COLS * RD_FWD_XS];
   __shared__ float ks[RD_FWD_ROWS * RD_FWD_XS];
@@ -118,7 +72,7 @@ __global__ __launch_bounds__(256) void reid_fwd_kernel(const float *__restrict__
   const int chunk = blockIdx.x, n = blockIdx.z, q0 = blockIdx.y * RD_FWD_COLS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, kh = lane >> 5;
   int first, rows;
-  rd_image_rows(image_start, n, I, Q, first, rows);
+  image_rows(image_start, n, I, Q, first, rows);
   const int total = rows + 1;               // the keys' rows, then the row of ones
   const float *zb = z + (size_t)n * Q * P;
   const int wq0 = q0 + wave * 32;
@@ -217,14 +171,14 @@ __global__ __launch_bounds__(256) void reid_fwd_dice_kernel(const float *__restr
     if (tid == 0) bad_rows = 0;
     __syncthreads();
     int bad = 0;
-    for (int r = tid; r < I; r += 256) bad += rd_row_image(image_start, key, N, I, Q, r) < 0 ? 1 : 0;
+    for (int r = tid; r < I; r += 256) bad += row_image(image_start, key, N, I, Q, r) < 0 ? 1 : 0;
     if (bad) atomicAdd(&bad_rows, bad);
     __syncthreads();
     if (tid == 0) *status = bad_rows;
   }
   const int i = blockIdx.x / qblocks, q = (blockIdx.x % qblocks) * 256 + tid;
   if (q >= Q) return;
-  const int n = rd_row_image(image_start, key, N, I, Q, i);
+  const int n = row_image(image_start, key, N, I, Q, i);
   float d = 0.f;
   if (n >= 0) {
     float num = 0.f;
@@ -242,7 +196,7 @@ __global__ __launch_bounds__(256) void reid_bwd_rows_kernel(const float *__restr
 {
   __shared__ float part[4];
   const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = rd_row_image(image_start, key, N, I, Q, i);
+  const int n = row_image(image_start, key, N, I, Q, i);
   const float sk = n >= 0 ? s[(size_t)n * Q + key[i]] : 0.f;
   float sum = 0.f;
   for (int q = tid; q < Q; q += 256) {
@@ -257,8 +211,7 @@ __global__ __launch_bounds__(256) void reid_bwd_rows_kernel(const float *__restr
     b[(size_t)i * Q + q] = bv;
     sum += bv;
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
+  sum = wave_sum(sum);
   if (lane == 0) part[wave] = sum;
   __syncthreads();
   if (tid == 0) rowsum[i] = ((part[0] + part[1]) + part[2]) + part[3];
@@ -272,7 +225,7 @@ __global__ __launch_bounds__(256) void reid_bwd_const_kernel(const float *__rest
   if (idx >= (long long)N * Q) return;
   const int n = (int)(idx / Q), q = (int)(idx % Q);
   int first, rows;
-  rd_image_rows(image_start, n, I, Q, first, rows);
+  image_rows(image_start, n, I, Q, first, rows);
   float c1 = 0.f, c2 = 0.f;
   for (int r = 0; r < rows; ++r) {
     const int i = first + r;
@@ -296,7 +249,7 @@ __global__ __launch_bounds__(256) void reid_bwd_kernel(const float *__restrict__
   const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, kh = lane >> 5;
   const long long p0 = (long long)blockIdx.x * RD_BWD_PIX;
   int first, rows;
-  rd_image_rows(image_start, n, I, Q, first, rows);
+  image_rows(image_start, n, I, Q, first, rows);
   const float *zb = z + (size_t)n * Q * P;
   float *dzb = dz + (size_t)n * Q * P;
 
@@ -448,7 +401,7 @@ int launch_reid_dice_forward(const float *logits, const int *image_start, const 
 {
   if (const int rc = reid_dice_geometry_status(N, Q, h, w, I); rc != PCT_OK) return rc;
   const int P = h * w;
-  const ReidPlan plan = reid_plan(P);
+  const ChunkPlan plan = chunk_plan(P, RD_FWD_PIX, RD_MAX_CHUNKS);          // passes of RD_FWD_PIX pixels per chunk; chunks of an image
   float *ws = static_cast<float *>(workspace);
   const int qgroups = (Q + RD_FWD_COLS - 1) / RD_FWD_COLS, qblocks = (Q + 255) / 256;
   reid_fwd_kernel<<<dim3((unsigned)plan.chunks, (unsigned)qgroups, (unsigned)N), dim3(256), 0, stream>>>(logits, image_start, key, Q,

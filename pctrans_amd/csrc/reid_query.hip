@@ -5,8 +5,8 @@
 // kernels are shaped for few launches and coalesced 16-byte row loads, not for the matrix cores.
 //
 // A row of X ([Q, N, C]: row (q, n) at (q N + n) C) lives in the registers of ONE wave: lane l holds the float4s l and l + 64 of
-// the row (C <= 512).  A dot product of two rows is, in every kernel here, rq_wave_sum(rq_lane_dot(a, b)): per lane an fmaf chain
-// over its (at most 8) channels in ascending order, then a 6-step xor butterfly.  It passes through at most
+// the row (C <= 512).  A dot product of two rows is, in every kernel here, wave_sum(rq_lane_dot(a, b)): per lane an fmaf chain
+// over its (at most 8) channels in ascending order, then a 6-step xor butterfly (wave_reduce.hpp).  It passes through at most
 // RQ_LANE_CHANNELS + RQ_WAVE_STEPS = 14 additions, and equal operand rows give equal bits whichever kernel or wave computes them
 // (the norms of the forward, of the nearest-positive table and of the keys are the same expression).
 //
@@ -21,11 +21,13 @@
 // No floating-point atomic, every sum in one order that depends on the shapes alone: two calls give the same bits.
 //
 // A key outside [0, Q) reads nothing: its rows of S and Cs are 0 and it adds nothing to any gradient.  image_start is clamped to
-// [0, num_rows] before it indexes anything (the conventions of reid_dice.hip).
+// [0, num_rows] before it indexes anything (row_ranges.hpp, shared with reid_dice.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "launchers.hpp"
+#include "row_ranges.hpp"     // image_rows, row_image: the clamping rules, shared with reid_dice.hip
+#include "wave_reduce.hpp"    // wave_sum, wave_max: every lane ends with the same bits
 
 namespace pct {
 
@@ -70,21 +72,6 @@ __device__ __forceinline__ float rq_lane_dot(const RqRow &a, const RqRow &b)
   return s;
 }
 
-// every lane ends with the same bits (each step adds the same two numbers in both lanes of a pair)
-__device__ __forceinline__ float rq_wave_sum(float s)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  return s;
-}
-
-__device__ __forceinline__ float rq_wave_max(float s)
-{
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s = fmaxf(s, __shfl_xor(s, m, 64));
-  return s;
-}
-
 __device__ __forceinline__ void rq_axpy(RqRow &acc, const float a, const RqRow &x)
 {
 #pragma unroll
@@ -96,36 +83,6 @@ __device__ __forceinline__ void rq_axpy(RqRow &acc, const float a, const RqRow &
   }
 }
 
-// the rows [first, first + rows) of image n, clamped so that they index key[0 .. I) and at most Q of them count
-__device__ __forceinline__ void rq_image_rows(const int *__restrict__ image_start, const int n, const int I, const int Q, int &first,
-                                              int &rows)
-{
-  const long long a = image_start[n], b = image_start[n + 1];
-  const long long f = a < 0 ? 0 : (a > I ? I : a);
-  long long r = b - f;
-  const long long cap = (long long)(I - f) < Q ? (long long)(I - f) : Q;
-  r = r < 0 ? 0 : (r > cap ? cap : r);
-  first = (int)f;
-  rows = (int)r;
-}
-
-// row i counts: it lies inside the clamped range of its image (the largest n with image_start[n] <= i) and its key is a query.
-// -> the image, or -1
-__device__ __forceinline__ int rq_row_image(const int *__restrict__ image_start, const int *__restrict__ key, const int N, const int I,
-                                            const int Q, const int i)
-{
-  int lo = 0, hi = N;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (image_start[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  int first, rows;
-  rq_image_rows(image_start, lo, I, Q, first, rows);
-  if (i < first || i >= first + rows) return -1;
-  return (unsigned)key[i] < (unsigned)Q ? lo : -1;
-}
-
 __global__ __launch_bounds__(256) void rq_nearest_kernel(const float *__restrict__ x, const int *__restrict__ pos, const int Q,
                                                          const int N, const int C, const int Pmax, int *__restrict__ nearest)
 {
@@ -134,15 +91,15 @@ __global__ __launch_bounds__(256) void rq_nearest_kernel(const float *__restrict
   if (q >= Q) return;                                                       // (uniform in the wave; the kernel has no barrier)
   const int C4 = C >> 2;
   const RqRow xr = rq_load_row(x + ((size_t)q * N + n) * C, C4, lane);
-  const float nr = fmaxf(sqrtf(rq_wave_sum(rq_lane_dot(xr, xr))), 1e-8f);
+  const float nr = fmaxf(sqrtf(wave_sum(rq_lane_dot(xr, xr))), 1e-8f);
   float best = 0.f;
   int bestp = -1;
   for (int p = 0; p < Pmax; ++p) {
     const int k = pos[(size_t)n * Pmax + p];
     if ((unsigned)k >= (unsigned)Q) continue;                               // padding
     const RqRow xk = rq_load_row(x + ((size_t)k * N + n) * C, C4, lane);
-    const float d = rq_wave_sum(rq_lane_dot(xr, xk));
-    const float nk = fmaxf(sqrtf(rq_wave_sum(rq_lane_dot(xk, xk))), 1e-8f);
+    const float d = wave_sum(rq_lane_dot(xr, xk));
+    const float nk = fmaxf(sqrtf(wave_sum(rq_lane_dot(xk, xk))), 1e-8f);
     const float c = d / (nr * nk);
     if (bestp < 0 || c > best) {                                            // the first maximum wins
       best = c;
@@ -162,17 +119,17 @@ __global__ __launch_bounds__(256) void rq_rows_fwd_kernel(const float *__restric
   if (q >= Q) return;                                                       // (uniform in the wave; the kernel has no barrier)
   const int C4 = C >> 2;
   const RqRow xr = rq_load_row(x + ((size_t)q * N + n) * C, C4, lane);
-  const float mq = fmaxf(sqrtf(rq_wave_sum(rq_lane_dot(xr, xr))), 1e-12f);
+  const float mq = fmaxf(sqrtf(wave_sum(rq_lane_dot(xr, xr))), 1e-12f);
   if (lane == 0) norm[(size_t)n * Q + q] = mq;
   int first, rows;
-  rq_image_rows(image_start, n, I, Q, first, rows);
+  image_rows(image_start, n, I, Q, first, rows);
   for (int r = 0; r < rows; ++r) {
     const int i = first + r, k = key[i];
     float s = 0.f, c = 0.f;
     if ((unsigned)k < (unsigned)Q) {
       const RqRow xk = rq_load_row(x + ((size_t)k * N + n) * C, C4, lane);
-      s = rq_wave_sum(rq_lane_dot(xr, xk));
-      const float mk = fmaxf(sqrtf(rq_wave_sum(rq_lane_dot(xk, xk))), 1e-12f);   // the bits of norm[n, k]
+      s = wave_sum(rq_lane_dot(xr, xk));
+      const float mk = fmaxf(sqrtf(wave_sum(rq_lane_dot(xk, xk))), 1e-12f);   // the bits of norm[n, k]
       c = s / (mq * mk);
     }
     if (lane == 0) {
@@ -190,7 +147,7 @@ __global__ __launch_bounds__(256) void rq_bwd_coef_kernel(const float *__restric
 {
   __shared__ float part[4];
   const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = rq_row_image(image_start, key, N, I, Q, i);
+  const int n = row_image(image_start, key, N, I, Q, i);
   const float mk = n >= 0 ? norm[(size_t)n * Q + key[i]] : 1.f;
   float sum = 0.f;
   for (int q = tid; q < Q; q += 256) {
@@ -204,7 +161,7 @@ __global__ __launch_bounds__(256) void rq_bwd_coef_kernel(const float *__restric
     b[(size_t)i * Q + q] = bv;
     sum += bv;
   }
-  sum = rq_wave_sum(sum);
+  sum = wave_sum(sum);
   if (lane == 0) part[wave] = sum;
   __syncthreads();
   if (tid == 0) rowsum[i] = ((part[0] + part[1]) + part[2]) + part[3];
@@ -216,7 +173,7 @@ __global__ __launch_bounds__(256) void rq_bwd_key_kernel(const float *__restrict
 {
   __shared__ float4 ys[256];
   const int i = blockIdx.x, tid = threadIdx.x;
-  const int n = rq_row_image(image_start, key, N, I, Q, i);
+  const int n = row_image(image_start, key, N, I, Q, i);
   const int C4 = C >> 2;
   const int colp = C4 <= 64 ? 64 : 128, parts = 256 / colp;                 // 4 ranges of queries, or 2
   const int col = tid % colp, part = tid / colp;
@@ -266,7 +223,7 @@ __global__ __launch_bounds__(256) void rq_bwd_kernel(const float *__restrict__ x
 #pragma unroll
   for (int j = 0; j < RQ_ROW_VECS; ++j) acc.v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   int first, rows;
-  rq_image_rows(image_start, n, I, Q, first, rows);
+  image_rows(image_start, n, I, Q, first, rows);
   if (rows > 0) {                                                           // (uniform) an image without rows: exact zeros
     const RqRow xr = rq_load_row(x + row, C4, lane);
     float c1 = 0.f, c2 = 0.f;
@@ -325,8 +282,8 @@ __global__ __launch_bounds__(256) void rq_contrast_kernel(const float *__restric
       if (cls[j] == 2) mxp = fmaxf(mxp, -z[j]);
     }
   }
-  mxn = rq_wave_max(mxn);
-  mxp = rq_wave_max(mxp);
+  mxn = wave_max(mxn);
+  mxp = wave_max(mxp);
   if (lane == 0) {
     red[0][wave] = mxn;
     red[1][wave] = mxp;
@@ -346,8 +303,8 @@ __global__ __launch_bounds__(256) void rq_contrast_kernel(const float *__restric
     sn += en[j];
     sp += ep[j];
   }
-  sn = rq_wave_sum(sn);
-  sp = rq_wave_sum(sp);
+  sn = wave_sum(sn);
+  sp = wave_sum(sp);
   if (lane == 0) {
     red[0][wave] = sn;
     red[1][wave] = sp;

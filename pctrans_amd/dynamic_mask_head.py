@@ -20,10 +20,7 @@ def supported(mask_feats, rel_coord=True):
 
 def train_default():
     """Process default of the decoder's `dmh_train` switch: PCT_DMH_TRAIN = hip | torch (default torch)."""
-    v = os.environ.get("PCT_DMH_TRAIN") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_DMH_TRAIN must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_DMH_TRAIN")
 
 
 def fused_geometry(H, W, target_size):

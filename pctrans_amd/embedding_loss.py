@@ -6,7 +6,6 @@ pctrans_amd/csrc/embedding_loss.hip).
 read straight from the full-resolution planes; `discriminative_loss` is loss/maskformer_criterion.py's function of the same name
 on such a label map with a HIP backward: no torch.unique, no membership matrix, no host synchronisation, bit-identical from call
 to call.  Opt-in: `SetCriterion.emb_loss` is "torch" unless set to "hip" (process default: PCT_EMB_LOSS)."""
-import os
 
 import torch
 
@@ -23,10 +22,7 @@ UNSUPPORTED = -4      # PCT_ERR_UNSUPPORTED
 
 def default():
     """Process default of `SetCriterion.emb_loss`: PCT_EMB_LOSS = hip | torch (default torch)."""
-    v = os.environ.get("PCT_EMB_LOSS") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_EMB_LOSS must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_EMB_LOSS")
 
 
 def supported(embedding, num_labels):
@@ -39,9 +35,7 @@ def supported(embedding, num_labels):
 
 def chunks(pixels):
     """(passes of PIXELS_PER_PASS pixels per chunk, chunks) of include/pctrans_hip_train.h."""
-    subs = -(-pixels // PIXELS_PER_PASS)
-    passes = -(-subs // MAX_CHUNKS)
-    return passes, -(-subs // passes)
+    return _lib.chunk_plan(pixels, PIXELS_PER_PASS, MAX_CHUNKS)
 
 
 def channel_slots(channels):

@@ -443,11 +443,7 @@ def seg_head_forward(x, seg_head, logits):
 
 def fpn_default():
     """Process default of MSDeformAttnPixelDecoder's `fpn` switch: PCT_FPN = hip | torch (default torch)."""
-    import os
-    v = os.environ.get("PCT_FPN") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_FPN must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_FPN")
 
 
 def _fpn_norm_tensors(norm):

@@ -33,7 +33,7 @@ import torch
 
 from . import _lib
 
-MAX_VALUES = 512          # csrc/label_metrics.hip: LM_MAX; PCT_METRICS_MAX_VALUES (distinct values per map, background included)
+MAX_VALUES = 512          # csrc/label_census.hpp: LC_MAX; PCT_METRICS_MAX_VALUES (distinct values per map, background included)
 MAX_LABEL = 65535
 MAX_BATCH = 65535
 MAX_PIXELS = 2 ** 24      # height * width below this
@@ -68,10 +68,7 @@ class Overlap:
 
 def default():
     """Process default of the `mode` argument: PCT_METRICS = hip | torch (default hip: see the module text)."""
-    v = os.environ.get("PCT_METRICS") or "hip"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_METRICS must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_METRICS", "hip")
 
 
 def _mode(mode):

@@ -5,7 +5,6 @@ its forward is the eval path's one launch (MSDA.ms_deform_attn_fused_forward), i
 grad_logits directly -- no locations tensor, no softmax output and no gradient of either as an autograd tensor.  MSDeformAttn takes
 it when a gradient is required and its `train_front` switch is "hip" (PCT_MSDA_TRAIN); otherwise it uses the torch chain of
 pixel_decoder/ops/modules/ms_deform_attn.py."""
-import os
 
 import torch
 
@@ -17,10 +16,7 @@ MAX_SAMPLES = 64        # num_levels * num_point of a record, the kernels' bound
 
 def default():
     """Process default of MSDeformAttn's `train_front` switch: PCT_MSDA_TRAIN = hip | torch (default torch)."""
-    v = os.environ.get("PCT_MSDA_TRAIN") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_MSDA_TRAIN must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_MSDA_TRAIN")
 
 
 def covered(value, reference_points, offsets, logits):

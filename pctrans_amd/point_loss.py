@@ -40,26 +40,17 @@ MAX_HEADS = 16        # heads of one *_many launch (include/pctrans_hip_train.h:
 def default():
     """Process default of `SetCriterion.point_loss` / `Point_HungarianMatcher.point_sample`: PCT_POINT_LOSS = hip | torch
     (default torch)."""
-    v = os.environ.get("PCT_POINT_LOSS") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_POINT_LOSS must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_POINT_LOSS")
 
 
 def select_default():
     """Process default of `SetCriterion.point_select`: PCT_POINT_SELECT = hip | torch (default torch)."""
-    v = os.environ.get("PCT_POINT_SELECT") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_POINT_SELECT must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_POINT_SELECT")
 
 
 def match_cost_default():
     """Process default of `Point_HungarianMatcher.match_cost`: PCT_MATCH_COST = hip | torch (default torch)."""
-    v = os.environ.get("PCT_MATCH_COST") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_MATCH_COST must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_MATCH_COST")
 
 
 def heads_default():

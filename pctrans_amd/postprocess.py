@@ -16,7 +16,6 @@ consequences of that cache:
     `clear_workspaces()` drops them all; call it between geometries when memory matters and no captured graph uses them.
   * calls of one geometry share one buffer, so they must be ordered on one stream (or by events): two streams running the
     same geometry at the same time would overwrite each other's intermediate planes."""
-import os
 
 import torch
 
@@ -29,10 +28,7 @@ _WORKSPACES = {}
 
 def default():
     """Process default of MaskFormer's `postprocess` switch: PCT_POSTPROCESS = hip | torch (default torch)."""
-    v = os.environ.get("PCT_POSTPROCESS") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_POSTPROCESS must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_POSTPROCESS")
 
 
 def plane_words(H, W):

@@ -4,7 +4,6 @@
 `dice_rows` is the rows of query_contrast.dice_for that select_pos_neg_mask keeps -- row k_i of image n_i for every item i --
 with a HIP backward: no [N, Q, P] sigmoid tensor, no [N, Q, Q] matrix, no host synchronisation, bit-identical from call to
 call.  Opt-in: `MultiScaleMaskedTransformerDecoder.reid_dice` is "torch" unless set to "hip" (process default: PCT_REID_DICE)."""
-import os
 
 import torch
 
@@ -19,10 +18,7 @@ UNSUPPORTED = -4          # PCT_ERR_UNSUPPORTED
 
 def default():
     """Process default of `MultiScaleMaskedTransformerDecoder.reid_dice`: PCT_REID_DICE = hip | torch (default torch)."""
-    v = os.environ.get("PCT_REID_DICE") or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_REID_DICE must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_REID_DICE")
 
 
 def supported(logits, rows_per_image):
@@ -39,9 +35,7 @@ def supported(logits, rows_per_image):
 
 def chunks(pixels):
     """(passes of PIXELS_PER_PASS pixels per chunk, chunks) of include/pctrans_hip_reid.h."""
-    subs = -(-pixels // PIXELS_PER_PASS)
-    passes = -(-subs // MAX_CHUNKS)
-    return passes, -(-subs // passes)
+    return _lib.chunk_plan(pixels, PIXELS_PER_PASS, MAX_CHUNKS)
 
 
 def chain_length(pixels):

@@ -7,7 +7,6 @@ Gram matrix that select_pos_neg_query keeps, with their cosines and a HIP backwa
 gather, bit-identical from call to call; `contrast_loss_rows` is _contrast_softplus of the criterion on such rows (or on
 reid_dice.dice_rows'), loss and coefficients in one launch.  Opt-in: `MultiScaleMaskedTransformerDecoder.reid_query` and
 `SetCriterion.contrast_loss` are "torch" unless set to "hip" (process defaults: PCT_REID_QUERY, PCT_CONTRAST_LOSS)."""
-import os
 
 import torch
 
@@ -21,21 +20,14 @@ WAVE_STEPS = 6            # RQ_WAVE_STEPS: the additions of the butterfly over t
 CHAIN_LENGTH = LANE_CHANNELS + WAVE_STEPS     # the L of include/pctrans_hip_reid_query.h
 
 
-def _env(name):
-    v = os.environ.get(name) or "torch"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("%s must be 'hip' or 'torch', got %r" % (name, v))
-    return v
-
-
 def default():
     """Process default of `MultiScaleMaskedTransformerDecoder.reid_query`: PCT_REID_QUERY = hip | torch (default torch)."""
-    return _env("PCT_REID_QUERY")
+    return _lib.env_switch("PCT_REID_QUERY")
 
 
 def contrast_default():
     """Process default of `SetCriterion.contrast_loss`: PCT_CONTRAST_LOSS = hip | torch (default torch)."""
-    return _env("PCT_CONTRAST_LOSS")
+    return _lib.env_switch("PCT_CONTRAST_LOSS")
 
 
 def _query_ok(query):

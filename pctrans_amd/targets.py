@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, _timing
 
-MAX_INSTANCES = 512       # csrc/instance_targets.hip: IT_MAX; PCT_TARGETS_MAX_INSTANCES (the matcher's column limit)
+MAX_INSTANCES = 512       # csrc/label_census.hpp: LC_MAX; PCT_TARGETS_MAX_INSTANCES (the matcher's column limit)
 MAX_LABEL = 65535         # label values the device tables cover: 0 .. 65 535
 MAX_BATCH = 65535
 WORKSPACE_PER_IMAGE = 151552          # PCT_TARGETS_WORKSPACE_PER_IMAGE
@@ -44,10 +44,7 @@ class TargetList(list):
 
 def default():
     """Process default of `prepare_instance_targets(mode=None)`: PCT_TARGETS = hip | torch (default hip: see the module text)."""
-    v = os.environ.get("PCT_TARGETS") or "hip"
-    if v not in ("hip", "torch"):
-        raise RuntimeError("PCT_TARGETS must be 'hip' or 'torch', got %r" % v)
-    return v
+    return _lib.env_switch("PCT_TARGETS", "hip")
 
 
 def supported(label_maps, points_num, device):

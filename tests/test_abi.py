@@ -68,6 +68,29 @@ def test_missing_library_fails_loudly(monkeypatch):
         _lib.lib()
 
 
+SWITCHES = [("point_loss", "default", "PCT_POINT_LOSS", "torch"), ("point_loss", "select_default", "PCT_POINT_SELECT", "torch"),
+            ("point_loss", "match_cost_default", "PCT_MATCH_COST", "torch"), ("postprocess", "default", "PCT_POSTPROCESS", "torch"),
+            ("msda_train", "default", "PCT_MSDA_TRAIN", "torch"), ("embedding_loss", "default", "PCT_EMB_LOSS", "torch"),
+            ("attention_train", "default", "PCT_ATTN_TRAIN", "torch"), ("targets", "default", "PCT_TARGETS", "hip"),
+            ("metrics", "default", "PCT_METRICS", "hip"), ("dynamic_mask_head", "train_default", "PCT_DMH_TRAIN", "torch"),
+            ("reid_dice", "default", "PCT_REID_DICE", "torch"), ("reid_query", "default", "PCT_REID_QUERY", "torch"),
+            ("reid_query", "contrast_default", "PCT_CONTRAST_LOSS", "torch"), ("fused_ops", "fpn_default", "PCT_FPN", "torch")]
+
+
+@pytest.mark.parametrize("module,function,variable,unset", SWITCHES)
+def test_every_hip_torch_switch_keeps_its_default_and_its_message(monkeypatch, module, function, variable, unset):
+    """The process defaults of the opt-in device paths (one rule, pctrans_amd/_lib.py: env_switch): unset or empty gives the
+    module's default, 'hip' and 'torch' are taken, anything else raises with the variable's name and the value."""
+    import importlib
+    default = getattr(importlib.import_module("pctrans_amd." + module), function)
+    for value, want in ((None, unset), ("", unset), ("hip", "hip"), ("torch", "torch")):
+        monkeypatch.delenv(variable, raising=False) if value is None else monkeypatch.setenv(variable, value)
+        assert default() == want
+    monkeypatch.setenv(variable, "triton")
+    with pytest.raises(RuntimeError, match=re.escape("%s must be 'hip' or 'torch', got 'triton'" % variable)):
+        default()
+
+
 def test_cpu_tensors_raise_like_the_reference_extension():
     import torch
     from pctrans_amd import MultiScaleDeformableAttention as MSDA

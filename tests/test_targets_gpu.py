@@ -164,6 +164,37 @@ def test_values_outside_the_tables_give_the_torch_result(dtype, value):
     _same_lists(got, want)
 
 
+@pytest.mark.parametrize("dtype", [torch.int32, torch.float32])
+def test_census_and_label_overlap_keep_the_same_values(dtype):
+    """The census that the targets and the validation metrics share (csrc/label_census.hpp): the kept ids of
+    pct_instance_targets_census, the ground-truth values of pct_label_overlap and torch.unique of the map are one list, element
+    for element.  31 / 32 is a bitmap-word boundary, 255 / 256 the boundary between two threads of the rank step, 65 535 the top
+    value; image 1 holds a subset; `ignore_label` is a value no pixel has, so it leaves nothing out."""
+    from pctrans_amd import _lib, metrics, targets
+    N, H, W = 2, 19, 17
+    p = torch.arange(H * W)
+    full, part = torch.tensor([0, 1, 31, 32, 255, 256, 65535]), torch.tensor([1, 32, 255, 65535])
+    maps = torch.stack([full[p % 7], part[(3 * p) % 4]]).view(N, H, W).to(dtype).to(DEV)
+    ws = torch.empty(N * targets.WORKSPACE_PER_IMAGE // 4, dtype=torch.int32, device=DEV)
+    ids = torch.empty((N, targets.MAX_INSTANCES), dtype=torch.int32, device=DEV)
+    pixels = torch.empty_like(ids)
+    centres = torch.empty((N, targets.MAX_INSTANCES, 2), dtype=torch.float32, device=DEV)
+    word = torch.empty((2, N), dtype=torch.int32, device=DEV)                   # num, status
+    with torch.cuda.device(DEV):
+        rc = _lib.lib().pct_instance_targets_census(maps.data_ptr(), targets._DTYPES[dtype], N, H, W, 7, ws.data_ptr(),
+                                                    ids.data_ptr(), pixels.data_ptr(), centres.data_ptr(), word[0].data_ptr(),
+                                                    word[1].data_ptr(), torch.cuda.current_stream(DEV).cuda_stream)
+    _lib.check(rc, "instance_targets_census")
+    ov = metrics.label_overlap(maps, maps, mode="hip")
+    assert ov.mode == "hip" and ov.status.tolist() == [0, 0]
+    num, status = word.tolist()
+    assert status == [0, 0] and num == [7, 4] and ov.num[:, 1].tolist() == num
+    for n in range(N):
+        want = torch.unique(maps[n]).to(torch.int32)
+        assert torch.equal(ids[n, :num[n]], want) and torch.equal(ov.values[n, 1, :num[n]], want)
+        assert torch.equal(ids[n, :num[n]], ov.values[n, 1, :num[n]])
+
+
 def test_views_repeats_and_the_single_allocation():
     from pctrans_amd import targets
     big = torch.zeros((2, 74, 60), dtype=torch.int64)
