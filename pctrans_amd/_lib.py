@@ -166,6 +166,16 @@ METRICS_SYMBOLS = {
     "pct_label_metrics": ([_vp] * 5 + [_i] + [_vp] * 3, _i, "tests/test_metrics_gpu.py"),
 }
 
+# Entry points of the differentiable fp32 self-attention (include/pctrans_hip_self_attn_train.h; pctrans_amd/self_attention_train.py,
+# reached with SelfAttentionLayer.self_attn_train = "hip").  A table of its own, as the cross-attention's: name -> (argtypes,
+# restype, the test module that checks the entry against float64)
+SELF_ATTN_TRAIN_SYMBOLS = {
+    "pct_self_attention_forward_f32": ([_vp] * 5 + [_i] * 3 + [ctypes.c_float, _vp, _vp, _vp], _i,
+                                       "tests/test_self_attention_train_gpu.py"),
+    "pct_self_attention_backward_f32": ([_vp] * 8 + [_i] * 3 + [ctypes.c_float] + [_vp] * 5, _i,
+                                        "tests/test_self_attention_train_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -185,7 +195,8 @@ def lib():
     for name, (argtypes, restype) in list(SYMBOLS.items()) + [
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
-            + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())]:
+            + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())
+            + list(SELF_ATTN_TRAIN_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

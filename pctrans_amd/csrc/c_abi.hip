@@ -997,4 +997,36 @@ int pct_cross_attention_backward_f32(const float *q_content, const float *q_pos,
                                                         static_cast<hipStream_t>(stream)));
 }
 
+int pct_self_attention_forward_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,
+                                   const float *v, int batch, int heads, int num_query, float scale, float *out, float *lse,
+                                   void *stream)
+{
+  if (batch < 0 || heads <= 0 || num_query < 0) return PCT_ERR_BAD_ARG;
+  if (batch == 0 || num_query == 0) return PCT_OK;
+  if (!q_content || !q_pos || !k_content || !k_pos || !v || !out || !lse) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v | (uintptr_t)out |
+       (uintptr_t)lse) & 15u)
+    return PCT_ERR_ALIGNMENT;
+  return abi_status(pct::launch_self_attention_fwd_f32(q_content, q_pos, k_content, k_pos, v, batch, heads, num_query, scale, out,
+                                                       lse, static_cast<hipStream_t>(stream)));
+}
+
+int pct_self_attention_backward_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,
+                                    const float *v, const float *out, const float *lse, const float *grad_out, int batch,
+                                    int heads, int num_query, float scale, float *workspace, float *grad_q, float *grad_k,
+                                    float *grad_v, void *stream)
+{
+  if (batch < 0 || heads <= 0 || num_query < 0) return PCT_ERR_BAD_ARG;
+  if (batch == 0 || num_query == 0) return PCT_OK;
+  if (!q_content || !q_pos || !k_content || !k_pos || !v || !lse || !grad_out || !workspace || !grad_q || !grad_k || !grad_v)
+    return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v | (uintptr_t)lse |
+       (uintptr_t)grad_out | (uintptr_t)workspace | (uintptr_t)grad_q | (uintptr_t)grad_k | (uintptr_t)grad_v) & 15u)
+    return PCT_ERR_ALIGNMENT;
+  (void)out;
+  return abi_status(pct::launch_self_attention_bwd_f32(q_content, q_pos, k_content, k_pos, v, lse, grad_out, batch, heads,
+                                                       num_query, scale, workspace, grad_q, grad_k, grad_v,
+                                                       static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

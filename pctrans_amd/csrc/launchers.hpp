@@ -194,6 +194,13 @@ int launch_cross_attention_bwd_f32(const float *q_c, const float *q_s, const flo
                                    const float *grad_out, int N, int heads, int Q, int S, float scale, float *workspace,
                                    float *grad_q_c, float *grad_q_s, float *grad_k_c, float *grad_k_p, float *grad_v,
                                    hipStream_t stream);
+// differentiable fp32 self-attention (self_attention_train.hip; include/pctrans_hip_self_attn_train.h).  PCT_NOT_COVERED: heads
+// outside {4, 8}, more than 512 queries or an operand of 2^31 elements or more.  workspace: N * heads * Q floats
+int launch_self_attention_fwd_f32(const float *q_c, const float *q_p, const float *k_c, const float *k_p, const float *v, int N,
+                                  int heads, int Q, float scale, float *out, float *lse, hipStream_t stream);
+int launch_self_attention_bwd_f32(const float *q_c, const float *q_p, const float *k_c, const float *k_p, const float *v,
+                                  const float *lse, const float *grad_out, int N, int heads, int Q, float scale, float *workspace,
+                                  float *grad_q, float *grad_k, float *grad_v, hipStream_t stream);
 int launch_lsap(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
                 int *status, hipStream_t stream);
 

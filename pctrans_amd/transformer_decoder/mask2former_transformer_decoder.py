@@ -36,6 +36,7 @@ from .. import dynamic_mask_head as dmh
 from .. import fused_ops
 from .. import reid_dice
 from .. import reid_query
+from .. import self_attention_train
 from ..layers import CachedLinear, Conv2d, c2_xavier_fill, get_norm
 from .attention import MultiheadAttention
 from .position_encoding import PositionEmbeddingSine
@@ -106,14 +107,29 @@ class SelfAttentionLayer(nn.Module):
         self.self_attn = MultiheadAttention(d_model, nhead, dropout=dropout, vdim=d_model)
         self.norm1 = nn.LayerNorm(d_model)
         self.dropout1 = nn.Dropout(dropout)
+        # "hip": when a gradient is required, fp32 operands outside autocast without a mask go through the differentiable
+        # kernels (self_attention_train.py) instead of the torch chain.  A plain attribute; process default from
+        # PCT_SELF_ATTN_TRAIN
+        self.self_attn_train = self_attention_train.default()
         _xavier_all(self)
 
     def forward_post(self, tgt, tgt_mask: Optional[Tensor] = None, tgt_key_padding_mask: Optional[Tensor] = None,
                      query_pos: Optional[Tensor] = None):
         t, qp = _lp(tgt), _lp(query_pos)
-        q = self.sa_qcontent_proj(t) + self.sa_qpos_proj(qp)
-        k = self.sa_kcontent_proj(t) + self.sa_kpos_proj(qp)
+        h = self.self_attn.num_heads
+        q_c, q_p = self.sa_qcontent_proj(t), self.sa_qpos_proj(qp)
+        k_c, k_p = self.sa_kcontent_proj(t), self.sa_kpos_proj(qp)
         v = self.sa_v_proj(t)
+        # the differentiable fp32 kernels take the five projections' outputs as they are: the two adds are made inside them
+        train = (self.self_attn_train == "hip" and tgt_mask is None and tgt_key_padding_mask is None and torch.is_grad_enabled()
+                 and v.is_cuda and v.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+                 and (q_c.requires_grad or q_p.requires_grad or k_c.requires_grad or k_p.requires_grad or v.requires_grad)
+                 and tgt.shape[2] // h == 16 and self.self_attn.dropout == 0.0)
+        if train and self_attention_train.supported(q_c, q_p, k_c, k_p, v, h):
+            core = self_attention_train.self_attention_train(q_c, q_p, k_c, k_p, v, h)
+            return self.norm1(tgt + self.dropout1(self.self_attn.out_proj(core)))
+        q = q_c + q_p
+        k = k_c + k_p
         tgt2 = self.self_attn(q, k, value=v, attn_mask=tgt_mask, key_padding_mask=tgt_key_padding_mask)[0]
         return self.norm1(tgt + self.dropout1(tgt2))
 
