@@ -3,7 +3,11 @@
 `cross_attention_train` is a torch.autograd.Function on the split operands the projections write -- no per-head
 concatenation, no [N, heads, Q, S] tensor in forward or backward; it keeps the five operands, `out` and `lse` for the backward
 and nothing else.  CrossAttentionLayer takes it when a gradient is required and its `attn_train` switch is "hip"
-(PCT_ATTN_TRAIN); otherwise it uses the torch chain of transformer_decoder/attention.py."""
+(PCT_ATTN_TRAIN); otherwise it uses the torch chain of transformer_decoder/attention.py.
+
+The helpers both differentiable attention paths share live here (self_attention_train.py imports them): HEAD_DIM, _HEADS,
+_dense, workspace_bytes, the operand check _operands_ok, and the allocate / launch / check steps _dense_operands, _out_and_lse,
+_workspace and _call."""
 
 import torch
 
@@ -26,23 +30,28 @@ def _mask_ok(attn_mask, N, Q, S, device):
                                  and tuple(attn_mask.shape) in ((N, 1, Q, S), (N, Q, S)))
 
 
+def _operands_ok(q_ops, k_ops, heads):
+    """Five fp32 device tensors on one device outside autocast: q_ops [Q, N, heads * 16], k_ops [S, N, heads * 16], heads 4 or
+    8, at least one query, key and image, N within the grid's z extent and every tensor below 2^31 elements."""
+    ts = tuple(q_ops) + tuple(k_ops)
+    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in ts):
+        return False
+    if torch.is_autocast_enabled("cuda") or len({t.device for t in ts}) != 1:
+        return False
+    Q, N, C = q_ops[0].shape
+    S = k_ops[0].shape[0]
+    if heads not in _HEADS or C != heads * HEAD_DIM or min(Q, N, S) < 1 or N > 65535 or max(Q, S) * N * C >= 2 ** 31:
+        return False
+    return all(tuple(t.shape) == (Q, N, C) for t in q_ops) and all(tuple(t.shape) == (S, N, C) for t in k_ops)
+
+
 def covered(q_c, q_s, k_c, k_p, v, heads, attn_mask=None, row_open=None):
     """True where the kernels can run: five fp32 device operands [Q | S, N, heads * 16] outside autocast, heads 4 or 8, at
     least one query, key and image, a bool mask [N, 1, Q, S] (or [N, Q, S]) or none, a bool row_open of N * Q elements or
     none, everything on one device."""
-    ts = (q_c, q_s, k_c, k_p, v)
-    if not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 for t in ts):
+    if not _operands_ok((q_c, q_s), (k_c, k_p, v), heads):
         return False
-    if torch.is_autocast_enabled("cuda"):
-        return False
-    Q, N, C = q_c.shape
-    S = k_c.shape[0]
-    if heads not in _HEADS or C != heads * HEAD_DIM or min(Q, N, S) < 1 or N > 65535:
-        return False
-    if tuple(q_s.shape) != (Q, N, C) or any(tuple(t.shape) != (S, N, C) for t in (k_c, k_p, v)):
-        return False
-    if max(Q, S) * N * C >= 2 ** 31 or len({t.device for t in ts}) != 1:
-        return False
+    (Q, N, _), S = q_c.shape, k_c.shape[0]
     if not _mask_ok(attn_mask, N, Q, S, q_c.device):
         return False
     if row_open is not None and (row_open.dtype != torch.bool or row_open.device != q_c.device or row_open.numel() != N * Q):
@@ -57,7 +66,8 @@ def supported(q_c, q_s, k_c, k_p, v, heads, attn_mask=None, row_open=None):
 
 
 def workspace_bytes(N, heads, Q):
-    """include/pctrans_hip_attn_train.h, pct_cross_attention_backward_f32: D = rowsum(grad_out * out), one float per row."""
+    """include/pctrans_hip_attn_train.h, pct_cross_attention_backward_f32, and include/pctrans_hip_self_attn_train.h,
+    pct_self_attention_backward_f32: D = rowsum(grad_out * out), one float per row."""
     return 4 * N * heads * Q
 
 
@@ -65,6 +75,32 @@ def _dense(t):
     """fp32, contiguous, 16-byte aligned (a view at an odd offset is copied)."""
     t = t.detach().float().contiguous()
     return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _dense_operands(operands):
+    """The five operands as the kernels read them (`_dense`)."""
+    if not operands[0].is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    return [_dense(t) for t in operands]
+
+
+def _out_and_lse(q_c, heads):
+    Q, N, C = q_c.shape
+    return (torch.empty((Q, N, C), dtype=torch.float32, device=q_c.device),
+            torch.empty((2, N, heads, Q), dtype=torch.float32, device=q_c.device))
+
+
+def _workspace(q_c, heads):
+    """The backward's N * heads * Q floats, from torch's caching allocator (which also works inside a graph capture)."""
+    Q, N, _ = q_c.shape
+    return torch.empty((max(workspace_bytes(N, heads, Q) // 4, 4),), dtype=torch.float32, device=q_c.device)
+
+
+def _call(name, label, ref, *args):
+    """C ABI entry pct_`name` on `ref`'s device and current stream, timed as `label`; a status other than 0 raises."""
+    with torch.cuda.device(ref.device), _timing.timed(label, ref):
+        rc = getattr(_lib.lib(), "pct_" + name)(*args, torch.cuda.current_stream(ref.device).cuda_stream)
+    _lib.check(rc, name)
 
 
 def _bytes(t):
@@ -78,19 +114,12 @@ def _ptr(t):
 def cross_attention_forward(q_c, q_s, k_c, k_p, v, heads, attn_mask=None, row_open=None):
     """-> (out [Q, N, heads * 16] fp32, lse [2, N, heads, Q] fp32: row maximum + log of the row sum and its low-order word).
     A row with nothing attendable: out 0, lse 0."""
-    if not q_c.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
-    Q, N, C = q_c.shape
-    S = k_c.shape[0]
-    ops = [_dense(t) for t in (q_c, q_s, k_c, k_p, v)]
+    ops = _dense_operands((q_c, q_s, k_c, k_p, v))
+    (Q, N, _), S = q_c.shape, k_c.shape[0]
     m, ro = _bytes(attn_mask), _bytes(row_open)
-    out = torch.empty((Q, N, C), dtype=torch.float32, device=q_c.device)
-    lse = torch.empty((2, N, heads, Q), dtype=torch.float32, device=q_c.device)
-    with torch.cuda.device(q_c.device), _timing.timed("cross_attention train forward", out):
-        rc = _lib.lib().pct_cross_attention_forward_f32(
-            *[t.data_ptr() for t in ops], _ptr(m), _ptr(ro), N, heads, Q, S, float(2 * HEAD_DIM) ** -0.5, out.data_ptr(),
-            lse.data_ptr(), torch.cuda.current_stream(q_c.device).cuda_stream)
-    _lib.check(rc, "cross_attention_forward_f32")
+    out, lse = _out_and_lse(q_c, heads)
+    _call("cross_attention_forward_f32", "cross_attention train forward", out, *[t.data_ptr() for t in ops], _ptr(m), _ptr(ro),
+          N, heads, Q, S, float(2 * HEAD_DIM) ** -0.5, out.data_ptr(), lse.data_ptr())
     return out, lse
 
 
@@ -98,21 +127,15 @@ def cross_attention_backward(q_c, q_s, k_c, k_p, v, heads, attn_mask, row_open, 
     """-> (grad_q_c, grad_q_s, grad_k_c, grad_k_p, grad_v), fp32 contiguous in the operands' layouts.  Deterministic: two calls
     on the same operands give the same bits.  The C entry allocates nothing; this wrapper takes the outputs and the
     N * heads * Q float workspace from torch's caching allocator, which also works inside a graph capture."""
-    if not q_c.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
-    Q, N, C = q_c.shape
-    S = k_c.shape[0]
-    ops = [_dense(t) for t in (q_c, q_s, k_c, k_p, v)]
+    ops = _dense_operands((q_c, q_s, k_c, k_p, v))
+    (Q, N, _), S = q_c.shape, k_c.shape[0]
     l, go = _dense(lse), _dense(grad_out)
     m, ro = _bytes(attn_mask), _bytes(row_open)
     grads = [torch.empty_like(t) for t in ops]
-    ws = torch.empty((max(workspace_bytes(N, heads, Q) // 4, 4),), dtype=torch.float32, device=q_c.device)
-    with torch.cuda.device(q_c.device), _timing.timed("cross_attention train backward", go):
-        rc = _lib.lib().pct_cross_attention_backward_f32(
-            *[t.data_ptr() for t in ops], _ptr(m), _ptr(ro), out.data_ptr(), l.data_ptr(), go.data_ptr(), N, heads, Q, S,
-            float(2 * HEAD_DIM) ** -0.5, ws.data_ptr(), *[g.data_ptr() for g in grads],
-            torch.cuda.current_stream(q_c.device).cuda_stream)
-    _lib.check(rc, "cross_attention_backward_f32")
+    ws = _workspace(q_c, heads)
+    _call("cross_attention_backward_f32", "cross_attention train backward", go, *[t.data_ptr() for t in ops], _ptr(m), _ptr(ro),
+          out.data_ptr(), l.data_ptr(), go.data_ptr(), N, heads, Q, S, float(2 * HEAD_DIM) ** -0.5, ws.data_ptr(),
+          *[g.data_ptr() for g in grads])
     return tuple(grads)
 
 

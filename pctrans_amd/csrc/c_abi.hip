@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "launchers.hpp"
 #include "msda_common.hpp"
 
@@ -961,16 +963,30 @@ int pct_cross_attention_bf16(const void *q_content, const void *q_pos, const voi
                                                 num_query, num_key, scale, out, static_cast<hipStream_t>(stream)));
 }
 
+// The argument checks of the four differentiable fp32 attention entries, in the order the ABI fixes: a negative size or no head,
+// the empty call (nothing is read, every pointer may be null), a null pointer, a pointer off 16 bytes (self-attention:
+// num_key = num_query).  -> true: launch; false: return *status.
+static bool attn_train_args(int batch, int heads, int num_query, int num_key, std::initializer_list<const void *> ptrs,
+                            int *status)
+{
+  *status = PCT_OK;
+  if (batch < 0 || heads <= 0 || num_query < 0 || num_key < 0) *status = PCT_ERR_BAD_ARG;
+  if (*status != PCT_OK || batch == 0 || num_query == 0 || num_key == 0) return false;
+  uintptr_t bits = 0;
+  for (const void *p : ptrs) {
+    if (!p) *status = PCT_ERR_BAD_ARG;
+    bits |= (uintptr_t)p;
+  }
+  if (*status == PCT_OK && (bits & 15u)) *status = PCT_ERR_ALIGNMENT;
+  return *status == PCT_OK;
+}
+
 int pct_cross_attention_forward_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,
                                     const float *v, const unsigned char *mask, const unsigned char *row_open, int batch, int heads,
                                     int num_query, int num_key, float scale, float *out, float *lse, void *stream)
 {
-  if (batch < 0 || heads <= 0 || num_query < 0 || num_key < 0) return PCT_ERR_BAD_ARG;
-  if (batch == 0 || num_query == 0 || num_key == 0) return PCT_OK;
-  if (!q_content || !q_pos || !k_content || !k_pos || !v || !out || !lse) return PCT_ERR_BAD_ARG;
-  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v | (uintptr_t)out |
-       (uintptr_t)lse) & 15u)
-    return PCT_ERR_ALIGNMENT;
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_key, {q_content, q_pos, k_content, k_pos, v, out, lse}, &status)) return status;
   return abi_status(pct::launch_cross_attention_fwd_f32(q_content, q_pos, k_content, k_pos, v, mask, mask ? row_open : nullptr, batch,
                                                         heads, num_query, num_key, scale, out, lse,
                                                         static_cast<hipStream_t>(stream)));
@@ -982,15 +998,12 @@ int pct_cross_attention_backward_f32(const float *q_content, const float *q_pos,
                                      float scale, float *workspace, float *grad_q_content, float *grad_q_pos, float *grad_k_content,
                                      float *grad_k_pos, float *grad_v, void *stream)
 {
-  if (batch < 0 || heads <= 0 || num_query < 0 || num_key < 0) return PCT_ERR_BAD_ARG;
-  if (batch == 0 || num_query == 0 || num_key == 0) return PCT_OK;
-  if (!q_content || !q_pos || !k_content || !k_pos || !v || !lse || !grad_out || !workspace || !grad_q_content ||
-      !grad_q_pos || !grad_k_content || !grad_k_pos || !grad_v)
-    return PCT_ERR_BAD_ARG;
-  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v |
-       (uintptr_t)lse | (uintptr_t)grad_out | (uintptr_t)workspace | (uintptr_t)grad_q_content | (uintptr_t)grad_q_pos |
-       (uintptr_t)grad_k_content | (uintptr_t)grad_k_pos | (uintptr_t)grad_v) & 15u)
-    return PCT_ERR_ALIGNMENT;
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_key,
+                       {q_content, q_pos, k_content, k_pos, v, lse, grad_out, workspace, grad_q_content, grad_q_pos,
+                        grad_k_content, grad_k_pos, grad_v},
+                       &status))
+    return status;
   return abi_status(pct::launch_cross_attention_bwd_f32(q_content, q_pos, k_content, k_pos, v, mask, mask ? row_open : nullptr, out, lse,
                                                         grad_out, batch, heads, num_query, num_key, scale, workspace, grad_q_content,
                                                         grad_q_pos, grad_k_content, grad_k_pos, grad_v,
@@ -1001,12 +1014,9 @@ int pct_self_attention_forward_f32(const float *q_content, const float *q_pos, c
                                    const float *v, int batch, int heads, int num_query, float scale, float *out, float *lse,
                                    void *stream)
 {
-  if (batch < 0 || heads <= 0 || num_query < 0) return PCT_ERR_BAD_ARG;
-  if (batch == 0 || num_query == 0) return PCT_OK;
-  if (!q_content || !q_pos || !k_content || !k_pos || !v || !out || !lse) return PCT_ERR_BAD_ARG;
-  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v | (uintptr_t)out |
-       (uintptr_t)lse) & 15u)
-    return PCT_ERR_ALIGNMENT;
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_query, {q_content, q_pos, k_content, k_pos, v, out, lse}, &status))
+    return status;
   return abi_status(pct::launch_self_attention_fwd_f32(q_content, q_pos, k_content, k_pos, v, batch, heads, num_query, scale, out,
                                                        lse, static_cast<hipStream_t>(stream)));
 }
@@ -1016,13 +1026,10 @@ int pct_self_attention_backward_f32(const float *q_content, const float *q_pos, 
                                     int heads, int num_query, float scale, float *workspace, float *grad_q, float *grad_k,
                                     float *grad_v, void *stream)
 {
-  if (batch < 0 || heads <= 0 || num_query < 0) return PCT_ERR_BAD_ARG;
-  if (batch == 0 || num_query == 0) return PCT_OK;
-  if (!q_content || !q_pos || !k_content || !k_pos || !v || !lse || !grad_out || !workspace || !grad_q || !grad_k || !grad_v)
-    return PCT_ERR_BAD_ARG;
-  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v | (uintptr_t)lse |
-       (uintptr_t)grad_out | (uintptr_t)workspace | (uintptr_t)grad_q | (uintptr_t)grad_k | (uintptr_t)grad_v) & 15u)
-    return PCT_ERR_ALIGNMENT;
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_query,
+                       {q_content, q_pos, k_content, k_pos, v, lse, grad_out, workspace, grad_q, grad_k, grad_v}, &status))
+    return status;
   (void)out;
   return abi_status(pct::launch_self_attention_bwd_f32(q_content, q_pos, k_content, k_pos, v, lse, grad_out, batch, heads,
                                                        num_query, scale, workspace, grad_q, grad_k, grad_v,
