@@ -30,6 +30,8 @@ constexpr int FZ_W = 128;              // feature-map width this kernel is built
 constexpr int FZ_BAND = 8;             // rows per workgroup
 constexpr int FZ_TILES = 20;           // per wave: 2 x 8 own tiles + 4 halo tiles
 constexpr int FZ_SLOTS = FZ_BAND + 2;  // LDS rows per buffer: halo above, the band, halo below
+constexpr int FZ_STORE_NT = 2;         // aux bit 1 of a buffer store: the non-temporal hint
+constexpr int FZ_DROP = 0x7ffffff0;    // a byte offset no descriptor of this kernel reaches: the store is dropped
 
 // one wave per (image, query pair): the pair's generated parameters in the form DmhPair::take reads them
 template <bool REL>
@@ -85,12 +87,23 @@ __global__ __launch_bounds__(256, FZ_WGS) void dmh_fused_kernel(const float *__r
   const int OW = 2 * W;
   const int th_w = W / SC;                                                   // attention-mask row length
 
+  // byte offsets of this lane's stores inside the pair's planes (the descriptors: below)
+  const int up_plane_b = 4 * HW * 2, m_plane_b = (H / SC) * th_w;
+  const int u_off = qsel * up_plane_b + ((2 * y0 + par) * OW + 16 * col) * 2;
+  const bool m_mine = (SC == 2 || (y0 & (SC - 1)) == SC / 2) && !par;
+  const int m_ty = SC == 2 ? y0 / 2 : (y0 - SC / 2) / SC;
+  const int m_off = m_mine ? qsel * m_plane_b + m_ty * th_w + (8 / SC) * col : FZ_DROP;
+
   const int npairs = (Q + 1) / 2;
   // the pairs' parameters in the form the MFMAs take them, written by dmh_prepare_kernel: 5 coalesced 16-byte loads per lane
   // and pair instead of ~40 scattered dword loads and ~100 vector instructions of splitting and packing in EACH of the
   // image's 16 bands (a fifth of a pair's cycles before); the next pair's are in flight while this pair is computed
   const unsigned *wsn = ws + (size_t)n * npairs * (DmhPair<REL>::PREP_DWORDS * 64);
   typename DmhPair<REL>::Prepared prep = DmhPair<REL>::fetch_prepared(wsn, lane);
+  // the first pair's parameters are complete before the loop: entered with these loads pending and nothing behind them, the
+  // loop's top would have to wait vmcnt(0), and on the way round that wait takes the previous pair's stores with it
+#pragma unroll
+  for (int k = 0; k < 5; ++k) asm volatile("" : "+v"(prep.v[k]));
   // The attention-mask byte of a bf16 value v is  bf16(sigmoid(v)) < 0.5.  sigmoid is monotonic and bf16(.) rounds 0.5 - x/4
   // to 0.5 for every bf16 |x| < 2^-8 and below it for every |x| > 2^-8, so the byte is (v < -2^-8) except AT v = -2^-8, where
   // the fp32 evaluation decides: evaluated once here with the very expression the two-launch path uses
@@ -99,7 +112,6 @@ __global__ __launch_bounds__(256, FZ_WGS) void dmh_fused_kernel(const float *__r
     DmhPair<REL> pw;
     pw.take(prep);
     prep = DmhPair<REL>::fetch_prepared(wsn + (size_t)min(pr + 1, npairs - 1) * (DmhPair<REL>::PREP_DWORDS * 64), lane);
-    const int q_acc = min(2 * pr + qsel, Q - 1);
     const int buf = pr & 1;
 
     // ---- logits of my tiles, rounded to bf16 (what the two-launch path stores and reads back) -----------------------------
@@ -154,8 +166,6 @@ __global__ __launch_bounds__(256, FZ_WGS) void dmh_fused_kernel(const float *__r
     // ---- x2 upsample: horizontal blends of the three rows once, then the two output rows ---------------------------------
     // even output column 2 (x0 + k): source columns (x0 + k - 1, x0 + k), weights (1/4, 3/4) -- at the map's left edge
     // (1, 0) on the clamped pair; odd column: (x0 + k, x0 + k + 1), weights (3/4, 1/4)
-    const bool wr = 2 * pr + qsel < Q;
-    __bf16 *uplane = up + ((size_t)n * Q + q_acc) * (size_t)(4 * HW);
     float tx[3][16];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
@@ -172,24 +182,30 @@ __global__ __launch_bounds__(256, FZ_WGS) void dmh_fused_kernel(const float *__r
       ob[k >> 2][k & 3] = pack_bf16x2(dm_blend_y(hB0, hB1, tx[1][2 * k], tx[2][2 * k]),
                                        dm_blend_y(hB0, hB1, tx[1][2 * k + 1], tx[2][2 * k + 1]));
     }
-    if (wr) {
+    // Every lane stores, in straight-line code: a store inside a branch is one the compiler cannot count, and the wait for the
+    // next pair's parameters at the loop's top then becomes vmcnt(0) -- on this target one counter holds loads and stores in
+    // issue order -- which drains this pair's 4 KB of stores per wave before the next pair may start.  The descriptors span
+    // the planes of the pair's queries that exist (two, or one for the last pair of an odd Q): the second query's lane groups
+    // are one plane further in and fall off the end where it does not exist, and the hardware drops their stores.
+    const int nq = min(2, Q - 2 * pr);
+    const size_t plane0 = (size_t)n * Q + 2 * pr;
+    {
       // output rows 2 y0 + par (from window rows 0, 1) and 2 y1 + par (rows 1, 2), columns 16 col .. 16 col + 15
-      __bf16 *ra = uplane + (size_t)(2 * y0 + par) * OW + 16 * col;
-      __bf16 *rb = uplane + (size_t)(2 * y1 + par) * OW + 16 * col;
+      const auto ru = __builtin_amdgcn_make_buffer_rsrc(up + plane0 * (size_t)(4 * HW), 0, nq * up_plane_b, 0x00020000);
       // (non-temporal: 1.68 GB per call that nothing in this kernel reads back -- kept out of the L2's way of the feature
       // tiles and the query pairs' parameters: 0.64-0.66 -> 0.58-0.61 ms per call at batch 128, two same-box alternations)
-      __builtin_nontemporal_store(oa[0], reinterpret_cast<dm_u32x4 *>(ra));
-      __builtin_nontemporal_store(oa[1], reinterpret_cast<dm_u32x4 *>(ra + 8));
-      __builtin_nontemporal_store(ob[0], reinterpret_cast<dm_u32x4 *>(rb));
-      __builtin_nontemporal_store(ob[1], reinterpret_cast<dm_u32x4 *>(rb + 8));
+      __builtin_amdgcn_raw_buffer_store_b128(oa[0], ru, u_off, 0, FZ_STORE_NT);
+      __builtin_amdgcn_raw_buffer_store_b128(oa[1], ru, u_off + 16, 0, FZ_STORE_NT);
+      __builtin_amdgcn_raw_buffer_store_b128(ob[0], ru, u_off + 2 * OW * 2, 0, FZ_STORE_NT);
+      __builtin_amdgcn_raw_buffer_store_b128(ob[1], ru, u_off + 2 * OW * 2 + 16, 0, FZ_STORE_NT);
     }
 
     // ---- attention mask at 1 / SC of the map: target (ty, tx) reads rows SC ty + SC/2 - 1, + 1 and the same two columns,
     // all four weights 1/2.  SC = 2: my own rows (window rows 1, 2 of parity 0); SC = 4, 8: the row above + my first row
-    // (window rows 0, 1), in the waves whose first row is SC/2 (mod SC).
-    if ((SC == 2 || (y0 & (SC - 1)) == SC / 2) && !par && wr) {
+    // (window rows 0, 1), in the waves whose first row is SC/2 (mod SC).  Every lane evaluates its bytes; the lanes of the
+    // other parity and of the other waves store them at FZ_DROP, past every descriptor's end.
+    {
       constexpr int RA = SC == 2 ? 1 : 0;
-      const int ty = SC == 2 ? y0 / 2 : (y0 - SC / 2) / SC;
       unsigned bytes = 0;
 #pragma unroll
       for (int j = 0; j < 8 / SC; ++j) {
@@ -197,10 +213,10 @@ __global__ __launch_bounds__(256, FZ_WGS) void dmh_fused_kernel(const float *__r
         const float v = (float)(__bf16)dm_blend(0.5f, 0.5f, 0.5f, 0.5f, e[RA][1 + xl], e[RA][2 + xl], e[RA + 1][1 + xl], e[RA + 1][2 + xl]);
         bytes |= (unsigned)(v < -0.00390625f || (edge_masked && v == -0.00390625f)) << (8 * j);
       }
-      unsigned char *mp = amask + ((size_t)n * Q + q_acc) * (size_t)((H / SC) * th_w) + (size_t)ty * th_w + (8 / SC) * col;
-      if constexpr (SC == 2) *reinterpret_cast<unsigned *>(mp) = bytes;
-      else if constexpr (SC == 4) *reinterpret_cast<unsigned short *>(mp) = (unsigned short)bytes;
-      else *mp = (unsigned char)bytes;
+      const auto rm = __builtin_amdgcn_make_buffer_rsrc(amask + plane0 * (size_t)m_plane_b, 0, nq * m_plane_b, 0x00020000);
+      if constexpr (SC == 2) __builtin_amdgcn_raw_buffer_store_b32(bytes, rm, m_off, 0, 0);
+      else if constexpr (SC == 4) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)bytes, rm, m_off, 0, 0);
+      else __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bytes, rm, m_off, 0, 0);
     }
   }
 }
@@ -218,6 +234,7 @@ int launch_dyn_mask_head_fused(const float *feat, const float *ref, const float 
   if ((long long)N * (H / FZ_BAND) > 0x7fffffffLL || (long long)N * npairs > 0x7fffffffLL) return PCT_NOT_COVERED;
   if (((uintptr_t)up & 15u) || ((uintptr_t)amask & 3u) || ((uintptr_t)workspace & 15u)) return PCT_NOT_COVERED;
   if (sc == 2 && (((size_t)(H / 2) * (W / 2)) & 3u)) return PCT_NOT_COVERED;          // 4-byte mask stores
+  if ((long long)H * W * 16 >= FZ_DROP) return PCT_NOT_COVERED;                        // two output planes inside one buffer descriptor
   unsigned *ws = static_cast<unsigned *>(workspace);
   if (rel_coord)
     hipLaunchKernelGGL(dmh_prepare_kernel<true>, dim3((unsigned)(N * npairs)), dim3(64), 0, stream, params, ref, Q, H, W, stride, ws);

@@ -172,16 +172,21 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
 #pragma unroll
     for (int q = 0; q < 4; ++q) g[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, g_voff, q * g_step, 0);
   };
-  // the x2 rows (the positional term, shared by the batch: L2 hits) are fetched one tile ahead only: one register set
-  auto fetch2 = [&](const long long tile, i32x4 (&g2)[4]) {
+  // the x2 rows (the positional term, shared by the batch: L2 hits) are fetched one tile ahead only: one register set.
+  // Successive calls fetch the slot's successive tiles (slot, slot + nslots, ...): the first row's index modulo the period is
+  // carried along (uniform; a 64-bit remainder per tile is ~130 instructions in front of the fetch)
+  int x2_base = HAS_X2 ? (int)(((long long)slot * 32) % x2_period) : 0;
+  const int x2_step = HAS_X2 ? (int)(((long long)nslots * 32) % x2_period) : 0;
+  auto fetch2 = [&](i32x4 (&g2)[4]) {
     if constexpr (HAS_X2) {
-      const int base = (int)((tile * 32) % x2_period);              // uniform
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        int row = base + (tid >> 5) + 8 * q;
+        int row = x2_base + (tid >> 5) + 8 * q;
         row = row >= x2_period ? row - x2_period : row;
         g2[q] = __builtin_amdgcn_raw_buffer_load_b128(rs2, (int)(row * ldx2 * 4) + 16 * (tid & 31), 0, 0);
       }
+      x2_base += x2_step;
+      x2_base = x2_base >= x2_period ? x2_base - x2_period : x2_base;
     }
   };
   auto stash_q = [&](unsigned char *dst, const int q, const i32x4 (&g)[4], const i32x4 (&g2)[4]) {
@@ -211,8 +216,11 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
   // Two tiles of x are in flight per workgroup (register sets ga / gb): under load a fetch takes longer than one
   // tile's MFMAs, and with a single tile of prefetch the iteration time is the memory latency (measured 3.2 us per
   // tile whatever n).  Issue order inside an iteration is what the in-order vmcnt makes cheap: [residual rows of this
-  // tile, x of tile+2] -> MFMAs -> split + stash of tile+1 (the oldest loads) -> epilogue (waits only for the residual,
-  // which is older than the far fetch) -> stores.
+  // tile, x of tile+2] -> MFMAs -> split + stash of tile+1 (the oldest loads) -> x2 of tile+2 -> epilogue (waits only for
+  // the residual, which is older than the far fetch) -> stores.  One counter holds loads and stores in issue order, so a
+  // wait for a load is a wait for every store issued before it: x2 goes out BEFORE the tile's stores (its registers are
+  // free after the last stash), and the next tile's wait for it leaves those stores and the far fetch in flight -- fetched
+  // at the top of the next tile, behind the stores, its first use one MFMA step later drained them.
   i32x4 ga[4], gb[4], g2[4] = {};
   auto body = [&](const long long tile, const int buf, i32x4 (&gn)[4], i32x4 (&gf)[4]) {
     const long long far = tile + 2 * (long long)nslots;
@@ -222,7 +230,6 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
 #pragma unroll
       for (int q = 0; q < 4; ++q) res[q] = __builtin_amdgcn_raw_buffer_load_b128(rr, r_voff, 32 * q, 0);
     }
-    fetch2(tile + nslots, g2);
     fetch(far, gf);                                               // past the end: empty descriptor, returns zeros
     __builtin_amdgcn_sched_barrier(0);                            // keep the fetches ahead of the MFMAs
 
@@ -264,8 +271,8 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
           // (an MFMA holds the SIMD's vector issue for 8 of its 16 cycles: one vector instruction per MFMA rides along) instead
           // of in a block of ~100 vector instructions behind the last MFMA with the matrix pipe idle (linear1 4.17 -> 3.95 ms,
           // same-box A/B)
-          // (with a second operand x2 -- fetched for the next tile at the top of THIS tile, from L2 -- the first quarters wait
-          // SPL_IL_DELAY steps for it and the last ones follow the loop)
+          // (with a second operand x2 -- fetched for the next tile behind the PREVIOUS tile's last stash, from L2 -- the first
+          // quarters still start SPL_IL_DELAY steps in and the last ones follow the loop)
           if (sk >= (HAS_X2 ? SPL_IL_DELAY : 0)) stash_q(abuf[buf ^ 1], sk - (HAS_X2 ? SPL_IL_DELAY : 0), gn, g2);
 #pragma unroll
           for (int cw = 0; cw < 2; ++cw) {
@@ -285,6 +292,8 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
       }
 #pragma unroll
       for (int q = 4 - (HAS_X2 ? SPL_IL_DELAY : 0); q < 4; ++q) stash_q(abuf[buf ^ 1], q, gn, g2);
+      fetch2(g2);                                                   // for the next tile's stash, ahead of this tile's stores
+      if constexpr (HAS_X2) __builtin_amdgcn_sched_barrier(0);
       {
         const auto ry = tile_rsrc(Y, ldy, active ? tile : ntiles);
         float *sw = oscr[wave];
@@ -333,6 +342,7 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
       }
     }
     stash(abuf[buf ^ 1], gn, g2);
+    fetch2(g2);
 
     {
       float v[16];
@@ -395,18 +405,42 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
 
   long long tile = slot;
   fetch(tile, ga);
-  fetch2(tile, g2);
+  fetch2(g2);
   stash(abuf[0], ga, g2);
   fetch(tile + nslots, ga);
+  fetch2(g2);
   // the per-column constants are complete before the loop (otherwise their pending loads cost a vmcnt(0) per tile)
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     asm volatile("" : "+v"(bvec[q]));
   }
-  __syncthreads();
-  for (; tile < ntiles; tile += 2 * (long long)nslots) {
-    body(tile, 0, ga, gb);
-    if (tile + nslots < ntiles) body(tile + nslots, 1, gb, ga);
+  if constexpr (HAS_X2) {
+    // and so are the fetches of the slot's second tile: entered with them pending and no store behind them, the loop's first
+    // body would take the smaller of the two counts for its waits -- the entry's -- and on the way round drain the stores
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      asm volatile("" : "+v"(ga[q]));
+      asm volatile("" : "+v"(g2[q]));
+    }
+    __syncthreads();
+    // Both bodies run in every trip, and the trips are counted in an int.  A slot with an odd number of tiles runs its last
+    // body on a tile past the end: empty descriptors, so it loads zeros and its stores are dropped.  With the second body
+    // under `if (tile + nslots < ntiles)` and the 64-bit loop test, the compiler put a vmcnt(4) at the join (the test's
+    // temporary was a register of the newest x fetch), which made every far fetch complete within its own tile.
+    const long long mine = slot < ntiles ? (ntiles - slot + nslots - 1) / nslots : 0;     // tiles of this slot
+    const int trips = (int)((mine + 1) / 2);
+    for (int it = 0; it < trips; ++it, tile += 2 * (long long)nslots) {
+      body(tile, 0, ga, gb);
+      body(tile + nslots, 1, gb, ga);
+    }
+  } else {
+    // (without x2 no wait sits behind fresh stores and the loop above measured no gain: 1.870 -> 1.848 ms at n = 1024,
+    // 0.404 -> 0.407 ms for the LayerNorm epilogue, inside three times the run-to-run spread of 0.012)
+    __syncthreads();
+    for (; tile < ntiles; tile += 2 * (long long)nslots) {
+      body(tile, 0, ga, gb);
+      if (tile + nslots < ntiles) body(tile + nslots, 1, gb, ga);
+    }
   }
 }
 
