@@ -60,7 +60,8 @@ PCT_API int pct_point_sample_f32(const float *planes, const int32_t *plane_index
  *   sums[k, 0..3] = sum_p bce(x, t),  sum_p sigma(x) t,  sum_p sigma(x),  sum_p t
  * with bce(x, t) = max(x, 0) - x t + log1p(exp(-|x|)), torch's binary_cross_entropy_with_logits.  One workgroup per pair:
  * each thread sums its points in ascending order, the threads are summed by a fixed tree.
- * Covered: what the backward covers for (height, width), and tgt_height * tgt_width < 2^31 - 1. */
+ * Covered: what the backward covers for (height, width), and tgt_height * tgt_width < 2^31 - 1.
+ * It is the one-head case of pct_point_mask_loss_forward_many_f32 (below): that entry's checks, that entry's launch. */
 PCT_API int pct_point_mask_loss_forward_f32(const float *pred, const int32_t *src_index, int num_pred_planes, int height,
                                             int width, const float *tgt, const int32_t *tgt_index, int num_tgt_planes,
                                             int tgt_height, int tgt_width, const float *coords, int num_pairs, int num_points,
@@ -105,7 +106,8 @@ PCT_API int pct_point_mask_loss_backward_f32(const float *x, const float *t, con
  * places the selected ones.  No sort, no workspace; everything is a function of the inputs alone.
  * Status, beyond the common rules: num_keep > num_cand or out_row_points < num_keep PCT_ERR_BAD_ARG; num_pairs == 0 or
  * num_keep == 0 PCT_OK with nothing launched.
- * Covered: num_cand <= 65536 (64 keys per thread) and height * width < 2^31 - 1. */
+ * Covered: num_cand <= 65536 (64 keys per thread) and height * width < 2^31 - 1.
+ * It is the one-head case of pct_point_select_uncertain_many_f32 (below): that entry's checks, that entry's launch. */
 PCT_API int pct_point_select_uncertain_f32(const float *pred, const int32_t *src_index, int num_pred_planes, int height,
                                            int width, const float *cand_coords, int num_pairs, int num_cand, int num_keep,
                                            float *out_coords, int out_row_points, int32_t *out_index, void *stream);
@@ -149,10 +151,11 @@ PCT_API int pct_point_match_cost_f32(const float *pred, int batch, int num_query
  * passed to the kernel by value: nothing is uploaded, allocated or synchronised, and the array may be reused at once.
  * Every per-head array is the single-head array with a leading [num_heads] dimension; the target planes, tgt_start and
  * tgt_count are shared by all heads.
- * Bit identity.  The workgroups run the code of their single-head siblings (the same device functions, on the head's pointer
- * and the head's slices): for every head the entry writes exactly the bits the single-head entry writes when called with
- * preds[h] and the slices [h] of the arrays -- the NaN rows of an index outside the planes and the zero columns past an image's
- * target count included.
+ * Bit identity.  A workgroup works on its head's pointer and its head's slices alone, and no sum's order depends on num_heads:
+ * for every head the entry writes exactly the bits the single-head entry -- for the selection and the loss forward the same
+ * kernels launched with one head, for the costs kernels of its own around the same device functions -- writes
+ * when called with preds[h] and the slices [h] of the arrays, the NaN rows of an index outside the planes and the zero columns
+ * past an image's target count included.
  * Status: num_heads < 0 or > PCT_POINT_MAX_HEADS, preds == NULL with num_heads > 0, or a NULL entry PCT_ERR_BAD_ARG; num_heads == 0
  * PCT_OK with nothing launched; otherwise the rules of the single-head entry, the alignment of every entry included.
  *

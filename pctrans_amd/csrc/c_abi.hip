@@ -479,18 +479,11 @@ int pct_point_mask_loss_forward_f32(const float *pred, const int32_t *src_index,
                                     int tgt_width, const float *coords, int num_pairs, int num_points, float *x, float *t,
                                     float *sums, void *stream)
 {
-  if (num_pred_planes < 0 || num_tgt_planes < 0 || height <= 0 || width <= 0 || tgt_height <= 0 || tgt_width <= 0 ||
-      num_pairs < 0 || num_points < 0)
-    return PCT_ERR_BAD_ARG;
-  if (num_pairs == 0 || num_points == 0) return PCT_OK;
-  if (!pred || !tgt || !coords || !x || !t || !sums || num_pred_planes == 0 || num_tgt_planes == 0) return PCT_ERR_BAD_ARG;
-  if ((!src_index && num_pairs > num_pred_planes) || (!tgt_index && num_pairs > num_tgt_planes)) return PCT_ERR_BAD_ARG;
-  if ((((uintptr_t)pred | (uintptr_t)src_index | (uintptr_t)tgt | (uintptr_t)tgt_index | (uintptr_t)x | (uintptr_t)t |
-        (uintptr_t)sums) & 3u) || ((uintptr_t)coords & 7u))
-    return PCT_ERR_ALIGNMENT;
-  return pct::launch_point_loss_forward(pred, src_index, num_pred_planes, height, width, tgt, tgt_index, num_tgt_planes,
-                                        tgt_height, tgt_width, coords, num_pairs, num_points, x, t, sums,
-                                        static_cast<hipStream_t>(stream));
+  // The one-head case of the _many entry (so is the selection below): its checks in its order, its launch.
+  // A NULL `pred` is the table's missing entry, PCT_ERR_BAD_ARG, and is seen before any alignment, pred's own included.
+  const float *const one[1] = {pred};
+  return pct_point_mask_loss_forward_many_f32(one, 1, src_index, num_pred_planes, height, width, tgt, tgt_index, num_tgt_planes,
+                                              tgt_height, tgt_width, coords, num_pairs, num_points, x, t, sums, stream);
 }
 
 int pct_point_mask_loss_backward_f32(const float *x, const float *t, const float *coords, const float *alpha, const float *beta,
@@ -511,17 +504,9 @@ int pct_point_select_uncertain_f32(const float *pred, const int32_t *src_index, 
                                    const float *cand_coords, int num_pairs, int num_cand, int num_keep, float *out_coords,
                                    int out_row_points, int32_t *out_index, void *stream)
 {
-  if (num_pred_planes < 0 || height <= 0 || width <= 0 || num_pairs < 0 || num_cand < 0 || num_keep < 0 || num_keep > num_cand ||
-      out_row_points < num_keep)
-    return PCT_ERR_BAD_ARG;
-  if (num_pairs == 0 || num_keep == 0) return PCT_OK;
-  if (!pred || !cand_coords || !out_coords || num_pred_planes == 0) return PCT_ERR_BAD_ARG;
-  if (!src_index && num_pairs > num_pred_planes) return PCT_ERR_BAD_ARG;
-  if ((((uintptr_t)pred | (uintptr_t)src_index | (uintptr_t)out_index) & 3u) ||
-      (((uintptr_t)cand_coords | (uintptr_t)out_coords) & 7u))
-    return PCT_ERR_ALIGNMENT;
-  return pct::launch_point_select(pred, src_index, num_pred_planes, height, width, cand_coords, num_pairs, num_cand, num_keep,
-                                  out_coords, out_row_points, out_index, static_cast<hipStream_t>(stream));
+  const float *const one[1] = {pred};
+  return pct_point_select_uncertain_many_f32(one, 1, src_index, num_pred_planes, height, width, cand_coords, num_pairs, num_cand,
+                                             num_keep, out_coords, out_row_points, out_index, stream);
 }
 
 int pct_point_match_cost_f32(const float *pred, int batch, int num_query, int height, int width, const float *tgt,

@@ -223,18 +223,14 @@ inline ChunkPlan chunk_plan(const long long pixels, const int per_pass, const in
 // PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover -----------------------------------------
 int launch_point_sample(const float *planes, const int *plane_index, const float *coords, int num_planes, int H, int W, int K,
                         int P, int per_row, float *out, hipStream_t stream);
-int launch_point_loss_forward(const float *pred, const int *src_index, int num_pred, int H, int W, const float *tgt,
-                              const int *tgt_index, int num_tgt, int Ht, int Wt, const float *coords, int K, int P, float *x,
-                              float *t, float *sums, hipStream_t stream);
 int launch_point_loss_backward(const float *x, const float *t, const float *coords, const float *alpha, const float *beta,
                                const float *gamma, int K, int P, int H, int W, float *grad_planes, hipStream_t stream);
-int launch_point_select(const float *pred, const int *src_index, int num_pred, int H, int W, const float *cand_coords, int K, int S,
-                        int num_keep, float *out_coords, int out_row_points, int *out_index, hipStream_t stream);
 int launch_point_match_cost(const float *pred, int B, int Q, int H, int W, const float *tgt, int num_tgt, int Ht, int Wt,
                             const int *tgt_start, const int *tgt_count, int Gmax, const float *coords, int P, float cost_mask,
                             float cost_dice, void *workspace, float *cost, hipStream_t stream);
-// the same for 0 < num_heads <= PCT_POINT_MAX_HEADS predictions in one launch: `preds` a host array of device pointers, copied
-// into a by-value kernel argument; every per-head array carries a leading [num_heads] dimension
+// the selection, the loss forward and the cost pass of 0 < num_heads <= PCT_POINT_MAX_HEADS predictions in one launch: `preds`
+// a host array of device pointers, copied into a by-value kernel argument; every per-head array carries a leading [num_heads]
+// dimension.  The single-head selection and loss forward call these with one head
 int launch_point_select_many(const float *const *preds, int num_heads, const int *src_index, int num_pred, int H, int W,
                              const float *cand_coords, int K, int S, int num_keep, float *out_coords, int out_row_points,
                              int *out_index, hipStream_t stream);

@@ -3,9 +3,10 @@
 // sums and the scatter of their gradient that loss/matcher.py and loss/maskformer_criterion.py otherwise run as grid_sample
 // forward / backward plus elementwise and reduce launches, the choice of the most uncertain of the oversampled candidates that
 // the criterion otherwise makes with a gather, topk, gather and cat, and the matcher's cost matrices that it otherwise forms
-// from two gathers with a chain of elementwise launches and three einsum.  The selection, the loss forward and the cost pass also
-// exist for several prediction heads in one launch (pct_point_select_uncertain_many_f32, pct_point_mask_loss_forward_many_f32,
-// pct_point_match_cost_many_f32): the same per-workgroup bodies, the head taken from a grid dimension (HeadPlanes below).
+// from two gathers with a chain of elementwise launches and three einsum.  The selection, the loss forward and the cost pass
+// serve up to PL_MAX_HEADS prediction heads in one launch (pct_point_select_uncertain_many_f32,
+// pct_point_mask_loss_forward_many_f32, pct_point_match_cost_many_f32), the head taken from a grid dimension (HeadPlanes below);
+// the single-head selection and loss forward are the same launch with one head.
 //
 // Sampling is F.grid_sample(input, 2c - 1, "bilinear", "zeros", align_corners=False): x = c_x * W - 0.5 (one fma),
 // y = c_y * H - 0.5, taps at floor and floor + 1, weights (1 - tx)(1 - ty) .. tx ty, a tap outside the plane adds nothing.
@@ -107,10 +108,14 @@ __global__ __launch_bounds__(PL_GATHER_BLOCK) void point_sample_kernel(const flo
   out[(size_t)k * P + p] = v;
 }
 
-// The prediction planes of the heads of a *_many launch: a by-value kernel argument (128 bytes of the kernarg segment, read
-// with a scalar load at a uniform index), so that nothing is uploaded.  A *_many kernel takes its head from a grid dimension,
-// moves every per-head array to that head's slice and runs the body of its single-head sibling: the same instructions on the
-// same values, so the same bits.
+// The prediction planes of the heads of a launch: a by-value kernel argument (128 bytes of the kernarg segment, read with a
+// scalar load at a uniform index), so that nothing is uploaded.  The *_many kernels take their head from a grid dimension, move
+// every per-head array to that head's slice and run their *_body on it: a head's bits do not depend on how many heads the
+// launch has.  A single-head selection or loss forward is a launch of one head (c_abi.hip); the cost pass alone keeps
+// single-head kernels beside its *_many pair, because one head of that pair measured slower than they are.
+// point_select_body and point_loss_forward_body now have one caller each and still stay device functions of their own, as
+// the cost pass's two do: written out inside their kernels, hipcc schedules every one of the four differently
+// (match_cost_partial_many_kernel then takes 228 VGPRs, not 165).
 constexpr int PL_MAX_HEADS = 16;           // include/pctrans_hip_train.h: PCT_POINT_MAX_HEADS
 static_assert(PL_MAX_HEADS == PCT_POINT_MAX_HEADS, "the header's limit");
 
@@ -161,14 +166,6 @@ __device__ __forceinline__ void point_loss_forward_body(
     for (int w = 0; w < PL_FWD_BLOCK / 64; ++w) a += part[w][threadIdx.x];
     sums[(size_t)k * 4 + threadIdx.x] = a;
   }
-}
-
-__global__ __launch_bounds__(PL_FWD_BLOCK) void point_loss_forward_kernel(
-    const float *__restrict__ pred, const int *__restrict__ src_index, const int num_pred, const int H, const int W,
-    const float *__restrict__ tgt, const int *__restrict__ tgt_index, const int num_tgt, const int Ht, const int Wt,
-    const float2 *__restrict__ coords, const int P, float *__restrict__ xs, float *__restrict__ ts, float *__restrict__ sums)
-{
-  point_loss_forward_body(pred, src_index, num_pred, H, W, tgt, tgt_index, num_tgt, Ht, Wt, coords, P, xs, ts, sums, blockIdx.x);
 }
 
 // grid (pair, head): the index vectors are [heads, K], coords [heads, K, P, 2], x, t [heads, K, P], sums [heads, K, 4]
@@ -405,16 +402,6 @@ __device__ __forceinline__ void point_select_body(const float *__restrict__ pred
   }
 }
 
-template <int IPT>
-__global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_kernel(const float *__restrict__ pred,
-                                                                       const int *__restrict__ src_index, const int num_pred,
-                                                                       const int H, const int W, const float2 *__restrict__ cand,
-                                                                       const int S, const int num_keep, float2 *__restrict__ out,
-                                                                       const int out_row_points, int *__restrict__ out_index)
-{
-  point_select_body<IPT>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index, blockIdx.x);
-}
-
 // grid (pair, head): src_index [heads, K], cand [heads, K, S], out [heads, K, out_row_points], out_index [heads, K, num_keep]
 template <int IPT>
 __global__ __launch_bounds__(PL_SELECT_BLOCK) void point_select_many_kernel(
@@ -576,6 +563,8 @@ __device__ __forceinline__ void match_cost_partial_body(
   if (ggrp == 0 && kh == 0) wsb[2 * Qp * Gp + (long long)qgrp * MC_QGROUP + wave * 32 + col] = s2;
 }
 
+// The cost pass keeps single-head kernels of its own: a launch of one head of the *_many pair below measured 1.1 - 1.3 % slower
+// than these (profiles/point_one_head.json).  The same bodies, so the same bits.
 __global__ __launch_bounds__(MC_BLOCK, 2) void match_cost_partial_kernel(
     const float *__restrict__ pred, const float *__restrict__ tgt, const int *__restrict__ tgt_start,
     const int *__restrict__ tgt_count, const float2 *__restrict__ coords, const int Q, const int H, const int W, const int num_tgt,
@@ -699,16 +688,6 @@ int launch_point_sample(const float *planes, const int *plane_index, const float
   return (int)hipGetLastError();
 }
 
-int launch_point_loss_forward(const float *pred, const int *src_index, int num_pred, int H, int W, const float *tgt,
-                              const int *tgt_index, int num_tgt, int Ht, int Wt, const float *coords, int K, int P, float *x,
-                              float *t, float *sums, hipStream_t stream)
-{
-  if (const int rc = point_loss_geometry_status(H, W, Ht, Wt, K); rc != PCT_OK) return rc;
-  point_loss_forward_kernel<<<dim3((unsigned)K), dim3(PL_FWD_BLOCK), 0, stream>>>(
-      pred, src_index, num_pred, H, W, tgt, tgt_index, num_tgt, Ht, Wt, reinterpret_cast<const float2 *>(coords), P, x, t, sums);
-  return (int)hipGetLastError();
-}
-
 int launch_point_loss_backward(const float *x, const float *t, const float *coords, const float *alpha, const float *beta,
                                const float *gamma, int K, int P, int H, int W, float *grad_planes, hipStream_t stream)
 {
@@ -720,23 +699,7 @@ int launch_point_loss_backward(const float *x, const float *t, const float *coor
   return (int)hipGetLastError();
 }
 
-int launch_point_select(const float *pred, const int *src_index, int num_pred, int H, int W, const float *cand_coords, int K, int S,
-                        int num_keep, float *out_coords, int out_row_points, int *out_index, hipStream_t stream)
-{
-  if ((long long)H * W >= 0x7fffffffLL || S > PL_SELECT_MAX_CAND) return PCT_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)K), block(PL_SELECT_BLOCK);
-  const float2 *cand = reinterpret_cast<const float2 *>(cand_coords);
-  float2 *out = reinterpret_cast<float2 *>(out_coords);
-  if (S <= 16 * PL_SELECT_BLOCK)
-    point_select_kernel<16><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
-  else if (S <= 40 * PL_SELECT_BLOCK)
-    point_select_kernel<40><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
-  else
-    point_select_kernel<64><<<grid, block, 0, stream>>>(pred, src_index, num_pred, H, W, cand, S, num_keep, out, out_row_points, out_index);
-  return (int)hipGetLastError();
-}
-
-// ---- the same for several prediction heads in one launch: the C ABI has checked 0 < num_heads <= PL_MAX_HEADS and the entries
+// ---- the launches with a head dimension: the C ABI has checked 0 < num_heads <= PL_MAX_HEADS and the entries
 static HeadPlanes head_planes(const float *const *preds, int num_heads)
 {
   HeadPlanes hp;
@@ -779,7 +742,7 @@ int launch_point_match_cost_many(const float *const *preds, int num_heads, int B
 {
   if (const int rc = match_cost_geometry_status(B, Q, H, W, Ht, Wt, Gmax, P); rc != PCT_OK) return rc;
   if ((long long)num_heads * B > 65535) return PCT_ERR_UNSUPPORTED;         // the grid's z holds (head, image)
-  const MatchCostPlan plan = match_cost_plan(B, Q, Gmax, P);                // of ONE head: the order of every sum is the single call's
+  const MatchCostPlan plan = match_cost_plan(B, Q, Gmax, P);                // of ONE head: no sum's order depends on num_heads
   float *ws = static_cast<float *>(workspace);
   match_cost_partial_many_kernel<<<dim3((unsigned)plan.chunks, (unsigned)(plan.qgroups * plan.ggroups), (unsigned)(num_heads * B)),
                                    dim3(MC_BLOCK), 0, stream>>>(head_planes(preds, num_heads), tgt, tgt_start, tgt_count,
