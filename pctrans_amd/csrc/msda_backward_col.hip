@@ -6,9 +6,11 @@
 // Why a second windowed backward: msda_backward_win.hip (round 1) works on 8 x 16 query tiles of ONE level.  A tile of a
 // coarse level looking at a fine level has a box the pool cannot hold -- those levels are retried slot by slot or fall to
 // direct global atomics -- and knock-out builds showed that neither the LDS adds (31 %) nor the flush (7 %) but this
-// skeleton is what the kernel spends its time in (2.6 of 3.8 ms at P2, batch 32).  Here the work item is the forward's
-// (msda_forward_col.hip): (image, pyramid COLUMN, head) -- the queries of all levels over one cell of a CX x CY grid, one
-// window per level serving the whole column -- and one lane = one (query, head) with all 16 channels:
+// skeleton is what the kernel spends its time in (2.6 of 3.8 ms at P2, batch 32).  Here the work item is the forward's:
+// (image, pyramid COLUMN, head) -- the queries of all levels over one cell of a CX x CY grid, one window per level serving
+// the whole column.  Grid, lane slots, cell tables, item decode, XCD chunking and the quad-cooperative record fetch
+// are the shared ones of msda_col_common.hpp (the queue is the windowed kernels' one-ahead protocol,
+// msda_win_common.hpp).  One lane = one (query, head) with all 16 channels:
 //   * pass 1 ("dots"): the value windows are staged by LDS-DMA with the forward's zero apron (the gate of cuh:290-296 is
 //     folded into the coordinates), every sample reads its four head-pixels (rotated 16-byte pieces, as the forward) and
 //     forms the four dot products <grad_out, v_corner> IN THE LANE -- no cross-lane butterflies -- from which
@@ -98,86 +100,24 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
   }
 
   // ---- level geometry (uniform) -------------------------------------------------------------------------------------
-  int Hs[L], Ws[L], St[L];
+  ColLevels<L> lv;
   col_f32x2 fWH[L];
 #pragma unroll
   for (int l = 0; l < L; ++l) {
-    Hs[l] = (int)shapes[2 * l];
-    Ws[l] = (int)shapes[2 * l + 1];
-    St[l] = (int)starts[l];
-    fWH[l] = uni_pair((float)Ws[l], (float)Hs[l]);
+    lv.H[l] = (int)shapes[2 * l];
+    lv.W[l] = (int)shapes[2 * l + 1];
+    lv.St[l] = (int)starts[l];
+    fWH[l] = uni_pair((float)lv.W[l], (float)lv.H[l]);
   }
 
-  // ---- column grid and this lane's slot: exactly the forward's (msda_forward_col.hip) ---------------------------------
-  int CX, CY;
-  {
-    int Hf = Hs[0], Wf = Ws[0];
-#pragma unroll
-    for (int l = 1; l < L; ++l)
-      if (Hs[l] * Ws[l] > Hf * Wf) { Hf = Hs[l]; Wf = Ws[l]; }
-    const float area = (float)BLOCK * (float)(Hf * Wf) / (float)S;
-    const int side = (int)sqrtf(area);
-    const int nxt = min(Wf, max(8, (side + 4) & ~7));
-    CX = (Wf + nxt - 1) / nxt;
-    const int nx0 = (Wf + CX - 1) / CX;
-    const int nyt = max(1, (int)(area / (float)nx0));
-    CY = min(Hf, (Hf + nyt - 1) / nyt);
-    for (int guard = 0; guard < 4096; ++guard) {
-      int maxq = 0;
-#pragma unroll
-      for (int l = 0; l < L; ++l) maxq += col_max_cell(Ws[l], CX) * col_max_cell(Hs[l], CY);
-      if (maxq <= BLOCK) break;
-      if (CY < Hf) ++CY;
-      else if (CX < Wf) ++CX;
-      else break;
-    }
-  }
-  int lane_c0 = 0;
-  unsigned lane_slot = 0x000FFFFFu;                                            // x | y << 10 | level << 20; x = y = 1023: no slot
-  {
-    int r = tid;
-    bool placed = false;
-#pragma unroll
-    for (int ll = 0; ll < L; ++ll) {
-      const int l = L - 1 - ll;
-      const int mxc = col_max_cell(Ws[l], CX), myc = col_max_cell(Hs[l], CY);
-      const int cnt = mxc * myc;
-      if (!placed && r < cnt) {
-        const int ly = r / max(mxc, 1), lx = r - ly * max(mxc, 1);
-        lane_slot = (unsigned)lx | ((unsigned)ly << 10) | ((unsigned)l << 20);
-        lane_c0 = St[l] + ly * Ws[l] + lx;
-        placed = true;
-      }
-      r -= placed ? 0 : cnt;
-    }
-  }
-  const bool use_tab = (L * (CX + CY) + L) * 4 <= BCOL_TAB_BYTES;
-  if (use_tab) {
-    for (int t = tid; t < L * CX; t += BLOCK) {
-      const int l = t / CX, c = t - l * CX;
-      const int a = col_lo(c, Ws[l], CX);
-      tab[t] = (unsigned)a | ((unsigned)(col_lo(c + 1, Ws[l], CX) - a) << 16);
-    }
-    for (int t = tid; t < L * CY; t += BLOCK) {
-      const int l = t / CY, c = t - l * CY;
-      const int a = col_lo(c, Hs[l], CY);
-      tab[L * CX + t] = (unsigned)a | ((unsigned)(col_lo(c + 1, Hs[l], CY) - a) << 16);
-    }
-    if (tid < L) tab[L * (CX + CY) + tid] = (unsigned)Ws[tid];
-    __syncthreads();
-  }
+  // ---- column grid, this lane's slot in a column, the cell tables and the launch's items (msda_col_common.hpp) --------
+  const ColGrid grid = col_grid<L, BLOCK>(lv, S);
+  ColSlot slot = col_lane_slot<L>(lv, grid, tid);
+  const bool use_tab = col_table_bytes<L>(grid) <= BCOL_TAB_BYTES;            // else: flat columns
+  if (use_tab) col_fill_tables<L, BLOCK>(tab, lv, grid, tid);
   constexpr int pool_use = BCOL_GPX;
-  bool big_map = false;                                                        // a level too large for the 16-bit box corners
-#pragma unroll
-  for (int l = 0; l < L; ++l) big_map = big_map || Ws[l] > 65531 || Hs[l] > 65531;
-  int ncol = CX * CY;
-  if (!use_tab) {
-    ncol = 0;
-#pragma unroll
-    for (int l = 0; l < L; ++l) ncol += (Hs[l] * Ws[l] + BLOCK - 1) / BLOCK;
-  }
-  const int items = N * ncol * M;
-  const UDiv dv_ncolM = make_udiv(ncol * M), dv_2ncol = make_udiv(2 * ncol), dv_CX = make_udiv(CX);
+  const ColItems ci = col_items<L, BLOCK>(lv, grid, use_tab, N, M);
+  const int items = ci.items;
 
   int qi = lane & 3;
   const bool qi0 = qi & 1, qi1 = qi & 2;
@@ -195,78 +135,22 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
 #pragma unroll
   for (int t = 0; t < 8; ++t) poff[t] = (unsigned)BCOL_CNT_BYTES + ((t + r8) & 7u) * (unsigned)BCOL_PLANE_BYTES;
 
-  const int xcd = blockIdx.x & 7, slot0 = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int chunk = (items + 7) / 8;
-  const int item_end = min((xcd + 1) * chunk, items);
-  const unsigned n_x = (unsigned)max(item_end - xcd * chunk, 0);
+  const ColChunk xc = col_chunk(items);                                        // the XCD-chunked walk (msda_col_common.hpp)
 
   constexpr int NPL = L * 2, NGL = (NPL + 3) / 4;                              // locations: 16-byte pieces, 64-byte groups
   constexpr int NGW = (L + 3) / 4;                                             // weights: one 16-byte piece per level
 
-  // item -> (image, head) [uniform] and this lane's query (qv = q, or ~q of the query an idle lane shadows); item order
-  // inside an image: head pair, column, head in the pair (the forward's)
-  auto decode = [&](const int it, int &b_, int &m_, int &qv_) {
-    b_ = udiv_s(it, dv_ncolM);
-    const int r_img = it - b_ * (ncol * M);
-    int col;
-    if (r_img < 2 * ncol * (M >> 1)) {
-      const int pr = udiv_s(r_img, dv_2ncol);
-      const int rr = r_img - pr * 2 * ncol;
-      col = rr >> 1;
-      m_ = 2 * pr + (rr & 1);
-    } else {
-      col = r_img - 2 * ncol * (M >> 1);
-      m_ = M - 1;
-    }
-    const int cy = udiv_s(col, dv_CX), cx = col - cy * CX;
-    int q;
-    bool valid;
-    if (use_tab) {
-      const unsigned lx = lane_slot & 0x3FFu, ly = (lane_slot >> 10) & 0x3FFu, lv = lane_slot >> 20;
-      const unsigned char *tb = reinterpret_cast<const unsigned char *>(tab);
-      const unsigned xt = *reinterpret_cast<const unsigned *>(tb + (__umul24(lv, (unsigned)(CX * 4)) + (unsigned)(cx * 4)));
-      const unsigned yt = *reinterpret_cast<const unsigned *>(tb + (__umul24(lv, (unsigned)(CY * 4)) + (unsigned)((L * CX + cy) * 4)));
-      const unsigned lw = *reinterpret_cast<const unsigned *>(tb + (lv * 4u + (unsigned)(L * (CX + CY) * 4)));
-      valid = lx < (xt >> 16) && ly < (yt >> 16);
-      q = lane_c0 + (int)__umul24(yt & 0xFFFFu, lw) + (int)(xt & 0xFFFFu);
-    } else {
-      int c = col;
-      q = 0;
-      valid = false;
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        const int cnt = Hs[l] * Ws[l], nch = (cnt + BLOCK - 1) / BLOCK;
-        if (c >= 0 && c < nch) {
-          q = St[l] + c * BLOCK + tid;
-          valid = c * BLOCK + tid < cnt;
-        }
-        c = c >= nch ? c - nch : -1;
-      }
-    }
-    const unsigned long long vm = __ballot(valid);
-    const int q_sh = vm ? __builtin_amdgcn_readlane(q, (int)__builtin_ctzll(vm)) : 0;
-    qv_ = valid ? q : ~q_sh;
-  };
-  auto rec_index = [&](const int qv_, const int m_) {
-    return __umul24((unsigned)(qv_ ^ (qv_ >> 31)), (unsigned)M) + (unsigned)m_;
-  };
-  auto quad_offsets = [&](const unsigned own_bytes, unsigned (&off)[4]) {
-    off[0] = dpp_u<0x00>(own_bytes) + ((unsigned)((0 - qi) & 3) << 4);
-    off[1] = dpp_u<0x55>(own_bytes) + ((unsigned)((1 - qi) & 3) << 4);
-    off[2] = dpp_u<0xAA>(own_bytes) + ((unsigned)((2 - qi) & 3) << 4);
-    off[3] = dpp_u<0xFF>(own_bytes) + ((unsigned)((3 - qi) & 3) << 4);
+  auto decode = [&](const int it, int &b_, int &m_, int &qv_) {               // col_decode for this launch and lane
+    const ColItem i = col_decode<L, BLOCK>(it, ci, grid, lv, tab, slot, tid);
+    b_ = i.b;
+    m_ = i.m;
+    qv_ = i.qv;
   };
   constexpr int RSRC_FLAGS = 0x00020000;
   auto issue_loc = [&](const int b_, const int m_, const int qv_, col_f32x4 (&raw)[NGL][4]) {
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(loc + (long long)b_ * S * M * (L * P * 2)), 0,
                                                       (int)((unsigned)S * (unsigned)M * (unsigned)(L * P * 8)), RSRC_FLAGS);
-    unsigned off[4];
-    quad_offsets(rec_index(qv_, m_) * (unsigned)(L * P * 8), off);
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-      for (int g = 0; g < NGL; ++g)
-        raw[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[s4] + g * 64), 0, 0));
+    col_quad_load<NGL>(rs, col_rec_index(qv_, m_, M) * (unsigned)(L * P * 8), qi, raw);
   };
 
   // ---- pieces shared by the main kernel and the DIRECT one ------------------------------------------------------------------
@@ -294,15 +178,14 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
                                                        (int)((unsigned)S * (unsigned)M * (unsigned)(L * P * 4)), RSRC_FLAGS);
     const auto rsg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(grad_out + (long long)b_ * S * MD), 0,
                                                        (int)((unsigned)S * (unsigned)MD * 4u), RSRC_FLAGS);
-    unsigned off[4], ofg[4];
-    quad_offsets(own_ * (unsigned)(L * P * 4), off);
-    quad_offsets(own_ * (unsigned)(D * 4), ofg);
+    const ColQuadOff off = col_quad_offsets(own_ * (unsigned)(L * P * 4), qi);
+    const ColQuadOff ofg = col_quad_offsets(own_ * (unsigned)(D * 4), qi);
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) {
 #pragma unroll
       for (int g = 0; g < NGW; ++g)
-        wraw_[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(off[s4] + g * 64), 0, 0));
-      graw_[s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsg, (int)ofg[s4], 0, 0));
+        wraw_[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, (int)(off.o[s4] + g * 64), 0, 0));
+      graw_[s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsg, (int)ofg.o[s4], 0, 0));
     }
   };
   // ... transposed; grad_output rotated like the head-pixel pieces (register j: piece (j + rho) % 4); an idle lane's are zero
@@ -366,7 +249,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
       if (mask == 0u) continue;
       int b, m, qv;
       decode(it, b, m, qv);
-      const unsigned own = rec_index(qv, m);
+      const unsigned own = col_rec_index(qv, m, M);
       const bool idle = qv < 0;
       col_f32x4 raw[NGL][4], wraw[NGW][4], gq[4];                              // gq[s]: piece (s - qi) % 4 of member s's grad_output
       issue_loc(b, m, qv, raw);
@@ -386,7 +269,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
         ([&] {
           constexpr int l = Ls;
           if (!((mask >> l) & 1u)) return;
-          const int H = Hs[l], W = Ws[l];
+          const int H = lv.H[l], W = lv.W[l];
           float ga[P];
           col_f32x2 gl[P];
           [&]<int... Ks>(std::integer_sequence<int, Ks...>) {
@@ -400,7 +283,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
               const bool lft = (unsigned)x0 < (unsigned)W, rgt = (unsigned)(x0 + 1) < (unsigned)W;
               // valid corners as bits; none for an idle lane or a gated-out sample (the reference skips it: exact zeros)
               const unsigned o_ok = idle ? 0u : ((top && lft ? 1u : 0u) | (top && rgt ? 2u : 0u) | (bot && lft ? 4u : 0u) | (bot && rgt ? 8u : 0u));
-              const int o_e0 = (St[l] + y0 * W + x0) * MD;                          // (launcher: S * M * D < 2^31)
+              const int o_e0 = (lv.St[l] + y0 * W + x0) * MD;                          // (launcher: S * M * D < 2^31)
               const float o_aw = wts[l][k];
               float pa[4], pw[4], ph[4];                                           // [member]: my 4 channels' share of its sums
               [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
@@ -471,8 +354,8 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
     return;
   }
 
-  int item = xcd * chunk + slot0;
-  bool have = item < item_end;
+  int item = xc.xcd * xc.chunk + xc.slot0;
+  bool have = item < xc.item_end;
   int b = 0, m = 0, qv = 0;
   col_f32x4 raw[NGL][4];
   if (have) {
@@ -481,10 +364,10 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
   }
 
   while (have) {
-    asm volatile("" : "+v"(tid), "+v"(qi), "+v"(lane_slot), "+v"(lane_c0));
+    asm volatile("" : "+v"(tid), "+v"(qi), "+v"(slot.slot), "+v"(slot.c0));
     unsigned rfetch = 0u;
-    if (queue && tid == 0) rfetch = atomicAdd(queue + xcd * WIN_QUEUE_STRIDE, 1u);
-    const unsigned own = rec_index(qv, m);                                    // this lane's record: query * M + head
+    if (queue && tid == 0) rfetch = atomicAdd(queue + xc.xcd * WIN_QUEUE_STRIDE, 1u);
+    const unsigned own = col_rec_index(qv, m, M);                             // this lane's record: query * M + head
     const bool idle = qv < 0;
 
     col_f32x2 lxy[L][P];
@@ -506,20 +389,17 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
     col_f32x4 wraw[NGW][4], graw[4];
     load_wg(b, own, wraw, graw);
     if (tid == 0) {
-      unsigned fetched = (unsigned)(item - xcd * chunk + nslots);             // static stride when there is no queue
+      unsigned fetched = (unsigned)(item - xc.xcd * xc.chunk + xc.nslots);             // static stride when there is no queue
       if (queue) {
-        if (rfetch + 1u >= n_x) atomicExch(queue + xcd * WIN_QUEUE_STRIDE, 0u);                   // that was the launch's last fetch
-        fetched = (unsigned)nslots + rfetch;
+        if (rfetch + 1u >= xc.n_x) atomicExch(queue + xc.xcd * WIN_QUEUE_STRIDE, 0u);                   // that was the launch's last fetch
+        fetched = (unsigned)xc.nslots + rfetch;
       }
       next_idx[0] = fetched;
     }
     __syncthreads();                                                          // (A) boxes visible; pool free (previous flush read)
-    int item_n, b_n = 0, m_n = 0, qv_n = 0;
-    {
-      const unsigned nxt = __builtin_amdgcn_readfirstlane(next_idx[0]);
-      item_n = nxt < n_x ? xcd * chunk + (int)nxt : item_end;
-    }
-    const bool have_n = item_n < item_end;
+    const int item_n = col_next_item(next_idx, xc);
+    int b_n = 0, m_n = 0, qv_n = 0;
+    const bool have_n = item_n < xc.item_end;
 
     // ---- windows and phases (uniform; the forward's planning) ---------------------------------------------------------------
     int wx0[L], wy0[L], wwid[L], whgt[L], wsize[L], wbase[L], phase_of[L], woff[L];
@@ -541,7 +421,7 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
 #pragma unroll
       for (int ll = 0; ll < L; ++ll) {
         const int l = col_level_of_step<L>(ll);
-        if (wsize[l] > pool_use || big_map) {
+        if (wsize[l] > pool_use || ci.big_map) {
           phase_of[l] = -1;
           wbase[l] = 0;
           continue;
@@ -574,16 +454,16 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
 #pragma unroll
       for (int l = 0; l < L; ++l) {
         if (phase_of[l] == phx && wsize[l] > 0) {
-          const unsigned lvl_off = (unsigned)St[l] * MDb + (unsigned)(m * D) * 4u;
-          const unsigned row_bytes = (unsigned)Ws[l] * MDb;
+          const unsigned lvl_off = (unsigned)lv.St[l] * MDb + (unsigned)(m * D) * 4u;
+          const unsigned row_bytes = (unsigned)lv.W[l] * MDb;
           unsigned char *dst = pool + (size_t)wbase[l] * PXB;
           for (int c0 = 0; c0 < wwid[l]; c0 += CPX) {
             const int xw = c0 + dx, x = wx0[l] + xw;
-            const unsigned voff = (unsigned)x < (unsigned)Ws[l] ? (unsigned)x * MDb + (unsigned)(cc * 16) : OOB;
+            const unsigned voff = (unsigned)x < (unsigned)lv.W[l] ? (unsigned)x * MDb + (unsigned)(cc * 16) : OOB;
             if (xw < wwid[l]) {
               for (int r = wv; r < whgt[l]; r += NW) {
                 const int y = wy0[l] + r;
-                const bool in_y = (unsigned)y < (unsigned)Hs[l];
+                const bool in_y = (unsigned)y < (unsigned)lv.H[l];
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rsrc, (__attribute__((address_space(3))) void *)(dst + (size_t)(r * wwid[l] + c0) * PXB), 16,
                     (int)(in_y ? voff : OOB), (int)(in_y ? lvl_off + (unsigned)y * row_bytes : 0u), 0, 0);
@@ -760,10 +640,10 @@ __global__ __launch_bounds__(BCOL_BLOCK, 2) void msda_backward_col_kernel(
       // its low / high field).  Rows and columns outside the map (the apron) and untouched texels (n = 0) are skipped.
       // Four column blocks at a time with all their LDS reads (counts and accumulators, unconditionally) in flight together:
       // one block per round trip -- count, branch, accumulator, decode, atomic -- took 800 cycles per block, a third of an item.
-      const int H = Hs[l], W = Ws[l];
+      const int H = lv.H[l], W = lv.W[l];
       const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
       const int ch = lane & 15, dxl = lane >> 4;
-      float *glev = gimg + (long long)St[l] * MD + ch;
+      float *glev = gimg + (long long)lv.St[l] * MD + ch;
       const unsigned plane_b = (unsigned)BCOL_CNT_BYTES + (unsigned)(ch >> 1) * (unsigned)BCOL_PLANE_BYTES;
       constexpr int UF = 4;
       for (int r = wv; r < whgt[l]; r += NW) {

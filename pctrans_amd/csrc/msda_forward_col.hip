@@ -23,8 +23,11 @@
 //     with a zero apron; levels that do not fit the pool together are staged and gathered in successive PHASES
 //     (accumulators stay in registers), a level whose box alone exceeds the pool is gathered from global memory
 //     through a bounds-checked buffer descriptor;
-//   * persistent grid, items handed out per XCD from self-resetting counters with the 8 heads of a column adjacent
-//     (the heads share every 128-byte line of the column's windows, two heads per line).
+//   * persistent grid, items handed out per XCD from self-resetting counters, two items ahead, the two heads that share
+//     every 128-byte line of a column's windows adjacent.
+// The launch-level structure -- column grid, a lane's slot, the cell tables, item order and decode, the queue, the
+// quad-cooperative record fetch -- is shared with msda_forward_col16.hip and msda_backward_col.hip and lives, with its
+// reasoning, in msda_col_common.hpp; this file keeps the windows and their phases, the staging and the gather.
 #include <math.h>
 
 #include <utility>
@@ -65,110 +68,30 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
   const int MD = M * D;
 
   // ---- level geometry (uniform) -------------------------------------------------------------------------------------
-  int Hs[L], Ws[L], St[L];
+  ColLevels<L> lv;
   col_f32x2 fWH[L], invWH[L];
 #pragma unroll
   for (int l = 0; l < L; ++l) {
-    Hs[l] = (int)shapes[2 * l];
-    Ws[l] = (int)shapes[2 * l + 1];
-    St[l] = (int)starts[l];
-    fWH[l] = uni_pair((float)Ws[l], (float)Hs[l]);
-    invWH[l] = uni_pair(1.0f / (float)Ws[l], 1.0f / (float)Hs[l]);           // FUSED: offset / (W, H) as offset * (1 / W, 1 / H)
+    lv.H[l] = (int)shapes[2 * l];
+    lv.W[l] = (int)shapes[2 * l + 1];
+    lv.St[l] = (int)starts[l];
+    fWH[l] = uni_pair((float)lv.W[l], (float)lv.H[l]);
+    invWH[l] = uni_pair(1.0f / (float)lv.W[l], 1.0f / (float)lv.H[l]);           // FUSED: offset / (W, H) as offset * (1 / W, 1 / H)
   }
 
-  // ---- column grid (uniform; every workgroup derives the same one): CX x CY cells such that no column holds more than
-  // BLOCK queries, cells about square on the finest level with a width near a multiple of 8 lanes ----------------------
-  int CX, CY;
-  {
-    int Hf = Hs[0], Wf = Ws[0];
-#pragma unroll
-    for (int l = 1; l < L; ++l)
-      if (Hs[l] * Ws[l] > Hf * Wf) { Hf = Hs[l]; Wf = Ws[l]; }
-    const float area = (float)BLOCK * (float)(Hf * Wf) / (float)S;           // finest-level pixels per full column
-    const int side = (int)sqrtf(area);
-    const int nxt = min(Wf, max(8, (side + 4) & ~7));
-    CX = (Wf + nxt - 1) / nxt;
-    const int nx0 = (Wf + CX - 1) / CX;
-    const int nyt = max(1, (int)(area / (float)nx0));
-    CY = min(Hf, (Hf + nyt - 1) / nyt);
-    for (int guard = 0; guard < 4096; ++guard) {
-      int maxq = 0;
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        int mx = 0, my = 0;
-        mx = col_max_cell(Ws[l], CX);
-        my = col_max_cell(Hs[l], CY);
-        maxq += mx * my;
-      }
-      if (maxq <= BLOCK) break;
-      if (CY < Hf) ++CY;
-      else if (CX < Wf) ++CX;
-      else break;                                                              // (L pixels per column: cannot exceed BLOCK)
-    }
-  }
-
-  // ---- this lane's SLOT in a column (fixed for the whole launch).  A column's queries are dealt to the lanes level by
-  // level, finest (last) first, each level taking a block of mx * my lanes where mx x my is its LARGEST cell over the
-  // grid -- the grid search above made these blocks fit the workgroup -- so a lane's (level, x, y inside the cell) never
-  // changes from item to item and the per-item decode is two table look-ups and a multiply-add (it used to walk the
-  // levels: ~100 vector and ~250 scalar instructions per item).  A lane whose slot lies outside a smaller border cell
-  // idles for that item.
-  int lane_c0 = 0;                                                             // level start + (y * W + x) inside the cell
-  unsigned lane_slot = 0x000FFFFFu;                                            // x | y << 10 | level << 20; x = y = 1023: no slot
-  {
-    int r = tid;
-    bool placed = false;
-#pragma unroll
-    for (int ll = 0; ll < L; ++ll) {
-      const int l = L - 1 - ll;
-      int mx = 0, my = 0;
-      mx = col_max_cell(Ws[l], CX);
-      my = col_max_cell(Hs[l], CY);
-      const int cnt = mx * my;                                                 // (<= BLOCK <= 1024: x, y fit 10 bits)
-      if (!placed && r < cnt) {
-        const int ly = r / max(mx, 1), lx = r - ly * max(mx, 1);
-        lane_slot = (unsigned)lx | ((unsigned)ly << 10) | ((unsigned)l << 20);
-        lane_c0 = St[l] + ly * Ws[l] + lx;
-        placed = true;
-      }
-      r -= placed ? 0 : cnt;
-    }
-  }
-  // cell tables in LDS, carved off the end of the pool: xtab[l][cx] = first x | width << 16, ytab[l][cy] likewise, then
-  // the level widths.  A grid whose tables would take more than half the pool (absurdly elongated maps: thousands of
-  // columns along one axis) is not used at all: the launch then runs on FLAT columns, see the decode.
-  const int tab_px = ((L * (CX + CY) + L) * 4 + PXB - 1) / PXB;
+  // ---- column grid, this lane's slot in a column, the cell tables and the launch's items (msda_col_common.hpp) --------
+  const ColGrid grid = col_grid<L, BLOCK>(lv, S);
+  ColSlot slot = col_lane_slot<L>(lv, grid, tid);
+  // the tables are carved off the end of the pool; a grid whose tables would take more than half of it is not used (flat columns)
+  const int tab_px = (col_table_bytes<L>(grid) + PXB - 1) / PXB;
   const int pool_eff = pool_px - tab_px;
   unsigned *tab = reinterpret_cast<unsigned *>(pool + (size_t)max(pool_eff, 0) * PXB);
   const bool use_tab = pool_eff * 2 >= pool_px;
-  if (use_tab) {
-    for (int t = tid; t < L * CX; t += BLOCK) {
-      const int l = t / CX, c = t - l * CX;
-      const int a = col_lo(c, Ws[l], CX);
-      tab[t] = (unsigned)a | ((unsigned)(col_lo(c + 1, Ws[l], CX) - a) << 16);
-    }
-    for (int t = tid; t < L * CY; t += BLOCK) {
-      const int l = t / CY, c = t - l * CY;
-      const int a = col_lo(c, Hs[l], CY);
-      tab[L * CX + t] = (unsigned)a | ((unsigned)(col_lo(c + 1, Hs[l], CY) - a) << 16);
-    }
-    if (tid < L) tab[L * (CX + CY) + tid] = (unsigned)Ws[tid];
-    __syncthreads();
-  }
+  if (use_tab) col_fill_tables<L, BLOCK>(tab, lv, grid, tid);
   const int pool_use = use_tab ? pool_eff : pool_px;                           // pixels the windows may take
-  bool big_map = false;                                                        // a level too large for the 16-bit box corners
-#pragma unroll
-  for (int l = 0; l < L; ++l) big_map = big_map || Ws[l] > 65531 || Hs[l] > 65531;
-  int ncol = CX * CY;
-  if (!use_tab) {
-    ncol = 0;
-#pragma unroll
-    for (int l = 0; l < L; ++l) ncol += (Hs[l] * Ws[l] + BLOCK - 1) / BLOCK;
-  }
-  const int items = N * ncol * M;
-  const UDiv dv_ncolM = make_udiv(ncol * M), dv_2ncol = make_udiv(2 * ncol), dv_CX = make_udiv(CX);
+  const ColItems ci = col_items<L, BLOCK>(lv, grid, use_tab, N, M);
 
-  // this lane's place in its quad (quad-cooperative record access, above)
+  // this lane's place in its quad (quad-cooperative record access, msda_col_common.hpp)
   int qi = lane & 3;
   const bool qi0 = qi & 1, qi1 = qi & 2;
   const bool qn1 = ((4 - qi) & 3) & 2;                                         // bit 1 of (-qi) % 4 (bit 0 is qi0)
@@ -179,92 +102,24 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
 #pragma unroll
   for (int j = 0; j < 4; ++j) rot[j] = ((j + rho) & 3u) << 4;
 
-  // ---- persistent, XCD-chunked walk over the items, software-pipelined across items --------------------------------
-  // Queue protocol as in msda_win_common.hpp (first item static, every further one nslots + the XCD's counter, the fetch
-  // that returns n_x - 1 resets the counter), run TWO items ahead: the index of item i + 1 is published before barrier
-  // (A) of item i, so right behind that barrier every lane knows its next query and ISSUES THE NEXT ITEM'S SAMPLING-
-  // LOCATION LOADS; they stay in flight through staging and gather of item i (32 registers) and item i + 1 starts on
-  // data that has already landed.  (Measured before this change: a workgroup spent a third of an item waiting for these
-  // loads.)  A fetch is made only while the next item is valid, so fetches == items processed still holds.
-  const int xcd = blockIdx.x & 7, slot0 = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int chunk = (items + 7) / 8;
-  const int item_end = min((xcd + 1) * chunk, items);
-  const unsigned n_x = (unsigned)max(item_end - xcd * chunk, 0);               // items of this XCD
+  // ---- persistent, XCD-chunked walk over the items, software-pipelined across items.  The queue runs TWO items ahead
+  // (msda_col_common.hpp): right behind barrier (A) of item i every lane knows its next query and ISSUES THE NEXT ITEM'S
+  // SAMPLING-LOCATION LOADS; they stay in flight through staging and gather of item i (32 registers) and item i + 1 starts
+  // on data that has already landed.  (Measured before this change: a workgroup spent a third of an item waiting for them.)
+  const ColChunk ch = col_chunk(ci.items);
 
   constexpr int NPL = L * 2, NGL = (NPL + 3) / 4;                              // locations: 16-byte pieces, 64-byte groups
   constexpr int NGW = (L + 3) / 4;                                             // weights: one 16-byte piece per level
 
-  // item -> (image, head) [uniform] and this lane's query (qv = q, or ~q of the query an idle lane shadows)
-  auto decode = [&](const int it, int &b_, int &m_, int &qv_) {
-    // Item order inside an image: head PAIR outermost, then column, then the head inside the pair.  The two heads of a
-    // pair share every 128-byte line of the value tensor (64 B each) and run in adjacent workgroups; the columns of one
-    // pair follow each other, so an XCD works through one head pair's value maps (2.8 MB of lines at the north-star
-    // shape, inside its 4 MB L2) with all the neighbouring columns -- whose windows overlap -- in flight together.
-    // (With the 8 heads of a column adjacent instead, an XCD held 12 columns x 8 heads of windows at once, more than its
-    // L2: measured 1.41x / 1.92x the algorithmic bytes on the memory side for distributions I / M.)
-    b_ = udiv_s(it, dv_ncolM);
-    const int r_img = it - b_ * (ncol * M);
-    int col;
-    if (r_img < 2 * ncol * (M >> 1)) {
-      const int pr = udiv_s(r_img, dv_2ncol);
-      const int rr = r_img - pr * 2 * ncol;
-      col = rr >> 1;
-      m_ = 2 * pr + (rr & 1);
-    } else {                                                                   // odd head count: the last head alone
-      col = r_img - 2 * ncol * (M >> 1);
-      m_ = M - 1;
-    }
-    const int cy = udiv_s(col, dv_CX), cx = col - cy * CX;
-    int q;
-    bool valid;
-    if (use_tab) {
-      const unsigned lx = lane_slot & 0x3FFu, ly = (lane_slot >> 10) & 0x3FFu, lv = lane_slot >> 20;
-      const unsigned char *tb = reinterpret_cast<const unsigned char *>(tab);
-      const unsigned xt = *reinterpret_cast<const unsigned *>(tb + (__umul24(lv, (unsigned)(CX * 4)) + (unsigned)(cx * 4)));
-      const unsigned yt = *reinterpret_cast<const unsigned *>(tb + (__umul24(lv, (unsigned)(CY * 4)) + (unsigned)((L * CX + cy) * 4)));
-      const unsigned lw = *reinterpret_cast<const unsigned *>(tb + (lv * 4u + (unsigned)(L * (CX + CY) * 4)));
-      valid = lx < (xt >> 16) && ly < (yt >> 16);
-      q = lane_c0 + (int)__umul24(yt & 0xFFFFu, lw) + (int)(xt & 0xFFFFu);
-    } else {
-      // flat columns: BLOCK consecutive queries of one level (no tables, no divisions; the boxes of such a strip are wide,
-      // so its levels mostly take the global-memory path -- correct, not fast)
-      int c = col;
-      q = 0;
-      valid = false;
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        const int cnt = Hs[l] * Ws[l], nch = (cnt + BLOCK - 1) / BLOCK;
-        if (c >= 0 && c < nch) {
-          q = St[l] + c * BLOCK + tid;
-          valid = c * BLOCK + tid < cnt;
-        }
-        c = c >= nch ? c - nch : -1;
-      }
-    }
-    // idle lanes shadow a query of the column (they cannot move its boxes): the wave's first busy lane's; a wave without
-    // any busy lane shadows query 0 (correct, merely wide boxes; it takes a pyramid whose levels shrink the wrong way)
-    const unsigned long long vm = __ballot(valid);
-    const int q_sh = vm ? __builtin_amdgcn_readlane(q, (int)__builtin_ctzll(vm)) : 0;
-    qv_ = valid ? q : ~q_sh;
+  auto decode = [&](const int it, int &b_, int &m_, int &qv_) {               // col_decode for this launch and lane
+    const ColItem i = col_decode<L, BLOCK>(it, ci, grid, lv, tab, slot, tid);
+    b_ = i.b;
+    m_ = i.m;
+    qv_ = i.qv;
   };
-  // ---- quad-cooperative record access (see the top of the file) through per-image buffer descriptors: a scalar base, one
-  // 32-bit vector offset per record and the piece as an immediate -- no 64-bit vector address arithmetic.  A lane forms
-  // the byte offset of ITS OWN record once; the quad's other three get it by DPP (record s of the quad belongs to lane
-  // 4 * (lane / 4) + s).  Offsets past the end of a descriptor read zeros / drop the store: an idle lane's record is
-  // simply moved out of range for the store.  (launcher: S < 2^24, per-image tensors below 2 GiB)
   typedef unsigned col_u32x4 __attribute__((ext_vector_type(4)));
-  auto rec_index = [&](const int qv_, const int m_) {                         // query * M + head of the lane's own record
-    return __umul24((unsigned)(qv_ ^ (qv_ >> 31)), (unsigned)M) + (unsigned)m_;
-  };
-  auto quad_offsets = [&](const unsigned own_bytes, unsigned (&off)[4]) {     // + the piece this lane fetches of record s
-    off[0] = dpp_u<0x00>(own_bytes) + ((unsigned)((0 - qi) & 3) << 4);
-    off[1] = dpp_u<0x55>(own_bytes) + ((unsigned)((1 - qi) & 3) << 4);
-    off[2] = dpp_u<0xAA>(own_bytes) + ((unsigned)((2 - qi) & 3) << 4);
-    off[3] = dpp_u<0xFF>(own_bytes) + ((unsigned)((3 - qi) & 3) << 4);
-  };
   constexpr int RSRC_FLAGS = 0x00020000;
-  // the location records of the quad's four queries, all groups (64 bytes each) at once: the two halves of a 128-byte line
-  // are requested back to back
+  // the location records of the quad's four queries (quad-cooperative, msda_col_common.hpp)
   auto issue_loc = [&](const int b_, const int m_, const int qv_, col_f32x4 (&raw)[NGL][4]) {
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(loc + (long long)b_ * S * M * (L * P * 2)), 0,
                                                       (int)((unsigned)S * (unsigned)M * (unsigned)(L * P * 8)), RSRC_FLAGS);
@@ -282,13 +137,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
                            : col_f32x4{0.f, 0.f, 0.f, 0.f};
       return;
     }
-    unsigned off[4];
-    quad_offsets(rec_index(qv_, m_) * (unsigned)(L * P * 8), off);
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-      for (int g = 0; g < NGL; ++g)                // (a partial last group reads into the next record: never looked at)
-        raw[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[s4] + g * 64), 0, 0));
+    col_quad_load<NGL>(rs, col_rec_index(qv_, m_, M) * (unsigned)(L * P * 8), qi, raw);
   };
   // FUSED: the query's reference points (one (x, y) per level), fetched with the record
   auto issue_ref = [&](const int b_, const int qv_, col_f32x2 (&rr)[L]) {
@@ -311,23 +160,21 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
     }
   };
 
-  int item = xcd * chunk + slot0;
-  bool have = item < item_end;
+  int item = ch.xcd * ch.chunk + ch.slot0;
+  bool have = item < ch.item_end;
   int b = 0, m = 0, qv = 0;
   col_f32x4 raw[NGL][4];
-  // (thread 0) the counter value fetched last lives in LDS word next_idx[1], not in a register: a register alive across
-  // the whole item was spilled by the compiler, and spilling an atomic's result means waiting for it on the spot
   if (have) {
     decode(item, b, m, qv);
     issue_loc(b, m, qv, raw);
-    if (queue && tid == 0) next_idx[1] = atomicAdd(queue + xcd * WIN_QUEUE_STRIDE, 1u);
+    col_queue_first_fetch(queue, next_idx, ch, tid);
   }
 
   while (have) {
     // (opaque per iteration: the compiler otherwise hoists every per-lane expression of tid / qi out of the item loop --
     // a dozen 64-bit piece offsets, float copies of tid, ... -- and spills them)
-    asm volatile("" : "+v"(tid), "+v"(qi), "+v"(lane_slot), "+v"(lane_c0));
-    const unsigned own = rec_index(qv, m);                                    // this lane's record: query * M + head
+    asm volatile("" : "+v"(tid), "+v"(qi), "+v"(slot.slot), "+v"(slot.c0));
+    const unsigned own = col_rec_index(qv, m, M);                             // this lane's record: query * M + head
 
     // FUSED: the reference points sit in L2 (shared by the heads and the batch): fetched here, not a whole item ahead
     // (eight more registers alive across the gather spilled); the transposition below runs while they arrive
@@ -372,29 +219,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
     __builtin_amdgcn_sched_barrier(0);
     // ---- publish the next item's index, fetch the one after it (its value is parked in LDS behind the staging barrier).
     // Issued behind the loads the pre-pass waits for: the memory counter is in-order, a wait for those would include it. ---
-    unsigned f_new = 0u;
-    bool fetched = false;
-    if (tid == 0) {
-      unsigned nxt = (unsigned)(item - xcd * chunk + nslots);                 // static stride when there is no queue
-      if (queue) {
-        const unsigned f_next = next_idx[1];
-        if (f_next + 1u >= n_x)                                               // that was the launch's last fetch
-          __hip_atomic_store(queue + xcd * WIN_QUEUE_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        nxt = (unsigned)nslots + f_next;
-        if (nxt < n_x) {
-          // (inline asm: the compiler waits for a returning atomic at the end of this divergent block -- a full round
-          // trip to L2 in front of the pre-pass; the wait now sits where the value is parked, behind the pre-pass)
-          const unsigned one = 1u, zero = 0u;
-          const unsigned *qp = queue + xcd * WIN_QUEUE_STRIDE;
-          // (s_nop: the base may just have been restored by v_readlane; a vector-memory instruction reading a scalar
-          // register a vector instruction wrote needs 5 wait states, and the hazard recogniser does not see into inline asm)
-          asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0"
-                       : "=v"(f_new) : "v"(zero), "v"(one), "s"(qp) : "memory");
-          fetched = true;
-        }
-      }
-      next_idx[0] = nxt;
-    }
+    const ColFetch fetch = col_queue_publish(queue, next_idx, ch, item, tid);
 
     // ---- pre-pass: per-level bounding box (first corners, biased by +1; the box covers x0 .. x0 + 1) ----------------
 #pragma unroll
@@ -430,13 +255,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
                               : col_f32x4{0.f, 0.f, 0.f, 0.f};
         return;
       }
-      unsigned off[4];
-      quad_offsets(own * (unsigned)(L * P * 4), off);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-        for (int g = 0; g < NGW; ++g)
-          wraw[g][s4] = __builtin_bit_cast(col_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(off[s4] + g * 64), 0, 0));
+      col_quad_load<NGW>(rs, own * (unsigned)(L * P * 4), qi, wraw);
     };
     load_weights();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       // boxes in LDS before the barrier
@@ -450,12 +269,9 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
     __builtin_amdgcn_s_setprio(0);
 
     // ---- the next item: its query per lane, its location loads issued (in flight until the next iteration) --------------
-    int item_n, b_n = 0, m_n = 0, qv_n = 0;
-    {
-      const unsigned nxt = __builtin_amdgcn_readfirstlane(next_idx[0]);
-      item_n = nxt < n_x ? xcd * chunk + (int)nxt : item_end;                // never out of the chunk
-    }
-    const bool have_n = item_n < item_end;             // (decoded once this item's first staging is issued, below)
+    const int item_n = col_next_item(next_idx, ch);
+    int b_n = 0, m_n = 0, qv_n = 0;
+    const bool have_n = item_n < ch.item_end;             // (decoded once this item's first staging is issued, below)
 
     // ---- windows and phases (uniform) --------------------------------------------------------------------------------
     int wx0[L], wy0[L], wwid[L], whgt[L], wsize[L], wbase[L], phase_of[L];
@@ -480,7 +296,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
         // A/B, P2 batch 128 (profiles/r04_forward_structural_ab.txt), against the fixed order everywhere: M 2.168 -> 2.085 ms
         // as an op, 2.290 -> 2.209 ms in the bench step; I 1.649 -> 1.700 (the two code paths cost the init-like case 3
         // spilled registers).  The conflict-free order on every level: M 2.038, I 1.779.
-        latin[l] = (wwid[l] - col_max_cell(Ws[l], CX)) + ((int)((hi >> 16) - ly) + 1 - col_max_cell(Hs[l], CY)) >= 16;
+        latin[l] = (wwid[l] - col_max_cell(lv.W[l], grid.CX)) + ((int)((hi >> 16) - ly) + 1 - col_max_cell(lv.H[l], grid.CY)) >= 16;
         if (latin[l]) wwid[l] += (2 - wwid[l]) & 3;
         whgt[l] = (int)((hi >> 16) - ly) + 1;
         wsize[l] = wwid[l] * whgt[l];
@@ -494,7 +310,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
         const int l = col_level_of_step<L>(ll);
         starts_phase[l] = false;
         // (never fits -- or a map too large for the 16-bit box corners --: gathered from global memory, which does not look at the box)
-        if (wsize[l] > pool_use || big_map) {
+        if (wsize[l] > pool_use || ci.big_map) {
           phase_of[l] = -1;
           wbase[l] = 0;
           continue;
@@ -693,7 +509,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
     // spill-free at 4 levels and the fastest on U.)
     auto gather_level_global = [&](auto lc) {
       constexpr int l = decltype(lc)::value;
-      const int H = Hs[l], W = Ws[l];
+      const int H = lv.H[l], W = lv.W[l];
       constexpr unsigned OOB = 0x80000000u;                                    // S * M * D * 4 < 2^31 (C ABI check)
       const unsigned MDb = (unsigned)MD * 4u;
       col_f32x2 part[4][2];                                                    // [member s]: piece (s - qi) % 4 of s's sum
@@ -706,8 +522,8 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
           const bool lft = (unsigned)g.x0 < (unsigned)W, rgt = (unsigned)(g.x0 + 1) < (unsigned)W;
           // (PP: piece c of pixel p of head m at ((m * 4 + c) * S + p) * 16: the pixel stride is 16 bytes, the piece a plane)
           const unsigned pxs = PP ? 16u : MDb;
-          const unsigned a = PP ? (unsigned)(m * (D / 4) * S + St[l] + g.y0 * W + g.x0) * 16u
-                                : (unsigned)(St[l] + g.y0 * W + g.x0) * MDb + (unsigned)(m * D) * 4u;
+          const unsigned a = PP ? (unsigned)(m * (D / 4) * S + lv.St[l] + g.y0 * W + g.x0) * 16u
+                                : (unsigned)(lv.St[l] + g.y0 * W + g.x0) * MDb + (unsigned)(m * D) * 4u;
           const unsigned o1 = (top && lft) ? a : OOB, o2 = (top && rgt) ? a + pxs : OOB;
           const unsigned o3 = (bot && lft) ? a + (unsigned)W * pxs : OOB, o4 = (bot && rgt) ? a + (unsigned)W * pxs + pxs : OOB;
           [&]<int... Ss>(std::integer_sequence<int, Ss...>) {                    // one member at a time (16 registers of data)
@@ -769,19 +585,19 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
         if (phase_of[l] == phx && wsize[l] > 0) {
           // (PP: piece cc of a pixel lives in plane m * 4 + cc, pixels 16 bytes apart: a copy instruction reads four runs of
           // 256 consecutive bytes instead of sixteen 64-byte slices 512 bytes apart)
-          const unsigned lvl_off = PP ? ((unsigned)(m * (D / 4)) * (unsigned)S + (unsigned)St[l]) * 16u
-                                      : (unsigned)St[l] * MDb + (unsigned)(m * D) * 4u;   // bytes, this level and head
-          const unsigned row_bytes = (unsigned)Ws[l] * (PP ? 16u : MDb);
+          const unsigned lvl_off = PP ? ((unsigned)(m * (D / 4)) * (unsigned)S + (unsigned)lv.St[l]) * 16u
+                                      : (unsigned)lv.St[l] * MDb + (unsigned)(m * D) * 4u;   // bytes, this level and head
+          const unsigned row_bytes = (unsigned)lv.W[l] * (PP ? 16u : MDb);
           unsigned char *dst = pool + (size_t)wbase[l] * PXB;
           for (int c0 = 0; c0 < wwid[l]; c0 += CPX) {
             const int xw = c0 + dx, x = wx0[l] + xw;
-            const unsigned voff = (unsigned)x < (unsigned)Ws[l]
+            const unsigned voff = (unsigned)x < (unsigned)lv.W[l]
                                       ? (PP ? (unsigned)x * 16u + (unsigned)cc * ((unsigned)S * 16u) : (unsigned)x * MDb + (unsigned)(cc * 16))
                                       : OOB;
             if (xw < wwid[l]) {
               for (int r = wv; r < whgt[l]; r += NW) {
                 const int y = wy0[l] + r;
-                const bool in_y = (unsigned)y < (unsigned)Hs[l];
+                const bool in_y = (unsigned)y < (unsigned)lv.H[l];
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rsrc, (__attribute__((address_space(3))) void *)(dst + (size_t)(r * wwid[l] + c0) * PXB), 16,
                     (int)(in_y ? voff : OOB), (int)(in_y ? lvl_off + (unsigned)y * row_bytes : 0u), 0, 0);
@@ -862,10 +678,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
       if constexpr (ll == 0) {
         // (thread 0) park the counter value fetched at the top of the item: the weights below need the memory counter at
         // zero anyway, so this wait is free -- anywhere earlier it would stall on the loads issued since
-        if (fetched) {
-          asm volatile("s_waitcnt vmcnt(0)" : "+v"(f_new)::"memory");
-          next_idx[1] = f_new;
-        }
+        col_queue_park(next_idx, fetch);
         front_end();
       }
       __builtin_amdgcn_s_setprio(ll == 0 ? 3 : 2);                            // (wave priorities: see the planning above)
@@ -916,7 +729,7 @@ __global__ __launch_bounds__(COL_BLOCK, COL_WG_PER_CU) void msda_forward_col_ker
                                                         (int)((unsigned)S * (unsigned)MD * 4u), RSRC_FLAGS);
       // an idle lane's record goes out of range (the descriptor's bounds check drops the store)
       // (the record index is formed again rather than kept alive through the gather)
-      const unsigned own_o = (rec_index(qv, m) * (unsigned)(D * 4)) | ((unsigned)(qv >> 31) & 0x80000000u);
+      const unsigned own_o = (col_rec_index(qv, m, M) * (unsigned)(D * 4)) | ((unsigned)(qv >> 31) & 0x80000000u);
       const unsigned oo[4] = {dpp_u<0x00>(own_o), dpp_u<0x55>(own_o), dpp_u<0xAA>(own_o), dpp_u<0xFF>(own_o)};
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4)

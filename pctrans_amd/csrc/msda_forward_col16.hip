@@ -6,6 +6,8 @@
 // structure as msda_forward_col.hip (read that file's header first): work item = (image, pyramid column, head), per-level
 // bounding-box windows staged by LDS-DMA with a zero apron, phases when the windows do not fit together, fixed level
 // order, items handed out per XCD two ahead so that the next item's sampling locations are in flight during the gather.
+// Column grid, lane slots, cell tables, item decode and queue are the shared ones of msda_col_common.hpp,
+// with BLOCK / HALVES queries per item and tid / HALVES as a lane's rank among them.
 // What differs:
 //   * a head-pixel is 32 bytes (16 channels x 2 B): two ds_read_b128 per corner, each converted and accumulated in fp32
 //     (fp16: v_fma_mix_f32; bf16: a shift / mask per element); the pool holds twice the pixels per KB;
@@ -48,101 +50,31 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
   const int MD = M * D;
 
   // ---- level geometry (uniform) -------------------------------------------------------------------------------------
-  int Hs[L], Ws[L], St[L];
+  ColLevels<L> lv;
   float fH[L], fW[L];
   col_f32x2 fWH[L], invWH[L];
 #pragma unroll
   for (int l = 0; l < L; ++l) {
-    Hs[l] = (int)shapes[2 * l];
-    Ws[l] = (int)shapes[2 * l + 1];
-    St[l] = (int)starts[l];
-    fH[l] = uni((float)Hs[l]);
-    fW[l] = uni((float)Ws[l]);
-    fWH[l] = uni_pair((float)Ws[l], (float)Hs[l]);
-    invWH[l] = uni_pair(1.0f / (float)Ws[l], 1.0f / (float)Hs[l]);
+    lv.H[l] = (int)shapes[2 * l];
+    lv.W[l] = (int)shapes[2 * l + 1];
+    lv.St[l] = (int)starts[l];
+    fH[l] = uni((float)lv.H[l]);
+    fW[l] = uni((float)lv.W[l]);
+    fWH[l] = uni_pair((float)lv.W[l], (float)lv.H[l]);
+    invWH[l] = uni_pair(1.0f / (float)lv.W[l], 1.0f / (float)lv.H[l]);
   }
 
-  // ---- column grid: CX x CY cells such that no column holds more than QPW queries (as msda_forward_col.hip) ----------
-  int CX, CY;
-  {
-    int Hf = Hs[0], Wf = Ws[0];
-#pragma unroll
-    for (int l = 1; l < L; ++l)
-      if (Hs[l] * Ws[l] > Hf * Wf) { Hf = Hs[l]; Wf = Ws[l]; }
-    const float area = (float)QPW * (float)(Hf * Wf) / (float)S;
-    const int side = (int)sqrtf(area);
-    const int nxt = min(Wf, max(8, (side + 4) & ~7));
-    CX = (Wf + nxt - 1) / nxt;
-    const int nx0 = (Wf + CX - 1) / CX;
-    const int nyt = max(1, (int)(area / (float)nx0));
-    CY = min(Hf, (Hf + nyt - 1) / nyt);
-    for (int guard = 0; guard < 4096; ++guard) {
-      int maxq = 0;
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        int mx = 0, my = 0;
-        mx = col_max_cell(Ws[l], CX);
-        my = col_max_cell(Hs[l], CY);
-        maxq += mx * my;
-      }
-      if (maxq <= QPW) break;
-      if (CY < Hf) ++CY;
-      else if (CX < Wf) ++CX;
-      else break;
-    }
-  }
-  // ---- this lane's SLOT in a column and the cell tables in LDS (as msda_forward_col.hip: a (query, head) pair's place --
-  // level, x, y inside the level's largest cell -- is fixed for the launch, the per-item decode is two table look-ups and
-  // a multiply-add instead of a walk over the levels with four scalar divisions each) ---------------------------------
-  int lane_c0 = 0;
-  unsigned lane_slot = 0x000FFFFFu;                                            // x | y << 10 | level << 20; x = y = 1023: no slot
-  {
-    int r = tid / HALVES;
-    bool placed = false;
-#pragma unroll
-    for (int ll = 0; ll < L; ++ll) {
-      const int l = L - 1 - ll;
-      const int mx = col_max_cell(Ws[l], CX), my = col_max_cell(Hs[l], CY);
-      const int cnt = mx * my;
-      if (!placed && r < cnt) {
-        const int ly = r / max(mx, 1), lx = r - ly * max(mx, 1);
-        lane_slot = (unsigned)lx | ((unsigned)ly << 10) | ((unsigned)l << 20);
-        lane_c0 = St[l] + ly * Ws[l] + lx;
-        placed = true;
-      }
-      r -= placed ? 0 : cnt;
-    }
-  }
-  const int tab_px = ((L * (CX + CY) + L) * 4 + PXB - 1) / PXB;
+  // ---- column grid, the (query, head) pair's slot in a column, the cell tables and the launch's items
+  // (msda_col_common.hpp; an item holds QPW queries, a lane's rank among them is tid / HALVES) -------------------------
+  const ColGrid grid = col_grid<L, QPW>(lv, S);
+  ColSlot slot = col_lane_slot<L>(lv, grid, tid / HALVES);
+  const int tab_px = (col_table_bytes<L>(grid) + PXB - 1) / PXB;               // tables: carved off the end of the pool
   const int pool_eff = pool_px - tab_px;
   unsigned *tab = reinterpret_cast<unsigned *>(pool + (size_t)max(pool_eff, 0) * PXB);
-  const bool use_tab = pool_eff * 2 >= pool_px;            // else: FLAT columns (absurdly elongated maps), see the decode
-  if (use_tab) {
-    for (int t = tid; t < L * CX; t += BLOCK) {
-      const int l = t / CX, c = t - l * CX;
-      const int a = col_lo(c, Ws[l], CX);
-      tab[t] = (unsigned)a | ((unsigned)(col_lo(c + 1, Ws[l], CX) - a) << 16);
-    }
-    for (int t = tid; t < L * CY; t += BLOCK) {
-      const int l = t / CY, c = t - l * CY;
-      const int a = col_lo(c, Hs[l], CY);
-      tab[L * CX + t] = (unsigned)a | ((unsigned)(col_lo(c + 1, Hs[l], CY) - a) << 16);
-    }
-    if (tid < L) tab[L * (CX + CY) + tid] = (unsigned)Ws[tid];
-    __syncthreads();
-  }
+  const bool use_tab = pool_eff * 2 >= pool_px;            // else: FLAT columns (absurdly elongated maps)
+  if (use_tab) col_fill_tables<L, BLOCK>(tab, lv, grid, tid);
   const int pool_use = use_tab ? pool_eff : pool_px;                           // pixels the windows may take
-  bool big_map = false;                                                        // a level too large for the 16-bit box corners
-#pragma unroll
-  for (int l = 0; l < L; ++l) big_map = big_map || Ws[l] > 65531 || Hs[l] > 65531;
-  int ncol = CX * CY;
-  if (!use_tab) {
-    ncol = 0;
-#pragma unroll
-    for (int l = 0; l < L; ++l) ncol += (Hs[l] * Ws[l] + QPW - 1) / QPW;
-  }
-  const int items = N * ncol * M;
-  const UDiv dv_ncolM = make_udiv(ncol * M), dv_2ncol = make_udiv(2 * ncol), dv_CX = make_udiv(CX);
+  const ColItems ci = col_items<L, QPW>(lv, grid, use_tab, N, M);
 
   // pixels 0 and 1 of the pool are zeros: gated-out samples read them
   if (tid < 4) reinterpret_cast<col_f32x4 *>(pool)[tid] = col_f32x4{0.f, 0.f, 0.f, 0.f};
@@ -155,55 +87,13 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
   rot[0] = rho << 4;
   rot[1] = (rho ^ 1u) << 4;
 
-  const int xcd = blockIdx.x & 7, slot0 = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int chunk = (items + 7) / 8;
-  const int item_end = min((xcd + 1) * chunk, items);
-  const unsigned n_x = (unsigned)max(item_end - xcd * chunk, 0);
+  const ColChunk ch = col_chunk(ci.items);                 // XCD-chunked walk, queue two items ahead (msda_col_common.hpp)
 
-  // item -> (image, head) [uniform] and this lane's query (qv = q, or ~q of the query an idle lane shadows); order inside
-  // an image: head pair, column, head in the pair (msda_forward_col.hip)
-  auto decode = [&](const int it, int &b_, int &m_, int &qv_) {
-    b_ = udiv_s(it, dv_ncolM);
-    const int r_img = it - b_ * (ncol * M);
-    int col;
-    if (r_img < 2 * ncol * (M >> 1)) {
-      const int pr = udiv_s(r_img, dv_2ncol);
-      const int rr = r_img - pr * 2 * ncol;
-      col = rr >> 1;
-      m_ = 2 * pr + (rr & 1);
-    } else {
-      col = r_img - 2 * ncol * (M >> 1);
-      m_ = M - 1;
-    }
-    const int cy = udiv_s(col, dv_CX), cx = col - cy * CX;
-    int q;
-    bool valid;
-    if (use_tab) {
-      const unsigned lx = lane_slot & 0x3FFu, ly = (lane_slot >> 10) & 0x3FFu, lv = lane_slot >> 20;
-      const unsigned char *tb = reinterpret_cast<const unsigned char *>(tab);
-      const unsigned xt = *reinterpret_cast<const unsigned *>(tb + (__umul24(lv, (unsigned)(CX * 4)) + (unsigned)(cx * 4)));
-      const unsigned yt = *reinterpret_cast<const unsigned *>(tb + (__umul24(lv, (unsigned)(CY * 4)) + (unsigned)((L * CX + cy) * 4)));
-      const unsigned lw = *reinterpret_cast<const unsigned *>(tb + (lv * 4u + (unsigned)(L * (CX + CY) * 4)));
-      valid = lx < (xt >> 16) && ly < (yt >> 16);
-      q = lane_c0 + (int)__umul24(yt & 0xFFFFu, lw) + (int)(xt & 0xFFFFu);
-    } else {
-      int c = col;
-      q = 0;
-      valid = false;
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        const int cnt = Hs[l] * Ws[l], nch = (cnt + QPW - 1) / QPW;
-        if (c >= 0 && c < nch) {
-          q = St[l] + c * QPW + tid / HALVES;
-          valid = c * QPW + tid / HALVES < cnt;
-        }
-        c = c >= nch ? c - nch : -1;
-      }
-    }
-    // idle lanes shadow a query of the column (the wave's first busy lane's; none: query 0 -- correct, merely wide boxes)
-    const unsigned long long vm = __ballot(valid);
-    const int q_sh = vm ? __builtin_amdgcn_readlane(q, (int)__builtin_ctzll(vm)) : 0;
-    qv_ = valid ? q : ~q_sh;
+  auto decode = [&](const int it, int &b_, int &m_, int &qv_) {               // col_decode for this launch and lane
+    const ColItem i = col_decode<L, QPW>(it, ci, grid, lv, tab, slot, tid / HALVES);
+    b_ = i.b;
+    m_ = i.m;
+    qv_ = i.qv;
   };
   // this lane's 4 points of level l of its record: 32 contiguous bytes (per-image base uniform, 32-bit offsets)
   auto issue_loc_level = [&](auto lc, const int b_, const int m_, const int qv_, col_f32x4 (&raw)[L][2]) {
@@ -215,8 +105,8 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
     raw[l][1] = *reinterpret_cast<const col_f32x4 *>(base + (size_t)(o + 4u));
   };
 
-  int item = xcd * chunk + slot0;
-  bool have = item < item_end;
+  int item = ch.xcd * ch.chunk + ch.slot0;
+  bool have = item < ch.item_end;
   int b = 0, m = 0, qv = 0;
   col_f32x4 raw[L][2];
   if (have) {
@@ -224,11 +114,11 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
     [&]<int... Ls>(std::integer_sequence<int, Ls...>) {
       (issue_loc_level(std::integral_constant<int, Ls>{}, b, m, qv, raw), ...);
     }(std::make_integer_sequence<int, L>{});
-    if (queue && tid == 0) next_idx[1] = atomicAdd(queue + xcd * WIN_QUEUE_STRIDE, 1u);
+    col_queue_first_fetch(queue, next_idx, ch, tid);
   }
 
   while (have) {
-    asm volatile("" : "+v"(tid), "+v"(lane_slot), "+v"(lane_c0));     // (opaque per iteration: see msda_forward_col.hip)
+    asm volatile("" : "+v"(tid), "+v"(slot.slot), "+v"(slot.c0));     // (opaque per iteration: see msda_forward_col.hip)
     const int hh = tid % HALVES;
     const bool valid = qv >= 0;
     const int q = valid ? qv : ~qv;
@@ -258,25 +148,8 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
       for (int k = 0; k < PL; ++k) asm volatile("" : "+v"(lxy[l][k]));
     __builtin_amdgcn_sched_barrier(0);
 
-    // ---- publish the next item's index, fetch the one after it (msda_forward_col.hip: queue protocol, two ahead) -----
-    unsigned f_new = 0u;
-    bool fetched = false;
-    if (tid == 0) {
-      unsigned nxt = (unsigned)(item - xcd * chunk + nslots);
-      if (queue) {
-        const unsigned f_next = next_idx[1];
-        if (f_next + 1u >= n_x) __hip_atomic_store(queue + xcd * WIN_QUEUE_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        nxt = (unsigned)nslots + f_next;
-        if (nxt < n_x) {
-          const unsigned one = 1u, zero = 0u;
-          const unsigned *qp = queue + xcd * WIN_QUEUE_STRIDE;
-          asm volatile("s_nop 4\n\tglobal_atomic_add %0, %1, %2, %3 sc0"
-                       : "=v"(f_new) : "v"(zero), "v"(one), "s"(qp) : "memory");
-          fetched = true;
-        }
-      }
-      next_idx[0] = nxt;
-    }
+    // ---- publish the next item's index, fetch the one after it -------------------------------------------------------
+    const ColFetch fetch = col_queue_publish(queue, next_idx, ch, item, tid);
 
     // ---- pre-pass: per-level bounding box of the lane's four first corners (biased by +1) ----------------------------
 #pragma unroll
@@ -311,12 +184,9 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();                                                          // (A) boxes visible; pool free
 
-    int item_n, b_n = 0, m_n = 0, qv_n = 0;
-    {
-      const unsigned nxt = __builtin_amdgcn_readfirstlane(next_idx[0]);
-      item_n = nxt < n_x ? xcd * chunk + (int)nxt : item_end;
-    }
-    const bool have_n = item_n < item_end;
+    const int item_n = col_next_item(next_idx, ch);
+    int b_n = 0, m_n = 0, qv_n = 0;
+    const bool have_n = item_n < ch.item_end;
 
     // ---- windows and phases (uniform) --------------------------------------------------------------------------------
     int wx0[L], wy0[L], wwid[L], whgt[L], wsize[L], wbase[L], phase_of[L];
@@ -341,7 +211,7 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
       for (int ll = 0; ll < L; ++ll) {
         const int l = col_level_of_step<L>(ll);
         starts_phase[l] = false;
-        if (wsize[l] > pool_use - 2 || big_map) {     // (or too large for the 16-bit box corners)
+        if (wsize[l] > pool_use - 2 || ci.big_map) {     // (or too large for the 16-bit box corners)
           phase_of[l] = -1;
           wbase[l] = 0;
           continue;
@@ -457,7 +327,7 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
     // two neighbouring queries.)
     auto gather_level_global = [&](auto lc) {
       constexpr int l = decltype(lc)::value;
-      const int H = Hs[l], W = Ws[l];
+      const int H = lv.H[l], W = lv.W[l];
       constexpr unsigned OOB = 0x80000000u;
       const unsigned MDb = (unsigned)MD * 2u;
       const unsigned pc = (unsigned)(lane & 1) << 4;                           // (an out-of-range offset stays out of range)
@@ -471,7 +341,7 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
           const Geo g = geometry(lc, std::integral_constant<int, Ks>{});
           const bool top = g.gate && g.y0 >= 0, bot = g.gate && g.y0 + 1 <= H - 1;
           const bool lft = g.x0 >= 0, rgt = g.x0 + 1 <= W - 1;
-          const unsigned a = (unsigned)(St[l] + g.y0 * W + g.x0) * MDb + (unsigned)(m * D) * 2u;
+          const unsigned a = (unsigned)(lv.St[l] + g.y0 * W + g.x0) * MDb + (unsigned)(m * D) * 2u;
           const unsigned o1 = (top && lft) ? a : OOB, o2 = (top && rgt) ? a + MDb : OOB;
           const unsigned o3 = (bot && lft) ? a + (unsigned)W * MDb : OOB, o4 = (bot && rgt) ? a + (unsigned)W * MDb + MDb : OOB;
           [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
@@ -533,16 +403,16 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
 #pragma unroll
       for (int l = 0; l < L; ++l) {
         if (phase_of[l] == phx && wsize[l] > 0) {
-          const unsigned lvl_off = (unsigned)St[l] * MDb + (unsigned)(m * D) * 2u;
-          const unsigned row_bytes = (unsigned)Ws[l] * MDb;
+          const unsigned lvl_off = (unsigned)lv.St[l] * MDb + (unsigned)(m * D) * 2u;
+          const unsigned row_bytes = (unsigned)lv.W[l] * MDb;
           unsigned char *dst = pool + (size_t)wbase[l] * PXB;
           for (int c0 = 0; c0 < wwid[l]; c0 += CPX) {
             const int xw = c0 + dx, x = wx0[l] + xw;
-            const unsigned voff = (unsigned)x < (unsigned)Ws[l] ? (unsigned)x * MDb + (unsigned)(cc * 16) : OOB;
+            const unsigned voff = (unsigned)x < (unsigned)lv.W[l] ? (unsigned)x * MDb + (unsigned)(cc * 16) : OOB;
             if (xw < wwid[l]) {
               for (int r = wv; r < whgt[l]; r += NW) {
                 const int y = wy0[l] + r;
-                const bool in_y = (unsigned)y < (unsigned)Hs[l];
+                const bool in_y = (unsigned)y < (unsigned)lv.H[l];
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rsrc, (__attribute__((address_space(3))) void *)(dst + (size_t)(r * wwid[l] + c0) * PXB), 16,
                     (int)(in_y ? voff : OOB), (int)(in_y ? lvl_off + (unsigned)y * row_bytes : 0u), 0, 0);
@@ -590,10 +460,7 @@ __global__ __launch_bounds__(BLOCK, 3) void msda_forward_col16_kernel(
         __syncthreads();
       }
       if constexpr (ll == 0) {
-        if (fetched) {
-          asm volatile("s_waitcnt vmcnt(0)" : "+v"(f_new)::"memory");
-          next_idx[1] = f_new;
-        }
+        col_queue_park(next_idx, fetch);
         front_end();
       }
       __builtin_amdgcn_s_setprio(ll == 0 ? 3 : 2);          // (the gather before the other workgroups' bookkeeping: msda_forward_col.hip)
