@@ -176,6 +176,20 @@ SELF_ATTN_TRAIN_SYMBOLS = {
                                         "tests/test_self_attention_train_gpu.py"),
 }
 
+# Entry points of the criterion's reference-point and semantic losses (include/pctrans_hip_aux_loss.h; pctrans_amd/aux_loss.py:
+# refpoint_l1_losses, sem_focal_loss; SetCriterion does not call them yet).  A table of its own, as the self-attention's:
+# name -> (argtypes, restype, the test module that checks the entry against float64)
+AUX_LOSS_SYMBOLS = {
+    "pct_refpoint_l1_forward_f32": ([_vp] * 4 + [_i, ctypes.c_longlong, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp], _i,
+                                    "tests/test_aux_loss_gpu.py"),
+    "pct_refpoint_l1_backward_f32": ([_vp] * 5 + [_i, ctypes.c_longlong, _i, _i, _i, ctypes.c_float, _vp, _vp], _i,
+                                     "tests/test_aux_loss_gpu.py"),
+    "pct_sigmoid_focal_strided_forward_f32": ([_vp, _vp] + [_i] * 7 + [ctypes.c_float] + [_vp] * 4, _i,
+                                              "tests/test_aux_loss_gpu.py"),
+    "pct_sigmoid_focal_strided_backward_f32": ([_vp, _vp, _i, _vp, _vp] + [_i] * 6 + [ctypes.c_float, _vp, _vp], _i,
+                                               "tests/test_aux_loss_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -196,7 +210,7 @@ def lib():
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
             + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())
-            + list(SELF_ATTN_TRAIN_SYMBOLS.items())]:
+            + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

@@ -660,6 +660,59 @@ int pct_reid_dice_rows_backward_f32(const float *logits, const int32_t *image_st
                                         workspace, grad_logits, static_cast<hipStream_t>(stream));
 }
 
+int pct_refpoint_l1_forward_f32(const float *points, const float *target_points, const int32_t *src, const int32_t *tgt, int heads,
+                                long long rows, int dims, int num_targets, int pairs, float num_masks, float *loss,
+                                int32_t *status, void *stream)
+{
+  if (heads < 0 || rows < 0 || dims <= 0 || num_targets < 0 || pairs < 0) return PCT_ERR_BAD_ARG;
+  if (heads == 0) return PCT_OK;
+  if (!loss || !status || (pairs > 0 && (!points || !target_points || !src || !tgt))) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)points | (uintptr_t)target_points | (uintptr_t)src | (uintptr_t)tgt | (uintptr_t)loss | (uintptr_t)status) & 3u)
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_refpoint_l1_forward(points, target_points, src, tgt, heads, rows, dims, num_targets, pairs, num_masks, loss,
+                                         status, static_cast<hipStream_t>(stream));
+}
+
+int pct_refpoint_l1_backward_f32(const float *points, const float *target_points, const int32_t *src, const int32_t *tgt,
+                                 const float *grad_loss, int heads, long long rows, int dims, int num_targets, int pairs,
+                                 float num_masks, float *grad_points, void *stream)
+{
+  if (heads < 0 || rows < 0 || dims <= 0 || num_targets < 0 || pairs < 0) return PCT_ERR_BAD_ARG;
+  if (heads == 0 || rows == 0) return PCT_OK;
+  if (!points || !grad_loss || !grad_points || (pairs > 0 && (!target_points || !src || !tgt))) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)points | (uintptr_t)target_points | (uintptr_t)src | (uintptr_t)tgt | (uintptr_t)grad_loss |
+       (uintptr_t)grad_points) & 3u)
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_refpoint_l1_backward(points, target_points, src, tgt, grad_loss, heads, rows, dims, num_targets, pairs,
+                                          num_masks, grad_points, static_cast<hipStream_t>(stream));
+}
+
+int pct_sigmoid_focal_strided_forward_f32(const float *logits, const void *fg, int fg_dtype, int batch, int out_h, int out_w,
+                                          int height, int width, int stride, float alpha, void *workspace, float *loss,
+                                          float *num_pos, void *stream)
+{
+  if (batch <= 0 || out_h <= 0 || out_w <= 0 || height <= 0 || width <= 0 || stride <= 0) return PCT_ERR_BAD_ARG;
+  if (!logits || !fg || !workspace || !loss || !num_pos) return PCT_ERR_BAD_ARG;
+  if ((((uintptr_t)logits | (uintptr_t)loss | (uintptr_t)num_pos | (fg_dtype == 4 ? (uintptr_t)fg : 0)) & 3u) ||
+      ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_sigmoid_focal_strided_forward(logits, fg, fg_dtype, batch, out_h, out_w, height, width, stride, alpha,
+                                                   workspace, loss, num_pos, static_cast<hipStream_t>(stream));
+}
+
+int pct_sigmoid_focal_strided_backward_f32(const float *logits, const void *fg, int fg_dtype, const float *num_pos,
+                                           const float *grad_loss, int batch, int out_h, int out_w, int height, int width,
+                                           int stride, float alpha, float *grad_logits, void *stream)
+{
+  if (batch <= 0 || out_h <= 0 || out_w <= 0 || height <= 0 || width <= 0 || stride <= 0) return PCT_ERR_BAD_ARG;
+  if (!logits || !fg || !num_pos || !grad_loss || !grad_logits) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)logits | (uintptr_t)num_pos | (uintptr_t)grad_loss | (uintptr_t)grad_logits |
+       (fg_dtype == 4 ? (uintptr_t)fg : 0)) & 3u)
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_sigmoid_focal_strided_backward(logits, fg, fg_dtype, num_pos, grad_loss, batch, out_h, out_w, height, width,
+                                                    stride, alpha, grad_logits, static_cast<hipStream_t>(stream));
+}
+
 int pct_reid_nearest_positive_f32(const float *query, const int32_t *pos, int num_query, int batch, int channels, int max_pos,
                                   int32_t *nearest, void *stream)
 {

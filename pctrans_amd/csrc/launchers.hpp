@@ -271,6 +271,22 @@ int launch_reid_query_rows_backward(const float *query, const int *image_start, 
 int launch_contrast_loss_rows(const float *rows, const int *image_of, const int *key, const int *owner, int I, int Q, int N,
                               float inv_temperature, float *loss, float *coef, hipStream_t stream);
 
+// ---- the criterion's reference-point L1 loss of all heads and its strided semantic focal loss (aux_losses.hip;
+// include/pctrans_hip_aux_loss.h).  fg_dtype: 0 one byte, 4 float32.  PCT_ERR_BAD_ARG / PCT_ERR_UNSUPPORTED before any launch for a
+// geometry that is wrong or not covered ----------------------------------------------------------------------------------------
+int launch_refpoint_l1_forward(const float *points, const float *target_points, const int *src, const int *tgt, int heads,
+                               long long rows, int dims, int num_targets, int pairs, float num_masks, float *loss, int *status,
+                               hipStream_t stream);
+int launch_refpoint_l1_backward(const float *points, const float *target_points, const int *src, const int *tgt,
+                                const float *grad_loss, int heads, long long rows, int dims, int num_targets, int pairs,
+                                float num_masks, float *grad_points, hipStream_t stream);
+int launch_sigmoid_focal_strided_forward(const float *logits, const void *fg, int fg_dtype, int batch, int out_h, int out_w,
+                                         int height, int width, int stride, float alpha, void *workspace, float *loss,
+                                         float *num_pos, hipStream_t stream);
+int launch_sigmoid_focal_strided_backward(const float *logits, const void *fg, int fg_dtype, const float *num_pos,
+                                          const float *grad_loss, int batch, int out_h, int out_w, int height, int width,
+                                          int stride, float alpha, float *grad_logits, hipStream_t stream);
+
 // ---- instance targets from label maps (instance_targets.hip; include/pctrans_hip_targets.h).  dtype: 0 uint8, 1 int16, 2 int32,
 // 3 int64, 4 float32.  PCT_ERR_UNSUPPORTED before any launch for a geometry the kernels do not cover -------------------------
 int instance_targets_geometry_status(int dtype, int N, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
