@@ -190,6 +190,14 @@ AUX_LOSS_SYMBOLS = {
                                                "tests/test_aux_loss_gpu.py"),
 }
 
+# Entry point of the split-operand cross-attention for any key count (include/pctrans_hip_xattn.h; pctrans_amd/ragged_attention.py,
+# reached with CrossAttentionLayer.ragged_keys = "hip").  A table of its own, as the losses': name -> (argtypes, restype, the
+# test module that checks the entry -- against pct_masked_attention_bf16 on the concatenated operands: the outputs are the same bits)
+XATTN_SYMBOLS = {
+    "pct_cross_attention_ragged_bf16": ([_vp] * 6 + [_i, _vp] + [_i] * 4 + [ctypes.c_float, _vp, _vp], _i,
+                                        "tests/test_ragged_attention_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -210,7 +218,7 @@ def lib():
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
             + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())
-            + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items())]:
+            + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items()) + list(XATTN_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

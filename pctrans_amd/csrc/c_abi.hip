@@ -1001,6 +1001,22 @@ int pct_cross_attention_bf16(const void *q_content, const void *q_pos, const voi
                                                 num_query, num_key, scale, out, static_cast<hipStream_t>(stream)));
 }
 
+int pct_cross_attention_ragged_bf16(const void *q_content, const void *q_pos, const void *k_content, const void *k_pos,
+                                    const void *v, const unsigned char *mask, int mask_pitch, const unsigned char *row_open,
+                                    int batch, int heads, int num_query, int num_key, float scale, void *out, void *stream)
+{
+  if (batch < 0 || heads <= 0 || num_query < 0 || num_key < 1) return PCT_ERR_BAD_ARG;
+  if (mask && (mask_pitch < num_key || mask_pitch % 16 != 0)) return PCT_ERR_BAD_ARG;
+  if (batch == 0 || num_query == 0) return PCT_OK;
+  if (!q_content || !q_pos || !k_content || !k_pos || !v || !out) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v | (uintptr_t)mask) & 15u)
+    return PCT_ERR_ALIGNMENT;
+  if ((uintptr_t)out & 7u) return PCT_ERR_ALIGNMENT;
+  return abi_status(pct::launch_cross_attention_ragged(q_content, q_pos, k_content, k_pos, v, mask, mask ? mask_pitch : 0,
+                                                       mask ? row_open : nullptr, batch, heads, num_query, num_key, scale, out,
+                                                       static_cast<hipStream_t>(stream)));
+}
+
 // The argument checks of the four differentiable fp32 attention entries, in the order the ABI fixes: a negative size or no head,
 // the empty call (nothing is read, every pointer may be null), a null pointer, a pointer off 16 bytes (self-attention:
 // num_key = num_query).  -> true: launch; false: return *status.

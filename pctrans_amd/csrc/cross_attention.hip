@@ -39,6 +39,14 @@ typedef unsigned xa_u32x2 __attribute__((ext_vector_type(2)));
 // row_open [N, Q] bytes or NULL: nonzero = this query's mask row is ignored (it attends everywhere) -- the decoder's "a query
 // whose mask rules out every pixel attends everywhere instead" (dec.py:561) without re-writing the [N, Q, S] mask;
 // out [Q, N, heads*16] bf16.  S % 64 == 0, heads % 4 == 0.
+// RAGGED instantiations (pct_cross_attention_ragged_bf16): any S >= 1, mask rows mask_pitch bytes apart (mask_pitch % 16 == 0,
+// mask_pitch >= S; bytes at positions >= S are never trusted).  The last chunk then holds 1 .. 64 keys.  Its rules:
+//   * no load addresses a key past S - 1 or a mask byte past mask_pitch (see fetch);
+//   * the LDS rows of keys >= S hold zeros, K and V alike: p = 0 times a finite value, never a NaN;
+//   * keys >= S are dead whatever the mask bytes, row_open or HAS_MASK say: their dead bytes come from the key index and are ORed
+//     in AFTER the AND with keep[t] (an opened row attends to every real key and to nothing else);
+//   * a 32-key step without a live key (S % 64 in 1 .. 32: the chunk's second step) is skipped -- masked_attention.hip walks
+//     ceil(S / 32) steps, and the bit identity with it on the concatenated operands holds for every S.
 struct XaShared {
   xa_u32x4 sKc[2][XA_CH * 8], sKp[2][XA_CH * 8], sV[2][XA_CH * 8];
   unsigned sM[2][XA_T * 16][16];
@@ -46,13 +54,13 @@ struct XaShared {
 
 // NT: the query tiles this workgroup's waves carry (1 .. XA_T; compile time, so that the tiles' chains are straight-line code
 // the scheduler can interleave -- with a run-time count each tile became its own basic block)
-template <bool HAS_MASK, int NT>
+template <bool HAS_MASK, bool RAGGED, int NT>
 __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 *__restrict__ q_c, const __bf16 *__restrict__ q_s,
                                                      const __bf16 *__restrict__ k_c, const __bf16 *__restrict__ k_p,
                                                      const __bf16 *__restrict__ v, const unsigned char *__restrict__ mask,
                                                      const unsigned char *__restrict__ row_open, const int N, const int heads,
-                                                     const int Q, const int S, const float scale, const int tgroups,
-                                                     __bf16 *__restrict__ out)
+                                                     const int Q, const int S, const int mask_pitch, const float scale,
+                                                     const int tgroups, __bf16 *__restrict__ out)
 {
   auto &sKc = sh.sKc;
   auto &sKp = sh.sKp;
@@ -99,17 +107,39 @@ __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 
   const int sm_q = tid >> 2, sm_part = tid & 3;
   const unsigned char *m_row = nullptr;
   if constexpr (HAS_MASK)
-    m_row = mask + ((size_t)n * Q + min(tile0 * 16 + sm_q, Q - 1)) * S + sm_part * 16;
+    m_row = mask + ((size_t)n * Q + min(tile0 * 16 + sm_q, Q - 1)) * (RAGGED ? mask_pitch : S) + sm_part * 16;
   xa_u32x4 pkc[2], pkp[2], pv[2], pm;
   auto fetch = [&](const int key0) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      const size_t off = (size_t)(key0 + sk_key + 32 * i) * row_elems + sk_c * 8;
+      int key = key0 + sk_key + 32 * i;
+      // RAGGED address bound: the row index is min(key, S - 1) <= S - 1 and the piece lies inside that row's N * C elements
+      // (n * C + hg * 64 + sk_c * 8 + 8 <= N * C), so the last byte read is inside key S - 1's row of the tensor; what a
+      // thread fetched for a key >= S is discarded for zeros
+      const bool live = !RAGGED || key < S;
+      if constexpr (RAGGED) key = min(key, S - 1);
+      const size_t off = (size_t)key * row_elems + sk_c * 8;
       pkc[i] = *reinterpret_cast<const xa_u32x4 *>(kc_img + off);
       pkp[i] = *reinterpret_cast<const xa_u32x4 *>(kp_img + off);
       pv[i] = *reinterpret_cast<const xa_u32x4 *>(v_img + off);
+      if constexpr (RAGGED) {
+        const xa_u32x4 zero = {0u, 0u, 0u, 0u};
+        pkc[i] = live ? pkc[i] : zero;
+        pkp[i] = live ? pkp[i] : zero;
+        pv[i] = live ? pv[i] : zero;
+      }
     }
-    if constexpr (HAS_MASK) pm = *reinterpret_cast<const xa_u32x4 *>(m_row + key0);
+    if constexpr (HAS_MASK) {
+      if constexpr (RAGGED) {
+        // address bound: the piece covers the row's bytes [key0 + 16 sm_part, + 16); key0, 16 sm_part and mask_pitch are
+        // multiples of 16, so start < mask_pitch implies end <= mask_pitch, and the address (16-byte aligned base + multiples
+        // of 16) is aligned.  A piece at or past the pitch is not fetched: all its keys are >= S, dead by the key index
+        pm = xa_u32x4{~0u, ~0u, ~0u, ~0u};
+        if (key0 + sm_part * 16 < mask_pitch) pm = *reinterpret_cast<const xa_u32x4 *>(m_row + key0);
+      } else {
+        pm = *reinterpret_cast<const xa_u32x4 *>(m_row + key0);
+      }
+    }
   };
   auto stash = [&](const int buf) {
 #pragma unroll
@@ -136,7 +166,7 @@ __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 
   const int v_r = 4 * g + (col >> 2), v_c = 2 * wave + ((col & 3) >> 1), v_h = col & 1;
   const int m_rot = 2 * (col >> 1);
 
-  const int nch = S / XA_CH;
+  const int nch = RAGGED ? (S + XA_CH - 1) / XA_CH : S / XA_CH;
   fetch(0);
   stash(0);
   __syncthreads();
@@ -148,6 +178,14 @@ __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 
 #pragma unroll
     for (int j = 0; j < XA_CH / 32; ++j) {
       const int kb = 32 * j;
+      // RAGGED: dead bytes of the keys >= S among this lane's kA .. kA + 3 and kB .. kB + 3 (0 .. 4 keys left in each group)
+      unsigned tailA = 0, tailB = 0;
+      if constexpr (RAGGED) {
+        if (ch * XA_CH + kb >= S) break;                  // no live key in this step (uniform: S is a launch constant)
+        const int leftA = S - (ch * XA_CH + kb + 4 * g), leftB = leftA - 16;
+        tailA = leftA >= 4 ? 0u : (leftA <= 0 ? ~0u : ~0u << (8 * leftA));
+        tailB = leftB >= 4 ? 0u : (leftB <= 0 ? ~0u : ~0u << (8 * leftB));
+      }
       // ---- fragments of this 32-key step, shared by the wave's query tiles ------------------------------------------------
       const int ka = kb + col, kb2 = kb + 16 + col;
       const bf16x8 a0 = *reinterpret_cast<const bf16x8 *>(kt + (ka * 8 + (a_c ^ (ka & 7))) * 16);
@@ -163,6 +201,10 @@ __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 
           const unsigned *mr = sM[buf][t * 16 + col];
           mA = mr[(8 * j + g + m_rot) & 15] & keep[t];
           mB = mr[(8 * j + 4 + g + m_rot) & 15] & keep[t];
+        }
+        if constexpr (RAGGED) {
+          mA |= tailA;                                      // after the AND with keep: an opened row's tail stays dead
+          mB |= tailB;
         }
         attn_step(a0, a1, qb[t], va, mA, mB, scale, o[t], m_run[t], l_run[t]);
       }
@@ -200,10 +242,31 @@ __global__ __launch_bounds__(256, 2) void cross_attention_kernel(const __bf16 *_
   const int tg = (int)(lb % (unsigned)tgroups);
   const int ntile = min(XA_T, (Q + 15) / 16 - tg * XA_T);            // uniform over the workgroup
   static_assert(XA_T == 4, "dispatch below");
-  if (ntile == 4) cross_attention_body<HAS_MASK, 4>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, scale, tgroups, out);
-  else if (ntile == 3) cross_attention_body<HAS_MASK, 3>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, scale, tgroups, out);
-  else if (ntile == 2) cross_attention_body<HAS_MASK, 2>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, scale, tgroups, out);
-  else cross_attention_body<HAS_MASK, 1>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, scale, tgroups, out);
+  if (ntile == 4) cross_attention_body<HAS_MASK, false, 4>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, S, scale, tgroups, out);
+  else if (ntile == 3) cross_attention_body<HAS_MASK, false, 3>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, S, scale, tgroups, out);
+  else if (ntile == 2) cross_attention_body<HAS_MASK, false, 2>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, S, scale, tgroups, out);
+  else cross_attention_body<HAS_MASK, false, 1>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, S, scale, tgroups, out);
+}
+
+// any S >= 1 (the RAGGED rules above); the same workgroup shape, LDS image and dispatch
+template <bool HAS_MASK>
+__global__ __launch_bounds__(256, 2) void cross_attention_ragged_kernel(
+    const __bf16 *__restrict__ q_c, const __bf16 *__restrict__ q_s, const __bf16 *__restrict__ k_c, const __bf16 *__restrict__ k_p,
+    const __bf16 *__restrict__ v, const unsigned char *__restrict__ mask, const unsigned char *__restrict__ row_open, const int N,
+    const int heads, const int Q, const int S, const int mask_pitch, const float scale, const int tgroups, __bf16 *__restrict__ out)
+{
+  __shared__ __attribute__((aligned(16))) XaShared sh;
+  const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+  const int tg = (int)(lb % (unsigned)tgroups);
+  const int ntile = min(XA_T, (Q + 15) / 16 - tg * XA_T);            // uniform over the workgroup
+  static_assert(XA_T == 4, "dispatch below");
+#define PCT_XA_RAGGED(NT_) \
+  cross_attention_body<HAS_MASK, true, NT_>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, mask_pitch, scale, tgroups, out)
+  if (ntile == 4) PCT_XA_RAGGED(4);
+  else if (ntile == 3) PCT_XA_RAGGED(3);
+  else if (ntile == 2) PCT_XA_RAGGED(2);
+  else PCT_XA_RAGGED(1);
+#undef PCT_XA_RAGGED
 }
 
 // PCT_NOT_COVERED: geometry not covered (the caller concatenates the halves and uses pct_masked_attention_bf16)
@@ -229,6 +292,35 @@ int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, co
   else
     hipLaunchKernelGGL(cross_attention_kernel<false>, grid, block, 0, stream, qc, qs, kc, kp, vv, mask, row_open, N, heads, Q, S,
                        scale, tgroups, static_cast<__bf16 *>(out));
+  return (int)hipGetLastError();
+}
+
+// Any S >= 1, mask rows mask_pitch bytes apart (the caller has checked mask_pitch >= S and mask_pitch % 16 == 0).  A call the
+// 64-key kernel covers in this very form goes to it: the same bits.  PCT_NOT_COVERED: heads % 4 != 0 or the 2^31 element limit
+int launch_cross_attention_ragged(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
+                                  const unsigned char *mask, int mask_pitch, const unsigned char *row_open, int N, int heads,
+                                  int Q, int S, float scale, void *out, hipStream_t stream)
+{
+  if (heads <= 0 || heads % XA_HG != 0 || S <= 0) return PCT_NOT_COVERED;
+  if (N == 0 || Q == 0) return 0;
+  if ((long long)S * N * heads * 16 >= 0x7fffffffLL || (long long)Q * N * heads * 16 >= 0x7fffffffLL) return PCT_NOT_COVERED;
+  if (S % XA_CH == 0 && (!mask || mask_pitch == S))
+    return launch_cross_attention(q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, scale, out, stream);
+  if ((((uintptr_t)q_c | (uintptr_t)q_s | (uintptr_t)k_c | (uintptr_t)k_p | (uintptr_t)v) & 15u) || ((uintptr_t)out & 7u)) return PCT_NOT_COVERED;
+  if (mask && (((uintptr_t)mask & 15u) || (mask_pitch & 15) || mask_pitch < S)) return PCT_NOT_COVERED;
+  const int qtiles = (Q + 15) / 16, tgroups = (qtiles + XA_T - 1) / XA_T;
+  const long long nblk = (long long)N * (heads / XA_HG) * tgroups;
+  if (nblk > 0x7fffffffLL) return PCT_NOT_COVERED;
+  const dim3 grid((unsigned)nblk), block(256);
+  const __bf16 *qc = static_cast<const __bf16 *>(q_c), *qs = static_cast<const __bf16 *>(q_s);
+  const __bf16 *kc = static_cast<const __bf16 *>(k_c), *kp = static_cast<const __bf16 *>(k_p);
+  const __bf16 *vv = static_cast<const __bf16 *>(v);
+  if (mask)
+    hipLaunchKernelGGL(cross_attention_ragged_kernel<true>, grid, block, 0, stream, qc, qs, kc, kp, vv, mask, row_open, N, heads, Q,
+                       S, mask_pitch, scale, tgroups, static_cast<__bf16 *>(out));
+  else
+    hipLaunchKernelGGL(cross_attention_ragged_kernel<false>, grid, block, 0, stream, qc, qs, kc, kp, vv, mask, row_open, N, heads, Q,
+                       S, 0, scale, tgroups, static_cast<__bf16 *>(out));
   return (int)hipGetLastError();
 }
 

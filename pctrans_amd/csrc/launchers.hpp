@@ -184,6 +184,11 @@ int launch_masked_attention(const void *q, const void *k, const void *vT, const 
 int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
                            const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S, float scale,
                            void *out, hipStream_t stream);
+// the same for any S >= 1 with mask rows mask_pitch bytes apart (cross_attention.hip; include/pctrans_hip_xattn.h).
+// PCT_NOT_COVERED: heads % 4 != 0 or an operand of 2^31 elements or more
+int launch_cross_attention_ragged(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
+                                  const unsigned char *mask, int mask_pitch, const unsigned char *row_open, int N, int heads,
+                                  int Q, int S, float scale, void *out, hipStream_t stream);
 // differentiable fp32 cross-attention (cross_attention_train.hip; include/pctrans_hip_attn_train.h).  PCT_NOT_COVERED: heads
 // outside {4, 8} or a tensor of 2^31 elements or more.  workspace: N * heads * Q floats
 int launch_cross_attention_fwd_f32(const float *q_c, const float *q_s, const float *k_c, const float *k_p, const float *v,

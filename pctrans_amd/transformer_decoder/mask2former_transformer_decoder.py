@@ -34,6 +34,7 @@ from torch.nn import functional as F
 from .. import attention_train
 from .. import dynamic_mask_head as dmh
 from .. import fused_ops
+from .. import ragged_attention
 from .. import reid_dice
 from .. import reid_query
 from .. import self_attention_train
@@ -152,6 +153,10 @@ class CrossAttentionLayer(nn.Module):
         # "hip": when a gradient is required, fp32 operands outside autocast go through the differentiable split-operand kernels
         # (attention_train.py) instead of the torch chain.  A plain attribute; process default from PCT_ATTN_TRAIN
         self.attn_train = attention_train.default()
+        # "hip": bf16 eval calls whose key count the split-operand kernel does not take (no multiple of 64) go through its ragged
+        # form (ragged_attention.py) instead of the concatenations, V^T and the generic kernel.  A plain attribute; process
+        # default from PCT_XATTN_RAGGED
+        self.ragged_keys = ragged_attention.default()
         _xavier_all(self)
 
     def forward_post(self, tgt, memory, memory_mask: Optional[Tensor] = None,
@@ -178,6 +183,11 @@ class CrossAttentionLayer(nn.Module):
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
         # the split-operand kernel takes the projections' outputs as they are: no per-head concatenation, no V^T
         split = fused and fused_ops.cross_attention_supported(q, k, k_pos, h, memory_mask)
+        if self.ragged_keys not in ("torch", "hip"):
+            raise ValueError("CrossAttentionLayer.ragged_keys must be 'torch' or 'hip', got %r" % (self.ragged_keys,))
+        # ... and so does its form for any key count, behind the switch
+        ragged = (fused and not split and self.ragged_keys == "hip"
+                  and ragged_attention.supported(q, k, k_pos, h, memory_mask))
         # the differentiable fp32 kernels take the projections' outputs, the mask and memory_row_open as they are, too
         train = (self.attn_train == "hip" and not fused and memory_key_padding_mask is None and torch.is_grad_enabled()
                  and k.is_cuda and k.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
@@ -187,10 +197,10 @@ class CrossAttentionLayer(nn.Module):
                  and C // h == 16 and self.cross_attn.dropout == 0.0
                  and (memory_mask is None or (memory_mask.dtype == torch.bool
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
-        if memory_row_open is not None and memory_mask is not None and not split and not train:
+        if memory_row_open is not None and memory_mask is not None and not split and not ragged and not train:
             memory_mask = memory_mask & ~memory_row_open
             memory_row_open = None
-        if fused and not split:
+        if fused and not split and not ragged:
             # V^T [N, C, HW] straight out of the projection GEMM (W . memory^T + b): the generic MFMA attention kernel reads
             # value rows per channel, so no [HW, N, C] -> [N, C, HW] transpose pass is needed
             w = self.ca_v_proj.weight
@@ -211,6 +221,9 @@ class CrossAttentionLayer(nn.Module):
             # per head [content (hd) | position (hd)] on both sides (:160-172), formed inside the kernel
             core = fused_ops.cross_attention(q, q_side, k, k_pos, v, h, memory_mask, row_open=memory_row_open)
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
+        if ragged and q.dtype == torch.bfloat16 and q_side.dtype == torch.bfloat16 and v.dtype == torch.bfloat16:
+            core = ragged_attention.cross_attention(q, q_side, k, k_pos, v, h, memory_mask, row_open=memory_row_open)
+            return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
         if train and attention_train.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
             core = attention_train.cross_attention_train(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
@@ -220,7 +233,7 @@ class CrossAttentionLayer(nn.Module):
         q = torch.cat([q.view(Q, bs, h, hd), q_side.view(Q, bs, h, hd)], dim=3).view(Q, bs, 2 * C)
         k = torch.cat([k.view(hw, bs, h, hd), k_pos.view(hw, bs, h, hd)], dim=3).view(hw, bs, 2 * C)
 
-        if fused and not split and q.dtype == torch.bfloat16 and v_t.dtype == torch.bfloat16:
+        if fused and not split and not ragged and q.dtype == torch.bfloat16 and v_t.dtype == torch.bfloat16:
             core = fused_ops.masked_attention(q, k, None, h, memory_mask, v_t=v_t)
             tgt2 = self.cross_attn.out_proj(core)
         else:
