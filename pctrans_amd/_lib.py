@@ -198,6 +198,16 @@ XATTN_SYMBOLS = {
                                         "tests/test_ragged_attention_gpu.py"),
 }
 
+# Entry points of the same cross-attention with the keys divided over several workgroups and a combine launch
+# (include/pctrans_hip_xattn_split.h; pctrans_amd/split_key_attention.py, reached with CrossAttentionLayer.split_keys = "hip").  A
+# table of its own, as the ragged entry's: name -> (argtypes, restype, the test module that checks the entry against that entry
+# and against float64)
+XATTN_SPLIT_SYMBOLS = {
+    "pct_cross_attention_split_keys_workspace": ([_i] * 4, ctypes.c_longlong, "tests/test_split_key_attention_gpu.py"),
+    "pct_cross_attention_split_keys_bf16": ([_vp] * 6 + [_i, _vp] + [_i] * 4 + [ctypes.c_float, _i, _vp, ctypes.c_longlong, _vp, _vp],
+                                            _i, "tests/test_split_key_attention_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -218,7 +228,8 @@ def lib():
             (k, v[:2]) for k, v in list(OPT_IN_SYMBOLS.items()) + list(POST_SYMBOLS.items()) + list(SEG_SYMBOLS.items())
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
             + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())
-            + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items()) + list(XATTN_SYMBOLS.items())]:
+            + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items()) + list(XATTN_SYMBOLS.items())
+            + list(XATTN_SPLIT_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

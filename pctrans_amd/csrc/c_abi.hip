@@ -1017,6 +1017,32 @@ int pct_cross_attention_ragged_bf16(const void *q_content, const void *q_pos, co
                                                        static_cast<hipStream_t>(stream)));
 }
 
+long long pct_cross_attention_split_keys_workspace(int batch, int heads, int num_query, int splits)
+{
+  if (batch < 0 || heads <= 0 || num_query < 0 || splits < 1 || splits > 16) return PCT_ERR_BAD_ARG;
+  if (heads % 4 != 0) return PCT_ERR_UNSUPPORTED;
+  return pct::cross_attention_split_keys_workspace(batch, heads, num_query, splits);
+}
+
+// the ragged entry's checks in its order; the launcher goes on with that launcher's coverage, then `splits` and the workspace
+int pct_cross_attention_split_keys_bf16(const void *q_content, const void *q_pos, const void *k_content, const void *k_pos,
+                                        const void *v, const unsigned char *mask, int mask_pitch, const unsigned char *row_open,
+                                        int batch, int heads, int num_query, int num_key, float scale, int splits, void *workspace,
+                                        long long workspace_bytes, void *out, void *stream)
+{
+  if (batch < 0 || heads <= 0 || num_query < 0 || num_key < 1) return PCT_ERR_BAD_ARG;
+  if (mask && (mask_pitch < num_key || mask_pitch % 16 != 0)) return PCT_ERR_BAD_ARG;
+  if (batch == 0 || num_query == 0) return PCT_OK;
+  if (!q_content || !q_pos || !k_content || !k_pos || !v || !out) return PCT_ERR_BAD_ARG;
+  if (((uintptr_t)q_content | (uintptr_t)q_pos | (uintptr_t)k_content | (uintptr_t)k_pos | (uintptr_t)v | (uintptr_t)mask) & 15u)
+    return PCT_ERR_ALIGNMENT;
+  if ((uintptr_t)out & 7u) return PCT_ERR_ALIGNMENT;
+  return abi_status(pct::launch_cross_attention_split_keys(q_content, q_pos, k_content, k_pos, v, mask, mask ? mask_pitch : 0,
+                                                           mask ? row_open : nullptr, batch, heads, num_query, num_key, scale,
+                                                           splits, workspace, workspace_bytes, out,
+                                                           static_cast<hipStream_t>(stream)));
+}
+
 // The argument checks of the four differentiable fp32 attention entries, in the order the ABI fixes: a negative size or no head,
 // the empty call (nothing is read, every pointer may be null), a null pointer, a pointer off 16 bytes (self-attention:
 // num_key = num_query).  -> true: launch; false: return *status.

@@ -54,14 +54,28 @@ struct XaShared {
 
 // NT: the query tiles this workgroup's waves carry (1 .. XA_T; compile time, so that the tiles' chains are straight-line code
 // the scheduler can interleave -- with a run-time count each tile became its own basic block)
-template <bool HAS_MASK, bool RAGGED, int NT>
+// PARTIAL (RAGGED only; pct_cross_attention_split_keys_bf16): the grid holds `splits` workgroups for every workgroup of the plain
+// grid, next to each other's tile groups (block order: image, head group, split, tile group -- the tile groups of one split are
+// adjacent and share its K / V lines in L2).  Split j walks the chunks [xa_split_begin(j), xa_split_begin(j + 1)) with the same
+// staging, steps and tail rules -- `ch` stays the call's absolute chunk index, so a ragged tail can only sit in the last split --
+// and its epilogue does not divide: o (still relative to m_run), m_run and l_run of every live query row go to the workspace
+//   o [splits][N][heads][Q][16] fp32 | m [splits][N][heads][Q] fp32 | l [splits][N][heads][Q] fp32
+// for cross_attention_combine_kernel.  A wave's store of one tile's o is 1 KB contiguous; m and l come from the g == 0 lanes.
+__host__ __device__ __forceinline__ int xa_split_begin(const int j, const int nch, const int splits)
+{
+  return (int)((long long)j * nch / splits);             // the one statement of the rule (split_key_attention.chunk_ranges)
+}
+
+template <bool HAS_MASK, bool RAGGED, int NT, bool PARTIAL = false>
 __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 *__restrict__ q_c, const __bf16 *__restrict__ q_s,
                                                      const __bf16 *__restrict__ k_c, const __bf16 *__restrict__ k_p,
                                                      const __bf16 *__restrict__ v, const unsigned char *__restrict__ mask,
                                                      const unsigned char *__restrict__ row_open, const int N, const int heads,
                                                      const int Q, const int S, const int mask_pitch, const float scale,
-                                                     const int tgroups, __bf16 *__restrict__ out)
+                                                     const int tgroups, __bf16 *__restrict__ out, const int splits = 1,
+                                                     float *__restrict__ ws = nullptr)
 {
+  static_assert(RAGGED || !PARTIAL, "the partial kernel is built on the ragged rules");
   auto &sKc = sh.sKc;
   auto &sKp = sh.sKp;
   auto &sV = sh.sV;
@@ -72,8 +86,15 @@ __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 
   const int hgroups = heads / XA_HG;
   const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
   const int tg = (int)(lb % (unsigned)tgroups);
-  const int hg = (int)((lb / (unsigned)tgroups) % (unsigned)hgroups);
-  const int n = (int)(lb / (unsigned)(tgroups * hgroups));
+  int hg, n, split = 0;
+  if constexpr (PARTIAL) {
+    split = (int)((lb / (unsigned)tgroups) % (unsigned)splits);
+    hg = (int)((lb / (unsigned)(tgroups * splits)) % (unsigned)hgroups);
+    n = (int)(lb / (unsigned)(tgroups * splits * hgroups));
+  } else {
+    hg = (int)((lb / (unsigned)tgroups) % (unsigned)hgroups);
+    n = (int)(lb / (unsigned)(tgroups * hgroups));
+  }
   const int h = hg * XA_HG + wave;
   const int tile0 = tg * XA_T;
 
@@ -167,12 +188,17 @@ __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 
   const int m_rot = 2 * (col >> 1);
 
   const int nch = RAGGED ? (S + XA_CH - 1) / XA_CH : S / XA_CH;
-  fetch(0);
+  int c0 = 0, c1 = nch;                                  // this workgroup's chunks
+  if constexpr (PARTIAL) {
+    c0 = xa_split_begin(split, nch, splits);
+    c1 = xa_split_begin(split + 1, nch, splits);
+  }
+  fetch(c0 * XA_CH);
   stash(0);
   __syncthreads();
-  if (nch > 1) fetch(XA_CH);
-  for (int ch = 0; ch < nch; ++ch) {
-    const int buf = ch & 1;
+  if (c0 + 1 < c1) fetch((c0 + 1) * XA_CH);
+  for (int ch = c0; ch < c1; ++ch) {
+    const int buf = (ch - c0) & 1;
     const unsigned char *kt = reinterpret_cast<const unsigned char *>(g < 2 ? sKc[buf] : sKp[buf]);
     const unsigned char *vt = reinterpret_cast<const unsigned char *>(sV[buf]);
 #pragma unroll
@@ -209,11 +235,30 @@ __device__ __forceinline__ void cross_attention_body(XaShared &sh, const __bf16 
         attn_step(a0, a1, qb[t], va, mA, mB, scale, o[t], m_run[t], l_run[t]);
       }
     }
-    if (ch + 1 < nch) {
+    if (ch + 1 < c1) {
       stash(buf ^ 1);               // (everyone left that buffer before the barrier that ended the previous chunk)
       __syncthreads();
-      if (ch + 2 < nch) fetch((ch + 2) * XA_CH);
+      if (ch + 2 < c1) fetch((ch + 2) * XA_CH);
     }
+  }
+
+  if constexpr (PARTIAL) {
+    // record of (split, image, head, query): every live query of every (split, image, head) is written by exactly one lane
+    // group here, so the combine reads no word this call has not written
+    const size_t rows = (size_t)splits * N * heads * Q;
+    const size_t row0 = (((size_t)split * N + n) * heads + h) * Q;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int qo = (tile0 + t) * 16 + col;
+      if (qo < Q) {
+        *reinterpret_cast<f32x4 *>(ws + (row0 + qo) * 16 + 4 * g) = o[t];
+        if (g == 0) {
+          ws[rows * 16 + row0 + qo] = m_run[t];
+          ws[rows * 17 + row0 + qo] = l_run[t];
+        }
+      }
+    }
+    return;
   }
 
 #pragma unroll
@@ -269,6 +314,69 @@ __global__ __launch_bounds__(256, 2) void cross_attention_ragged_kernel(
 #undef PCT_XA_RAGGED
 }
 
+// the PARTIAL form: the ragged kernel's workgroup, dispatch and LDS image on the chunks of one split
+template <bool HAS_MASK>
+__global__ __launch_bounds__(256, 2) void cross_attention_partial_kernel(
+    const __bf16 *__restrict__ q_c, const __bf16 *__restrict__ q_s, const __bf16 *__restrict__ k_c, const __bf16 *__restrict__ k_p,
+    const __bf16 *__restrict__ v, const unsigned char *__restrict__ mask, const unsigned char *__restrict__ row_open, const int N,
+    const int heads, const int Q, const int S, const int mask_pitch, const float scale, const int tgroups, const int splits,
+    float *__restrict__ ws)
+{
+  __shared__ __attribute__((aligned(16))) XaShared sh;
+  const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+  const int tg = (int)(lb % (unsigned)tgroups);
+  const int ntile = min(XA_T, (Q + 15) / 16 - tg * XA_T);            // uniform over the workgroup
+  static_assert(XA_T == 4, "dispatch below");
+#define PCT_XA_PARTIAL(NT_)                                                                                                      \
+  cross_attention_body<HAS_MASK, true, NT_, true>(sh, q_c, q_s, k_c, k_p, v, mask, row_open, N, heads, Q, S, mask_pitch, scale, \
+                                                  tgroups, nullptr, splits, ws)
+  if (ntile == 4) PCT_XA_PARTIAL(4);
+  else if (ntile == 3) PCT_XA_PARTIAL(3);
+  else if (ntile == 2) PCT_XA_PARTIAL(2);
+  else PCT_XA_PARTIAL(1);
+#undef PCT_XA_PARTIAL
+}
+
+// One thread per (query, image, head, 4 channels), in the order of `out`.  M = max_j m_j; w_j = exp(m_j - M), 0 for a split
+// that saw no live key (m_j = -inf: its o_j and l_j are 0); L = sum_j w_j l_j and O = sum_j w_j o_j in ascending j, starting
+// from the j = 0 term; out = bf16(O * (1 / L)).  No live key in any split: L = 0 and 0 * inf = NaN, as the kernels above.
+__global__ __launch_bounds__(256) void cross_attention_combine_kernel(const float *__restrict__ ws, const int N, const int heads,
+                                                                      const int Q, const int splits, __bf16 *__restrict__ out)
+{
+  const size_t per_split = (size_t)N * heads * Q, rows = per_split * splits;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= per_split * 4) return;
+  const int g = (int)(idx & 3);
+  const int h = (int)((idx >> 2) % (unsigned)heads);
+  const int n = (int)((idx / ((size_t)4 * heads)) % (unsigned)N);
+  const int qo = (int)(idx / ((size_t)4 * heads * N));
+  const size_t row0 = ((size_t)n * heads + h) * Q + qo;
+  const float *ws_m = ws + rows * 16, *ws_l = ws + rows * 17;
+  float M = -INFINITY;
+  for (int j = 0; j < splits; ++j) M = fmaxf(M, ws_m[row0 + j * per_split]);
+  f32x4 O = {0.f, 0.f, 0.f, 0.f};
+  float L = 0.f;
+  for (int j = 0; j < splits; ++j) {
+    const size_t row = row0 + j * per_split;
+    const float m = ws_m[row];
+    const float w = m == -INFINITY ? 0.f : __expf(m - M);
+    const f32x4 oj = *reinterpret_cast<const f32x4 *>(ws + row * 16 + 4 * g);
+    const float lj = ws_l[row];
+    if (j == 0) {
+      L = w * lj;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) O[r] = w * oj[r];
+    } else {
+      L += w * lj;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) O[r] += w * oj[r];
+    }
+  }
+  const float inv = 1.0f / L;
+  const bf16x4 r = {(__bf16)(O[0] * inv), (__bf16)(O[1] * inv), (__bf16)(O[2] * inv), (__bf16)(O[3] * inv)};
+  *reinterpret_cast<bf16x4 *>(out + idx * 4) = r;
+}
+
 // PCT_NOT_COVERED: geometry not covered (the caller concatenates the halves and uses pct_masked_attention_bf16)
 int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
                            const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S,
@@ -321,6 +429,50 @@ int launch_cross_attention_ragged(const void *q_c, const void *q_s, const void *
   else
     hipLaunchKernelGGL(cross_attention_ragged_kernel<false>, grid, block, 0, stream, qc, qs, kc, kp, vv, mask, row_open, N, heads, Q,
                        S, 0, scale, tgroups, static_cast<__bf16 *>(out));
+  return (int)hipGetLastError();
+}
+
+long long cross_attention_split_keys_workspace(int N, int heads, int Q, int splits)
+{
+  return splits <= 1 ? 0 : (long long)splits * N * heads * Q * 18 * (long long)sizeof(float);
+}
+
+int launch_cross_attention_split_keys(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
+                                      const unsigned char *mask, int mask_pitch, const unsigned char *row_open, int N, int heads,
+                                      int Q, int S, float scale, int splits, void *workspace, long long workspace_bytes, void *out,
+                                      hipStream_t stream)
+{
+  // what launch_cross_attention_ragged answers first, in its order
+  if (heads <= 0 || heads % XA_HG != 0 || S <= 0) return PCT_NOT_COVERED;
+  if (N == 0 || Q == 0) return 0;
+  if ((long long)S * N * heads * 16 >= 0x7fffffffLL || (long long)Q * N * heads * 16 >= 0x7fffffffLL) return PCT_NOT_COVERED;
+  if ((((uintptr_t)q_c | (uintptr_t)q_s | (uintptr_t)k_c | (uintptr_t)k_p | (uintptr_t)v) & 15u) || ((uintptr_t)out & 7u)) return PCT_NOT_COVERED;
+  if (mask && (((uintptr_t)mask & 15u) || (mask_pitch & 15) || mask_pitch < S)) return PCT_NOT_COVERED;
+  const int nch = (S + XA_CH - 1) / XA_CH;
+  if (splits < 1 || splits > 16 || splits > nch) return PCT_ERR_BAD_ARG;
+  if (splits == 1)
+    return launch_cross_attention_ragged(q_c, q_s, k_c, k_p, v, mask, mask_pitch, row_open, N, heads, Q, S, scale, out, stream);
+  if (!workspace || workspace_bytes < cross_attention_split_keys_workspace(N, heads, Q, splits)) return PCT_ERR_BAD_ARG;
+  if ((uintptr_t)workspace & 15u) return PCT_ERR_ALIGNMENT;
+  const int qtiles = (Q + 15) / 16, tgroups = (qtiles + XA_T - 1) / XA_T;
+  const long long nblk = (long long)N * (heads / XA_HG) * splits * tgroups;
+  if (nblk > 0x7fffffffLL) return PCT_NOT_COVERED;
+  const dim3 grid((unsigned)nblk), block(256);
+  const __bf16 *qc = static_cast<const __bf16 *>(q_c), *qs = static_cast<const __bf16 *>(q_s);
+  const __bf16 *kc = static_cast<const __bf16 *>(k_c), *kp = static_cast<const __bf16 *>(k_p);
+  const __bf16 *vv = static_cast<const __bf16 *>(v);
+  float *ws = static_cast<float *>(workspace);
+  if (mask)
+    hipLaunchKernelGGL(cross_attention_partial_kernel<true>, grid, block, 0, stream, qc, qs, kc, kp, vv, mask, row_open, N, heads, Q,
+                       S, mask_pitch, scale, tgroups, splits, ws);
+  else
+    hipLaunchKernelGGL(cross_attention_partial_kernel<false>, grid, block, 0, stream, qc, qs, kc, kp, vv, mask, row_open, N, heads, Q,
+                       S, 0, scale, tgroups, splits, ws);
+  int rc = (int)hipGetLastError();
+  if (rc != 0) return rc;
+  const long long threads = (long long)Q * N * heads * 4;             // < 2^29 by the element limit above
+  hipLaunchKernelGGL(cross_attention_combine_kernel, dim3((unsigned)((threads + 255) / 256)), block, 0, stream, ws, N, heads, Q,
+                     splits, static_cast<__bf16 *>(out));
   return (int)hipGetLastError();
 }
 

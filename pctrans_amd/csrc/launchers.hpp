@@ -189,6 +189,16 @@ int launch_cross_attention(const void *q_c, const void *q_s, const void *k_c, co
 int launch_cross_attention_ragged(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
                                   const unsigned char *mask, int mask_pitch, const unsigned char *row_open, int N, int heads,
                                   int Q, int S, float scale, void *out, hipStream_t stream);
+// the same with the keys of every workgroup of that grid divided over `splits` workgroups, and a combine launch
+// (cross_attention.hip; include/pctrans_hip_xattn_split.h).  splits == 1: launch_cross_attention_ragged.  After that launcher's
+// PCT_NOT_COVERED and empty-call answers: PCT_ERR_BAD_ARG for splits outside 1 .. min(16, ceil(S / 64)) or, with splits >= 2, a
+// null or too small workspace; PCT_ERR_ALIGNMENT for a workspace off 16 bytes
+int launch_cross_attention_split_keys(const void *q_c, const void *q_s, const void *k_c, const void *k_p, const void *v,
+                                      const unsigned char *mask, int mask_pitch, const unsigned char *row_open, int N, int heads,
+                                      int Q, int S, float scale, int splits, void *workspace, long long workspace_bytes, void *out,
+                                      hipStream_t stream);
+// bytes of that workspace: splits * N * heads * Q records of 16 + 1 + 1 floats (0 for splits == 1)
+long long cross_attention_split_keys_workspace(int N, int heads, int Q, int splits);
 // differentiable fp32 cross-attention (cross_attention_train.hip; include/pctrans_hip_attn_train.h).  PCT_NOT_COVERED: heads
 // outside {4, 8} or a tensor of 2^31 elements or more.  workspace: N * heads * Q floats
 int launch_cross_attention_fwd_f32(const float *q_c, const float *q_s, const float *k_c, const float *k_p, const float *v,

@@ -35,6 +35,7 @@ from .. import attention_train
 from .. import dynamic_mask_head as dmh
 from .. import fused_ops
 from .. import ragged_attention
+from .. import split_key_attention
 from .. import reid_dice
 from .. import reid_query
 from .. import self_attention_train
@@ -157,6 +158,10 @@ class CrossAttentionLayer(nn.Module):
         # form (ragged_attention.py) instead of the concatenations, V^T and the generic kernel.  A plain attribute; process
         # default from PCT_XATTN_RAGGED
         self.ragged_keys = ragged_attention.default()
+        # "hip": bf16 eval calls on grids too small to fill the device (split_key_attention.plan) divide their keys over several
+        # workgroups and combine the partial results in a second launch (split_key_attention.py), whatever the key count.  A
+        # plain attribute; process default from PCT_XATTN_SPLIT_KEYS
+        self.split_keys = split_key_attention.default()
         _xavier_all(self)
 
     def forward_post(self, tgt, memory, memory_mask: Optional[Tensor] = None,
@@ -181,12 +186,16 @@ class CrossAttentionLayer(nn.Module):
                  and C // h == 16 and self.cross_attn.dropout == 0.0
                  and (memory_mask is None or (memory_mask.dtype == torch.bool
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
+        if self.split_keys not in ("torch", "hip"):
+            raise ValueError("CrossAttentionLayer.split_keys must be 'torch' or 'hip', got %r" % (self.split_keys,))
+        # small grids, behind the switch: the keys of a workgroup divided over several, then a combine launch
+        splitk = fused and self.split_keys == "hip" and split_key_attention.supported(q, k, k_pos, h, memory_mask)
         # the split-operand kernel takes the projections' outputs as they are: no per-head concatenation, no V^T
-        split = fused and fused_ops.cross_attention_supported(q, k, k_pos, h, memory_mask)
+        split = fused and not splitk and fused_ops.cross_attention_supported(q, k, k_pos, h, memory_mask)
         if self.ragged_keys not in ("torch", "hip"):
             raise ValueError("CrossAttentionLayer.ragged_keys must be 'torch' or 'hip', got %r" % (self.ragged_keys,))
         # ... and so does its form for any key count, behind the switch
-        ragged = (fused and not split and self.ragged_keys == "hip"
+        ragged = (fused and not split and not splitk and self.ragged_keys == "hip"
                   and ragged_attention.supported(q, k, k_pos, h, memory_mask))
         # the differentiable fp32 kernels take the projections' outputs, the mask and memory_row_open as they are, too
         train = (self.attn_train == "hip" and not fused and memory_key_padding_mask is None and torch.is_grad_enabled()
@@ -197,10 +206,10 @@ class CrossAttentionLayer(nn.Module):
                  and C // h == 16 and self.cross_attn.dropout == 0.0
                  and (memory_mask is None or (memory_mask.dtype == torch.bool
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
-        if memory_row_open is not None and memory_mask is not None and not split and not ragged and not train:
+        if memory_row_open is not None and memory_mask is not None and not split and not ragged and not splitk and not train:
             memory_mask = memory_mask & ~memory_row_open
             memory_row_open = None
-        if fused and not split and not ragged:
+        if fused and not split and not ragged and not splitk:
             # V^T [N, C, HW] straight out of the projection GEMM (W . memory^T + b): the generic MFMA attention kernel reads
             # value rows per channel, so no [HW, N, C] -> [N, C, HW] transpose pass is needed
             w = self.ca_v_proj.weight
@@ -224,6 +233,9 @@ class CrossAttentionLayer(nn.Module):
         if ragged and q.dtype == torch.bfloat16 and q_side.dtype == torch.bfloat16 and v.dtype == torch.bfloat16:
             core = ragged_attention.cross_attention(q, q_side, k, k_pos, v, h, memory_mask, row_open=memory_row_open)
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
+        if splitk and q.dtype == torch.bfloat16 and q_side.dtype == torch.bfloat16 and v.dtype == torch.bfloat16:
+            core = split_key_attention.cross_attention(q, q_side, k, k_pos, v, h, memory_mask, row_open=memory_row_open)
+            return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
         if train and attention_train.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
             core = attention_train.cross_attention_train(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
@@ -233,7 +245,7 @@ class CrossAttentionLayer(nn.Module):
         q = torch.cat([q.view(Q, bs, h, hd), q_side.view(Q, bs, h, hd)], dim=3).view(Q, bs, 2 * C)
         k = torch.cat([k.view(hw, bs, h, hd), k_pos.view(hw, bs, h, hd)], dim=3).view(hw, bs, 2 * C)
 
-        if fused and not split and not ragged and q.dtype == torch.bfloat16 and v_t.dtype == torch.bfloat16:
+        if fused and not split and not ragged and not splitk and q.dtype == torch.bfloat16 and v_t.dtype == torch.bfloat16:
             core = fused_ops.masked_attention(q, k, None, h, memory_mask, v_t=v_t)
             tgt2 = self.cross_attn.out_proj(core)
         else:
