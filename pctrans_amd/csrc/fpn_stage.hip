@@ -9,7 +9,8 @@
 // convolution and its affine are linear the mean is taken FIRST -- the 1x1 GEMM runs on a quarter of the pixels and the first
 // kernel is bound by reading x once.
 //
-// Arithmetic: split_bf16.hpp -- every fp32 operand is exactly three bf16 numbers, a product is its six leading terms on
+// Arithmetic: split_bf16.hpp -- every fp32 operand is exactly three bf16 numbers (for 2^-110 <= |a| < 0x7F7F8000 and zero; an
+// operand above makes the outputs it reaches NaN, and the ReLU passes a NaN on), a product is its six leading terms on
 // v_mfma_f32_32x32x16_bf16, the w1 a1 chain and the five small terms in accumulators of their own (hi / lo), summed once.
 //
 // fpn_lateral_kernel: workgroup (4 waves) = (image, 4 rows x 32 columns of the output map), all 128 output channels; per step of
@@ -310,7 +311,7 @@ __global__ __launch_bounds__(FP_BLOCK, 2) void fpn_output_kernel(
         for (int t = 0; t < 4; ++t) {
           const int co = co_half * 64 + rb * 32 + 8 * q + 4 * h + t;
           const f32x2 c = aff[co];
-          on[(size_t)co * HWp + pix] = fmaxf(fmaf(c[0], acc.sum(rb, cb, 4 * q + t), c[1]), 0.f);
+          on[(size_t)co * HWp + pix] = relu_keep_nan(fmaf(c[0], acc.sum(rb, cb, 4 * q + t), c[1]));
         }
   }
 }

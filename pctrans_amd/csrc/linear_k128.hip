@@ -184,7 +184,7 @@ __global__ __launch_bounds__(LIN_BLOCK, 2) void linear_k128_kernel(
       for (int j = 0; j < 16; ++j) v[j] = v[j] * stat[8 * (j / 4) + 4 * h + (j % 4)] * gcol + becol;
     } else if constexpr (EPI == LIN_EPI_BIAS_RELU) {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = fmaxf(v[j], 0.f);
+      for (int j = 0; j < 16; ++j) v[j] = relu_keep_nan(v[j]);
     }
     const auto ry = tile_rsrc(Y, ldy, tile);
 #pragma unroll

@@ -3,7 +3,8 @@
 // reference lines as linear_k128.hip (ops/modules/ms_deform_attn.py:64-67,96-110; pixel_decoder/msdeformattn.py:100-131).
 //
 // Why: these GEMMs are bound by the fp32 MFMA rate (157 TFLOP/s peak; linear_k128.hip sustains 123), while the bf16
-// MFMA rate is 16x that.  Every fp32 number is EXACTLY the sum of three bf16 numbers
+// MFMA rate is 16x that.  Every fp32 number with 2^-110 <= |a| < 0x7F7F8000 (and zero; split_bf16.hpp has the two ends: bits
+// under 2^-133 lost below, a NaN row above) is EXACTLY the sum of three bf16 numbers
 //     a = a1 + a2 + a3,   a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)
 // (round-to-nearest leaves a residual below half an ulp of the 8-bit piece, so each piece contributes 9 bits: 27 >= 24;
 // both subtractions are exact in fp32).  A product a·w = sum_ij ai·wj is therefore evaluated from its six leading terms
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
               v[t] = (ahi[cw][rx][t] + alo[cw][rx][t]) + bvec[cw][t];
-              if constexpr (EPI == SPL_EPI_BIAS_RELU) v[t] = fmaxf(v[t], 0.f);
+              if constexpr (EPI == SPL_EPI_BIAS_RELU) v[t] = relu_keep_nan(v[t]);
             }
             *reinterpret_cast<f32x4 *>(sw + (16 * rx + (lane & 15)) * SPL_OLD + 16 * cw + 4 * (lane >> 4)) = v;
           }
@@ -383,7 +384,7 @@ __global__ __launch_bounds__(SPL_BLOCK, 2) void linear_k128_split_kernel(
         }
       } else if constexpr (EPI == SPL_EPI_BIAS_RELU) {
 #pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = fmaxf(v[j], 0.f);
+        for (int j = 0; j < 16; ++j) v[j] = relu_keep_nan(v[j]);
       }
       const auto ry = tile_rsrc(Y, ldy, active ? tile : ntiles);   // a wave past n stores nothing
       // through the wave's own LDS scratch (in-order DS ops of one wave: no barrier): the accumulator layout has a

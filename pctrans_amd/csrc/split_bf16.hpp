@@ -1,6 +1,9 @@
 // The split-bf16 arithmetic of the encoder's GEMMs (linear_k128_split.hip, linear_ln_split.hip, ffn_fused_split.hip,
-// conv1x1_split.hip), stated once.  Every fp32 number is EXACTLY the sum of three bf16 numbers
+// conv1x1_split.hip), stated once.  An fp32 number with 2^-110 <= |a| < 0x7F7F8000 (3.396e38), or zero, is EXACTLY the sum of
+// three bf16 numbers
 //     a = a1 + a2 + a3,   a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2)
+// (below 2^-110 the bits of a under 2^-133, the last bf16 subnormal, can be lost; from 0x7F7F8000 on a1 rounds to inf and
+// a2 = -inf, a3 = NaN: like an inf or a NaN, such an operand makes its whole output row NaN; tests/split_gemm_hard_inputs.py)
 // and a product a.w is evaluated from its six leading partial products on the bf16 matrix cores with fp32 accumulation
 // (linear_k128_split.hip has the error analysis).  Staging layouts and epilogues stay with the kernels; what they share is
 // the split, the order of the six products, the vector types and the wave's 2 x 2 accumulator tile -- the GEMMs agree bit for
@@ -106,6 +109,10 @@ struct SplitTile2x2 {
   // element j of block (rb, cb): the one addition of hi and lo
   __device__ __forceinline__ float sum(const int rb, const int cb, const int j) const { return hi[rb][cb][j] + lo[rb][cb][j]; }
 };
+
+// ReLU of the bias / ReLU epilogues: a NaN passes through as in torch.relu (fmaxf(v, 0.f) returns 0 for it, so a NaN of the
+// product would vanish from the output); every other v, -0 included, gives the bits fmaxf gave
+__device__ __forceinline__ float relu_keep_nan(const float v) { return (v > 0.f || v != v) ? v : 0.f; }
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v)
