@@ -216,6 +216,8 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_xattn.h"
 /* the same with the keys divided over several workgroups and a combine step, behind CrossAttentionLayer.split_keys = "hip" */
 #include "pctrans_hip_xattn_split.h"
+/* small-object merging of label maps (the trainer's merge_func), behind pctrans_amd.label_merge and MaskFormer.test_labels */
+#include "pctrans_hip_merge.h"
 
 /* ---- fused residual add + LayerNorm:  out = LayerNorm(x + y) * gamma + beta  over the last dimension ----------
  * Replaces the `x + dropout(y)` / `nn.LayerNorm` pairs of the encoder and decoder layers in eval mode

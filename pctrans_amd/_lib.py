@@ -208,6 +208,13 @@ XATTN_SPLIT_SYMBOLS = {
                                             _i, "tests/test_split_key_attention_gpu.py"),
 }
 
+# Entry point of the small-object merging of label maps (include/pctrans_hip_merge.h; pctrans_amd/label_merge.py:
+# merge_small_objects, MaskFormer.test_labels).  A table of its own, as the metrics': name -> (argtypes, restype, the test module
+# that checks the entry -- against the table-based restatement of the reference's merge_func: the outputs are exact)
+MERGE_SYMBOLS = {
+    "pct_label_merge_small": ([_vp, _i, _vp, _i, _i, _i, _vp, _i] + [_vp] * 10, _i, "tests/test_label_merge_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -229,7 +236,7 @@ def lib():
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
             + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())
             + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items()) + list(XATTN_SYMBOLS.items())
-            + list(XATTN_SPLIT_SYMBOLS.items())]:
+            + list(XATTN_SPLIT_SYMBOLS.items()) + list(MERGE_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from .. import label_merge as _label_merge
 from .. import metrics as _metrics
 from .. import postprocess as post
 from .. import targets as _targets
@@ -164,19 +165,36 @@ class MaskFormer(nn.Module):
             instance_discriminative=instance_discriminative, ignore_label=ignore_label, device=next(self.parameters()).device)
 
     @torch.no_grad()
-    def validation_metrics(self, volume, gt_labels, fg=None):
+    def validation_metrics(self, volume, gt_labels, fg=None, merge=False):
         """The reference trainer's validation step for one batch (connectomics/engine/trainer.py:398-450 for CVPPP, :497-573 for
         BBBC) without its host copies: the eval forward, then pctrans_amd.metrics.instance_metrics for `self.dataset_name` on
         the label maps `forward` returns -- with `postprocess == "hip"` those of post.instance_labels, still on the device --
         against `gt_labels` [N, H, W].  `fg`: the trainer's foreground map (the prediction is scored as `labels * fg`).
+        `merge=True`: the scored maps are those of `test_labels`, the gated maps after the trainer's merge_func (the call it
+        has commented out at :423-424).
         -> Metrics (a dict of [N] tensors with `.status`), carrying the scored label maps as `.labels`.  Call in eval mode."""
         if self.training:
             raise RuntimeError("validation_metrics runs the eval forward: call model.eval() first")
-        labels, _ = self.forward(volume)
+        if merge:
+            labels = self.test_labels(volume, fg)
+            fg = None                               # (the gate is in the merged maps)
+        else:
+            labels, _ = self.forward(volume)
         gt_labels = gt_labels.to(labels.device)
         out = _metrics.instance_metrics(labels, gt_labels, self.dataset_name, None if fg is None else fg.to(labels.device))
         out.labels = labels
         return out
+
+    @torch.no_grad()
+    def test_labels(self, volume, fg=None, passes=_label_merge.PASSES):
+        """The body of the reference trainer's test loop for one batch (connectomics/engine/trainer.py:452-495, test_cvppp)
+        without its host copy: the eval forward, `seg_outputs * fg`, then merge_func (:744-777) as
+        pctrans_amd.label_merge.merge_small_objects -- on the device kernels by default (PCT_LABEL_MERGE).  -> the merged label
+        maps [N, H, W], carrying `.status`, `.final`, `.values`, `.merges` and `.mode` (see that module).  Call in eval mode."""
+        if self.training:
+            raise RuntimeError("test_labels runs the eval forward: call model.eval() first")
+        labels, _ = self.forward(volume)
+        return _label_merge.merge_small_objects(labels, None if fg is None else fg.to(labels.device) != 0, passes)
 
     def forward(self, volume, targets=None, train=False):
         features = self.backbone(volume)

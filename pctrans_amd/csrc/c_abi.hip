@@ -820,6 +820,25 @@ int pct_label_metrics(const int32_t *values, const int32_t *areas, const int32_t
   return pct::launch_label_metrics(values, areas, num, range, table, batch, metrics, counts, static_cast<hipStream_t>(stream));
 }
 
+int pct_label_merge_small(const void *labels, int dtype, const uint8_t *fg, int batch, int height, int width,
+                          const int32_t *passes, int num_passes, void *workspace, void *out, int32_t *values, int32_t *final,
+                          int32_t *areas_before, int32_t *areas_after, int32_t *num, int32_t *merges, int32_t *status,
+                          void *stream)
+{
+  const int rc = pct::label_merge_status(dtype, batch, height, width, passes, num_passes);
+  if (rc != PCT_OK) return rc;
+  if (!labels || !workspace || !out || !values || !final || !areas_before || !areas_after || !num || !merges || !status)
+    return PCT_ERR_BAD_ARG;
+  static const uintptr_t elem[5] = {1, 2, 4, 8, 4};
+  if ((((uintptr_t)labels | (uintptr_t)out) & (elem[dtype] - 1)) ||
+      (((uintptr_t)values | (uintptr_t)final | (uintptr_t)areas_before | (uintptr_t)areas_after | (uintptr_t)num |
+        (uintptr_t)merges | (uintptr_t)status) & 3u) ||
+      ((uintptr_t)workspace & 15u))
+    return PCT_ERR_ALIGNMENT;
+  return pct::launch_label_merge_small(labels, dtype, fg, batch, height, width, passes, num_passes, workspace, out, values, final,
+                                       areas_before, areas_after, num, merges, status, static_cast<hipStream_t>(stream));
+}
+
 int pct_add_layernorm_f32(const float *x, const float *y, const float *gamma, const float *beta, float eps,
                           long long rows, int cols, float *out, void *stream)
 {

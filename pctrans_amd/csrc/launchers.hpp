@@ -320,6 +320,14 @@ int launch_label_overlap(const void *pred, int pred_dtype, const void *gt, int g
 int launch_label_metrics(const int *values, const int *areas, const int *num, const int *range, const int *table, int N,
                          double *metrics, int *counts, hipStream_t stream);
 
+// ---- small-object merging of label maps (label_merge.hip; include/pctrans_hip_merge.h).  dtype codes as the instance targets';
+// `passes` [num_passes, 2] (threshold, window) in host memory.  PCT_ERR_BAD_ARG for wrong passes, PCT_ERR_UNSUPPORTED for a
+// geometry the kernels do not cover, both before any launch ----------------------------------------------------------------
+int label_merge_status(int dtype, int N, int H, int W, const int *passes, int num_passes);
+int launch_label_merge_small(const void *labels, int dtype, const uint8_t *fg, int N, int H, int W, const int *passes,
+                             int num_passes, void *workspace, void *out, int *values, int *final_, int *areas_before,
+                             int *areas_after, int *num, int *merges, int *status, hipStream_t stream);
+
 // ---- instance post-processing (instance_post.hip; include/pctrans_hip_post.h).  dataset: 0 = CVPPP, 1 = BBBC -----------------
 int instance_geometry_status(int N, int Q, int H, int W);     // PCT_OK or PCT_ERR_UNSUPPORTED
 int launch_instance_masks(const void *logits, int bf16, int N, int Q, int h, int w, int H, int W, int dataset, unsigned *bits,
