@@ -218,6 +218,9 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_xattn_split.h"
 /* small-object merging of label maps (the trainer's merge_func), behind pctrans_amd.label_merge and MaskFormer.test_labels */
 #include "pctrans_hip_merge.h"
+/* the decoder's cross- and self-attention in fp32 evaluation, behind CrossAttentionLayer.attn_eval and
+ * SelfAttentionLayer.attn_eval = "hip" */
+#include "pctrans_hip_attn_eval.h"
 
 /* ---- fused residual add + LayerNorm:  out = LayerNorm(x + y) * gamma + beta  over the last dimension ----------
  * Replaces the `x + dropout(y)` / `nn.LayerNorm` pairs of the encoder and decoder layers in eval mode

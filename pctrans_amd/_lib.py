@@ -215,6 +215,14 @@ MERGE_SYMBOLS = {
     "pct_label_merge_small": ([_vp, _i, _vp, _i, _i, _i, _vp, _i] + [_vp] * 10, _i, "tests/test_label_merge_gpu.py"),
 }
 
+# Entry points of the decoder's attention in fp32 evaluation (include/pctrans_hip_attn_eval.h; pctrans_amd/attention_eval.py,
+# reached with CrossAttentionLayer.attn_eval / SelfAttentionLayer.attn_eval = "hip").  A table of its own, as the merge's:
+# name -> (argtypes, restype, the test module that checks the entry -- against the training forwards, bit for bit, and float64)
+ATTN_EVAL_SYMBOLS = {
+    "pct_cross_attention_eval_f32": ([_vp] * 7 + [_i] * 4 + [ctypes.c_float, _vp, _vp], _i, "tests/test_attention_eval_gpu.py"),
+    "pct_self_attention_eval_f32": ([_vp] * 5 + [_i] * 3 + [ctypes.c_float, _vp, _vp], _i, "tests/test_attention_eval_gpu.py"),
+}
+
 
 class PctransLibraryError(RuntimeError):
     pass
@@ -236,7 +244,7 @@ def lib():
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
             + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())
             + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items()) + list(XATTN_SYMBOLS.items())
-            + list(XATTN_SPLIT_SYMBOLS.items()) + list(MERGE_SYMBOLS.items())]:
+            + list(XATTN_SPLIT_SYMBOLS.items()) + list(MERGE_SYMBOLS.items()) + list(ATTN_EVAL_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

@@ -1,5 +1,6 @@
 // The differentiable fp32 attention of the decoder, stated once for its two instances (cross_attention_train.hip,
-// self_attention_train.hip): forward with the row statistics kept, and a backward that recomputes the probabilities.  Operands
+// self_attention_train.hip): forward with the row statistics kept, and a backward that recomputes the probabilities; and the
+// same forward without them for evaluation (attention_eval.hip: attn_fwd's LSE and AHEAD).  Operands
 // are fp32 rows [rows, N, heads * 16]; per head a query or key row has two 16-dim halves (a, b), and a policy F says what the
 // score makes of them:
 //   F::HALVES == 2 (cross)  the row is [a | b]: score = scale * (q_a . k_a + q_b . k_b), every half has a gradient of its own
@@ -124,16 +125,41 @@ struct Head {
   }
 };
 
+// the two policies: the decoder's cross-attention (cross_attention_train.hip, attention_eval.hip) ...
+struct Cross {
+  static constexpr int HALVES = 2;
+  static constexpr bool MASKED = true;
+  static __device__ int keys(const Geo &geo) { return geo.S; }
+};
+// ... and its self-attention (self_attention_train.hip, attention_eval.hip)
+struct Self {
+  static constexpr int HALVES = 1;
+  static constexpr bool MASKED = false;
+  static __device__ int keys(const Geo &geo) { return geo.Q; }   // the keys are the queries: one register
+};
+
 // ---- operands and the score tile ------------------------------------------------------------------------------------------
 template <class F>
 struct Row {   // a lane's four dims of a query or key row, as the score takes them
   d4 h[F::HALVES];
 };
+struct RawRow {   // the same four dims as the two loads deliver them: what a wave can hold ahead of the arithmetic
+  float4 a, b;
+};
+__device__ __forceinline__ RawRow load_raw(const float *a, const float *b, const Head &hd, const int row, const int g)
+{
+  return {hd.row4(a, row, g), hd.row4(b, row, g)};
+}
+template <class F>
+__device__ __forceinline__ Row<F> cook(const RawRow &w)
+{
+  if constexpr (F::HALVES == 2) return {{widen(w.a), widen(w.b)}};
+  else return {{widen(add4(w.a, w.b))}};
+}
 template <class F>
 __device__ __forceinline__ Row<F> load_row(const float *a, const float *b, const Head &hd, const int row, const int g)
 {
-  if constexpr (F::HALVES == 2) return {{widen(hd.row4(a, row, g)), widen(hd.row4(b, row, g))}};
-  else return {{widen(add4(hd.row4(a, row, g), hd.row4(b, row, g)))}};
+  return cook<F>(load_raw(a, b, hd, row, g));
 }
 // dim c of a row, one float per half: the A operand of the fp32 product that contracts over rows
 template <class F>
@@ -225,7 +251,82 @@ __device__ __forceinline__ float prob(const f64x4 s, const int r, const double d
 }
 
 // ---- forward --------------------------------------------------------------------------------------------------------------
+// What a wave reads from memory for one 16-key step, unconverted: lane (c, g)'s four dims of key row k0 + c (both operands), dim
+// c of the value rows k0 + g + 4 r and the mask bytes of those keys in the lane's query row.  Rows beyond S - 1 repeat row
+// S - 1 and are dead in fwd_step; no address lies behind the last row.  A masked position's byte is read only where the row
+// has a mask and is not open (key_dead's rule, taken at load time: mk[r] != 0 is "masked")
 template <class F>
+struct FwdTile {
+  RawRow k;
+  float va[4];
+  unsigned char mk[4];
+};
+template <class F>
+__device__ __forceinline__ FwdTile<F> fwd_load(const float *k_a, const float *k_b, const float *v, const Head &hd, const MaskRow &m,
+                                               const int k0, const int S, const int c, const int g)
+{
+  FwdTile<F> t;
+  t.k = load_raw(k_a, k_b, hd, min(k0 + c, S - 1), g);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int kk = k0 + g + 4 * r;
+    t.va[r] = v[hd.idx(min(kk, S - 1), c)];
+    t.mk[r] = 0;
+    if constexpr (F::MASKED)
+      if (!m.open && kk < S) t.mk[r] = m.row[kk];
+  }
+  return t;
+}
+// a wave's running softmax of its steps: per lane the row maximum and row sum of query c, and O[query c][value dim 4 g + r]
+struct FwdState {
+  double m_run;
+  float l_run;
+  f32x4 o;
+};
+// one step of the online softmax on the tile at k0
+template <class F>
+__device__ __forceinline__ void fwd_step(FwdState &st, const FwdTile<F> &t, const Row<F> &qa, const int k0, const int S, const int g,
+                                         const double dscale)
+{
+  const Row<F> ka = cook<F>(t.k);
+  float p[4];
+  double x[4];
+  double mx = -INFINITY;
+  const f64x4 s = score<F>(ka, qa);                                   // s[r] = score^T[key k0 + g + 4 r][query c] / scale
+  bool dead[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    dead[r] = k0 + g + 4 * r >= S || (F::MASKED && t.mk[r] != 0);
+    x[r] = s[r] * dscale;
+    mx = fmax(mx, dead[r] ? -INFINITY : x[r]);
+  }
+  mx = xgroup_max_f64(mx);                                            // not MASKED: finite, key k0 exists
+  const double m_new = fmax(st.m_run, mx);
+  double m_safe = m_new;
+  if constexpr (F::MASKED) m_safe = m_new == -INFINITY ? 0. : m_new;     // nothing attendable yet: keep everything 0
+  const float alpha = expf((float)(st.m_run - m_safe));               // exp(-inf) = 0 on the first live step
+  float rsum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    p[r] = dead[r] ? 0.f : expf((float)(x[r] - m_safe));
+    rsum += p[r];
+  }
+  rsum = xgroup_sum(rsum);
+  st.l_run = fmaf(st.l_run, alpha, rsum);                            // (fused by name, here and in the merge: see attn_fwd)
+  st.m_run = m_new;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) st.o[r] *= alpha;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) st.o = mfma4(t.va[r], p[r], st.o);      // o[r] = O[query c][value dim 4 g + r]
+}
+
+// LSE: the row statistics are written for a backward (training).  AHEAD: the wave issues the loads of its next step before the
+// arithmetic of the current one and keeps that one FwdTile in registers (evaluation: thousands of keys, 89 steps a wave at 5 655,
+// each of which would otherwise begin with its own trip to memory).  Neither changes an operation on the way to `out`: the
+// two forms give the same bits.  Every multiply-add of the forward is an fmaf by name: left to the compiler, whether a
+// product and a sum are fused is decided per instantiation (with lse to form, the merge's came out as v_pk_mul_f32 and adds;
+// without, as v_pk_fma_f32 -- one ulp apart).
+template <class F, bool LSE, bool AHEAD>
 __device__ __forceinline__ void attn_fwd(const float *q_a, const float *q_b, const float *k_a, const float *k_b, const float *v,
                                          const unsigned char *mask, const unsigned char *row_open, const Geo geo,
                                          const float scale, float *out, float *lse)
@@ -240,51 +341,30 @@ __device__ __forceinline__ void attn_fwd(const float *q_a, const float *q_b, con
   const Row<F> qa = load_row<F>(q_a, q_b, hd, q, g);
   const MaskRow m = mask_row<F>(mask, row_open, n, Q, S, q);
   const double dscale = (double)scale;
+  constexpr int STEP = 16 * AT_WAVES;
 
-  double m_run = -INFINITY;
-  float l_run = 0.f;
-  f32x4 o = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = wave * 16; k0 < S; k0 += 16 * AT_WAVES) {
-    const Row<F> ka = load_row<F>(k_a, k_b, hd, min(k0 + c, S - 1), g);
-    float va[4], p[4];
-    double x[4];
-    double mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) va[r] = v[hd.idx(min(k0 + g + 4 * r, S - 1), c)];
-    const f64x4 s = score<F>(ka, qa);                                 // s[r] = score^T[key k0 + g + 4 r][query c] / scale
-    bool dead[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dead[r] = key_dead<F>(m, k0 + g + 4 * r, S);
-      x[r] = s[r] * dscale;
-      mx = fmax(mx, dead[r] ? -INFINITY : x[r]);
+  FwdState st = {-INFINITY, 0.f, {0.f, 0.f, 0.f, 0.f}};
+  if constexpr (AHEAD) {
+    int k0 = wave * 16;
+    if (k0 < S) {
+      FwdTile<F> cur = fwd_load<F>(k_a, k_b, v, hd, m, k0, S, c, g);
+      for (; k0 + STEP < S; k0 += STEP) {
+        const FwdTile<F> nxt = fwd_load<F>(k_a, k_b, v, hd, m, k0 + STEP, S, c, g);   // in flight during the step below
+        fwd_step<F>(st, cur, qa, k0, S, g, dscale);
+        cur = nxt;
+      }
+      fwd_step<F>(st, cur, qa, k0, S, g, dscale);                     // the wave's last step: nothing is loaded behind it
     }
-    mx = xgroup_max_f64(mx);                                          // not MASKED: finite, key k0 exists
-    const double m_new = fmax(m_run, mx);
-    double m_safe = m_new;
-    if constexpr (F::MASKED) m_safe = m_new == -INFINITY ? 0. : m_new;   // nothing attendable yet: keep everything 0
-    const float alpha = expf((float)(m_run - m_safe));                // exp(-inf) = 0 on the first live step
-    float rsum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[r] = dead[r] ? 0.f : expf((float)(x[r] - m_safe));
-      rsum += p[r];
-    }
-    rsum = xgroup_sum(rsum);
-    l_run = l_run * alpha + rsum;
-    m_run = m_new;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o[r] *= alpha;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o = mfma4(va[r], p[r], o);            // o[r] = O[query c][value dim 4 g + r]
+  } else {
+    for (int k0 = wave * 16; k0 < S; k0 += STEP) fwd_step<F>(st, fwd_load<F>(k_a, k_b, v, hd, m, k0, S, c, g), qa, k0, S, g, dscale);
   }
 
   if (g == 0) {
-    s_m[wave][c] = m_run;
-    s_l[wave][c] = l_run;
+    s_m[wave][c] = st.m_run;
+    s_l[wave][c] = st.l_run;
   }
 #pragma unroll
-  for (int r = 0; r < 4; ++r) s_o[wave][c][4 * g + r] = o[r];
+  for (int r = 0; r < 4; ++r) s_o[wave][c][4 * g + r] = st.o[r];
   __syncthreads();
   // the four waves' partial softmaxes, merged in wave order: thread (query tq, value dim td).  A wave without a live step holds
   // (-inf, 0, 0) and enters with the factor exp(-inf) = 0; not MASKED, wave 0 always has a key and the maximum is finite
@@ -297,16 +377,18 @@ __device__ __forceinline__ void attn_fwd(const float *q_a, const float *q_b, con
 #pragma unroll
     for (int w = 0; w < AT_WAVES; ++w) {
       const float f = expf((float)(s_m[w][tq] - mm));
-      l += s_l[w][tq] * f;
-      acc += s_o[w][tq][td] * f;
+      l = fmaf(s_l[w][tq], f, l);
+      acc = fmaf(s_o[w][tq][td], f, acc);
     }
   }
   if (q0 + tq < Q) {
     const bool live = !F::MASKED || l > 0.f;
     out[hd.idx(q0 + tq, td)] = live ? acc / l : 0.f;
-    if (td == 0) {
-      const double e = live ? mm + log((double)l) : 0.0;
-      write_lse(lse, e, ((size_t)n * geo.heads + h) * Q + q0 + tq, (size_t)geo.N * geo.heads * Q);
+    if constexpr (LSE) {
+      if (td == 0) {
+        const double e = live ? mm + log((double)l) : 0.0;
+        write_lse(lse, e, ((size_t)n * geo.heads + h) * Q + q0 + tq, (size_t)geo.N * geo.heads * Q);
+      }
     }
   }
 }

@@ -1062,7 +1062,7 @@ int pct_cross_attention_split_keys_bf16(const void *q_content, const void *q_pos
                                                            static_cast<hipStream_t>(stream)));
 }
 
-// The argument checks of the four differentiable fp32 attention entries, in the order the ABI fixes: a negative size or no head,
+// The argument checks of the four differentiable fp32 attention entries and of the two evaluation ones, in the order the ABI fixes: a negative size or no head,
 // the empty call (nothing is read, every pointer may be null), a null pointer, a pointer off 16 bytes (self-attention:
 // num_key = num_query).  -> true: launch; false: return *status.
 static bool attn_train_args(int batch, int heads, int num_query, int num_key, std::initializer_list<const void *> ptrs,
@@ -1133,6 +1133,25 @@ int pct_self_attention_backward_f32(const float *q_content, const float *q_pos, 
   return abi_status(pct::launch_self_attention_bwd_f32(q_content, q_pos, k_content, k_pos, v, lse, grad_out, batch, heads,
                                                        num_query, scale, workspace, grad_q, grad_k, grad_v,
                                                        static_cast<hipStream_t>(stream)));
+}
+
+int pct_cross_attention_eval_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,
+                                 const float *v, const unsigned char *mask, const unsigned char *row_open, int batch, int heads,
+                                 int num_query, int num_key, float scale, float *out, void *stream)
+{
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_key, {q_content, q_pos, k_content, k_pos, v, out}, &status)) return status;
+  return abi_status(pct::launch_cross_attention_eval_f32(q_content, q_pos, k_content, k_pos, v, mask, mask ? row_open : nullptr, batch,
+                                                         heads, num_query, num_key, scale, out, static_cast<hipStream_t>(stream)));
+}
+
+int pct_self_attention_eval_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,
+                                const float *v, int batch, int heads, int num_query, float scale, float *out, void *stream)
+{
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_query, {q_content, q_pos, k_content, k_pos, v, out}, &status)) return status;
+  return abi_status(pct::launch_self_attention_eval_f32(q_content, q_pos, k_content, k_pos, v, batch, heads, num_query, scale, out,
+                                                        static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

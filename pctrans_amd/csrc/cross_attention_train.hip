@@ -15,19 +15,13 @@
 namespace pct {
 namespace {
 
-struct Cross {
-  static constexpr int HALVES = 2;
-  static constexpr bool MASKED = true;
-  static __device__ int keys(const Geo &geo) { return geo.S; }
-};
-
 __global__ __launch_bounds__(AT_THREADS) void xat_fwd_kernel(const float *__restrict__ q_c, const float *__restrict__ q_s,
                                                               const float *__restrict__ k_c, const float *__restrict__ k_p,
                                                               const float *__restrict__ v, const unsigned char *__restrict__ mask,
                                                               const unsigned char *__restrict__ row_open, const Geo geo,
                                                               const float scale, float *__restrict__ out, float *__restrict__ lse)
 {
-  attn_fwd<Cross>(q_c, q_s, k_c, k_p, v, mask, row_open, geo, scale, out, lse);
+  attn_fwd<Cross, true, false>(q_c, q_s, k_c, k_p, v, mask, row_open, geo, scale, out, lse);
 }
 
 __global__ __launch_bounds__(AT_THREADS) void xat_delta_kernel(const float *__restrict__ q_c, const float *__restrict__ q_s,

@@ -216,6 +216,13 @@ int launch_self_attention_fwd_f32(const float *q_c, const float *q_p, const floa
 int launch_self_attention_bwd_f32(const float *q_c, const float *q_p, const float *k_c, const float *k_p, const float *v,
                                   const float *lse, const float *grad_out, int N, int heads, int Q, float scale, float *workspace,
                                   float *grad_q, float *grad_k, float *grad_v, hipStream_t stream);
+// the same two forwards for evaluation: no lse, any query count, loads one step ahead (attention_eval.hip;
+// include/pctrans_hip_attn_eval.h).  PCT_NOT_COVERED: heads outside {4, 8} or an operand of 2^31 elements or more
+int launch_cross_attention_eval_f32(const float *q_c, const float *q_s, const float *k_c, const float *k_p, const float *v,
+                                    const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S,
+                                    float scale, float *out, hipStream_t stream);
+int launch_self_attention_eval_f32(const float *q_c, const float *q_p, const float *k_c, const float *k_p, const float *v, int N,
+                                   int heads, int Q, float scale, float *out, hipStream_t stream);
 int launch_lsap(const float *cost, int batch, int num_query, int ld_target, const int *num_target, int *row_for_target,
                 int *status, hipStream_t stream);
 

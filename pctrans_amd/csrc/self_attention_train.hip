@@ -24,18 +24,12 @@ namespace {
 
 constexpr int SAT_MAX_Q = 512;             // rows of the LDS image of k and v in sat_bwd_q_kernel
 
-struct Self {
-  static constexpr int HALVES = 1;
-  static constexpr bool MASKED = false;
-  static __device__ int keys(const Geo &geo) { return geo.Q; }   // the keys are the queries: one register
-};
-
 __global__ __launch_bounds__(AT_THREADS) void sat_fwd_kernel(const float *__restrict__ q_c, const float *__restrict__ q_p,
                                                               const float *__restrict__ k_c, const float *__restrict__ k_p,
                                                               const float *__restrict__ v, const Geo geo, const float scale,
                                                               float *__restrict__ out, float *__restrict__ lse)
 {
-  attn_fwd<Self>(q_c, q_p, k_c, k_p, v, nullptr, nullptr, geo, scale, out, lse);
+  attn_fwd<Self, true, false>(q_c, q_p, k_c, k_p, v, nullptr, nullptr, geo, scale, out, lse);
 }
 
 __global__ __launch_bounds__(AT_THREADS) void sat_bwd_q_kernel(const float *__restrict__ q_c, const float *__restrict__ q_p,

@@ -31,6 +31,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
+from .. import attention_eval
 from .. import attention_train
 from .. import dynamic_mask_head as dmh
 from .. import fused_ops
@@ -113,6 +114,9 @@ class SelfAttentionLayer(nn.Module):
         # kernels (self_attention_train.py) instead of the torch chain.  A plain attribute; process default from
         # PCT_SELF_ATTN_TRAIN
         self.self_attn_train = self_attention_train.default()
+        # "hip": when no gradient is required, fp32 operands outside autocast without a mask go through the forward-only kernel
+        # (attention_eval.py) instead of the torch chain.  A plain attribute; process default from PCT_ATTN_EVAL
+        self.attn_eval = attention_eval.default()
         _xavier_all(self)
 
     def forward_post(self, tgt, tgt_mask: Optional[Tensor] = None, tgt_key_padding_mask: Optional[Tensor] = None,
@@ -129,6 +133,17 @@ class SelfAttentionLayer(nn.Module):
                  and tgt.shape[2] // h == 16 and self.self_attn.dropout == 0.0)
         if train and self_attention_train.supported(q_c, q_p, k_c, k_p, v, h):
             core = self_attention_train.self_attention_train(q_c, q_p, k_c, k_p, v, h)
+            return self.norm1(tgt + self.dropout1(self.self_attn.out_proj(core)))
+        if self.attn_eval not in ("torch", "hip"):
+            raise ValueError("SelfAttentionLayer.attn_eval must be 'torch' or 'hip', got %r" % (self.attn_eval,))
+        # ... and so does the forward-only kernel, where nothing needs a gradient
+        evalk = (self.attn_eval == "hip" and tgt_mask is None and tgt_key_padding_mask is None
+                 and v.is_cuda and v.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+                 and not (torch.is_grad_enabled() and (q_c.requires_grad or q_p.requires_grad or k_c.requires_grad
+                                                       or k_p.requires_grad or v.requires_grad))
+                 and tgt.shape[2] // h == 16 and (self.self_attn.dropout == 0.0 or not self.self_attn.training))
+        if evalk and attention_eval.supported(q_c, q_p, k_c, k_p, v, h):
+            core = attention_eval.self_attention(q_c, q_p, k_c, k_p, v, h)
             return self.norm1(tgt + self.dropout1(self.self_attn.out_proj(core)))
         q = q_c + q_p
         k = k_c + k_p
@@ -162,6 +177,9 @@ class CrossAttentionLayer(nn.Module):
         # workgroups and combine the partial results in a second launch (split_key_attention.py), whatever the key count.  A
         # plain attribute; process default from PCT_XATTN_SPLIT_KEYS
         self.split_keys = split_key_attention.default()
+        # "hip": when no gradient is required, fp32 operands outside autocast go through the forward-only split-operand kernel
+        # (attention_eval.py) instead of the torch chain.  A plain attribute; process default from PCT_ATTN_EVAL
+        self.attn_eval = attention_eval.default()
         _xavier_all(self)
 
     def forward_post(self, tgt, memory, memory_mask: Optional[Tensor] = None,
@@ -206,7 +224,20 @@ class CrossAttentionLayer(nn.Module):
                  and C // h == 16 and self.cross_attn.dropout == 0.0
                  and (memory_mask is None or (memory_mask.dtype == torch.bool
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
-        if memory_row_open is not None and memory_mask is not None and not split and not ragged and not splitk and not train:
+        if self.attn_eval not in ("torch", "hip"):
+            raise ValueError("CrossAttentionLayer.attn_eval must be 'torch' or 'hip', got %r" % (self.attn_eval,))
+        # ... and so does their forward-only form, where nothing needs a gradient
+        evalk = (self.attn_eval == "hip" and not fused and memory_key_padding_mask is None
+                 and k.is_cuda and k.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+                 and not (torch.is_grad_enabled() and (
+                     tgt.requires_grad or memory.requires_grad or q.requires_grad or k.requires_grad or k_pos.requires_grad
+                     or self.ca_v_proj.weight.requires_grad or self.ca_qpos_sine_proj.weight.requires_grad
+                     or self.ca_qpos_proj.weight.requires_grad))
+                 and C // h == 16 and (self.cross_attn.dropout == 0.0 or not self.cross_attn.training)
+                 and (memory_mask is None or (memory_mask.dtype == torch.bool
+                                              and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
+        if (memory_row_open is not None and memory_mask is not None and not split and not ragged and not splitk and not train
+                and not evalk):
             memory_mask = memory_mask & ~memory_row_open
             memory_row_open = None
         if fused and not split and not ragged and not splitk:
@@ -238,6 +269,9 @@ class CrossAttentionLayer(nn.Module):
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
         if train and attention_train.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
             core = attention_train.cross_attention_train(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
+            return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
+        if evalk and attention_eval.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
+            core = attention_eval.cross_attention(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
         if memory_row_open is not None and memory_mask is not None:
             memory_mask = memory_mask & ~memory_row_open
