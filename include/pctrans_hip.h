@@ -197,6 +197,8 @@ PCT_API int pct_dynamic_mask_head_forward_fused_bf16(const float *mask_feat, con
 #include "pctrans_hip_fpn.h"
 /* the decoder's cross-attention with a backward, behind CrossAttentionLayer.attn_train = "hip" */
 #include "pctrans_hip_attn_train.h"
+/* the same with the keys divided over several workgroups and combine steps, behind CrossAttentionLayer.attn_train_split = "hip" */
+#include "pctrans_hip_attn_train_split.h"
 /* the mask side of the query-contrast loss in training, behind MultiScaleMaskedTransformerDecoder.reid_dice = "hip" */
 #include "pctrans_hip_reid.h"
 /* its query side and the per-item reduction of both, behind MultiScaleMaskedTransformerDecoder.reid_query = "hip" and

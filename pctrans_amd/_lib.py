@@ -122,6 +122,18 @@ ATTN_TRAIN_SYMBOLS = {
                                          "tests/test_attention_train_gpu.py"),
 }
 
+# Entry points of the same cross-attention with the keys of every query-side workgroup divided over several workgroups
+# (include/pctrans_hip_attn_train_split.h; pctrans_amd/split_key_attention_train.py, reached with
+# CrossAttentionLayer.attn_train_split = "hip").  A table of its own, as the unsplit entries': name -> (argtypes, restype, the test
+# module that checks the entry against those entries, bit for bit, and against float64)
+ATTN_TRAIN_SPLIT_SYMBOLS = {
+    "pct_cross_attention_split_train_workspace": ([_i] * 4, ctypes.c_longlong, "tests/test_split_key_attention_train_gpu.py"),
+    "pct_cross_attention_split_forward_f32": ([_vp] * 7 + [_i] * 4 + [ctypes.c_float, _i, _vp, ctypes.c_longlong, _vp, _vp, _vp], _i,
+                                              "tests/test_split_key_attention_train_gpu.py"),
+    "pct_cross_attention_split_backward_f32": ([_vp] * 10 + [_i] * 4 + [ctypes.c_float, _i, _vp, ctypes.c_longlong] + [_vp] * 6, _i,
+                                               "tests/test_split_key_attention_train_gpu.py"),
+}
+
 # Entry points of the mask side of the query-contrast loss (include/pctrans_hip_reid.h; pctrans_amd/reid_dice.py, reached with
 # MultiScaleMaskedTransformerDecoder.reid_dice = "hip").  A table of its own, as the attention's: name -> (argtypes, restype,
 # the test module that checks the entry against float64)
@@ -244,7 +256,8 @@ def lib():
             + list(FPN_SYMBOLS.items()) + list(ATTN_TRAIN_SYMBOLS.items()) + list(REID_SYMBOLS.items()) + list(TARGETS_SYMBOLS.items())
             + list(MSDA_TRAIN_SYMBOLS.items()) + list(REID_QUERY_SYMBOLS.items()) + list(METRICS_SYMBOLS.items())
             + list(SELF_ATTN_TRAIN_SYMBOLS.items()) + list(AUX_LOSS_SYMBOLS.items()) + list(XATTN_SYMBOLS.items())
-            + list(XATTN_SPLIT_SYMBOLS.items()) + list(MERGE_SYMBOLS.items()) + list(ATTN_EVAL_SYMBOLS.items())]:
+            + list(XATTN_SPLIT_SYMBOLS.items()) + list(MERGE_SYMBOLS.items()) + list(ATTN_EVAL_SYMBOLS.items())
+            + list(ATTN_TRAIN_SPLIT_SYMBOLS.items())]:
         try:
             fn = getattr(l, name)
         except AttributeError as e:

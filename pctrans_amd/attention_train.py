@@ -17,6 +17,8 @@ HEAD_DIM = 16
 _HEADS = (4, 8)
 # Measured as replays of a HIP graph of one forward + backward (tools/bench_attn_train.py, N = 2, 8 heads): the kernels take 0.38 -
 # 0.92 x the torch chain's time up to 1 024 keys and 1.13 - 1.30 x at 3 136 and 4 096.  Key counts in between were not timed.
+# Beyond MAX_KEYS the same kernels with the keys of a workgroup divided over several are the faster path
+# (split_key_attention_train.py, CrossAttentionLayer.attn_train_split; profiles/attn_train_split.json).
 MAX_KEYS = 1024
 
 

@@ -1062,7 +1062,7 @@ int pct_cross_attention_split_keys_bf16(const void *q_content, const void *q_pos
                                                            static_cast<hipStream_t>(stream)));
 }
 
-// The argument checks of the four differentiable fp32 attention entries and of the two evaluation ones, in the order the ABI fixes: a negative size or no head,
+// The argument checks of the four differentiable fp32 attention entries, of the two split-key ones and of the two evaluation ones, in the order the ABI fixes: a negative size or no head,
 // the empty call (nothing is read, every pointer may be null), a null pointer, a pointer off 16 bytes (self-attention:
 // num_key = num_query).  -> true: launch; false: return *status.
 static bool attn_train_args(int batch, int heads, int num_query, int num_key, std::initializer_list<const void *> ptrs,
@@ -1107,6 +1107,49 @@ int pct_cross_attention_backward_f32(const float *q_content, const float *q_pos,
                                                         grad_out, batch, heads, num_query, num_key, scale, workspace, grad_q_content,
                                                         grad_q_pos, grad_k_content, grad_k_pos, grad_v,
                                                         static_cast<hipStream_t>(stream)));
+}
+
+long long pct_cross_attention_split_train_workspace(int batch, int heads, int num_query, int splits)
+{
+  if (batch < 0 || heads <= 0 || num_query < 0 || splits < 1 || splits > 16) return PCT_ERR_BAD_ARG;
+  if (heads != 4 && heads != 8) return PCT_ERR_UNSUPPORTED;
+  return pct::cross_attention_split_train_workspace(batch, heads, num_query, splits);
+}
+
+// the unsplit entries' checks with the workspace among the pointers; the launchers go on with the geometry, `splits` and
+// workspace_bytes, all before their first launch
+int pct_cross_attention_split_forward_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,
+                                          const float *v, const unsigned char *mask, const unsigned char *row_open, int batch,
+                                          int heads, int num_query, int num_key, float scale, int splits, void *workspace,
+                                          long long workspace_bytes, float *out, float *lse, void *stream)
+{
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_key, {q_content, q_pos, k_content, k_pos, v, out, lse, workspace}, &status))
+    return status;
+  return abi_status(pct::launch_cross_attention_split_fwd_f32(q_content, q_pos, k_content, k_pos, v, mask, mask ? row_open : nullptr,
+                                                              batch, heads, num_query, num_key, scale, splits, workspace,
+                                                              workspace_bytes, out, lse, static_cast<hipStream_t>(stream)));
+}
+
+int pct_cross_attention_split_backward_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,
+                                           const float *v, const unsigned char *mask, const unsigned char *row_open,
+                                           const float *out, const float *lse, const float *grad_out, int batch, int heads,
+                                           int num_query, int num_key, float scale, int splits, void *workspace,
+                                           long long workspace_bytes, float *grad_q_content, float *grad_q_pos,
+                                           float *grad_k_content, float *grad_k_pos, float *grad_v, void *stream)
+{
+  int status;
+  if (!attn_train_args(batch, heads, num_query, num_key,
+                       {q_content, q_pos, k_content, k_pos, v, lse, grad_out, workspace, grad_q_content, grad_q_pos,
+                        grad_k_content, grad_k_pos, grad_v},
+                       &status))
+    return status;
+  (void)out;
+  return abi_status(pct::launch_cross_attention_split_bwd_f32(q_content, q_pos, k_content, k_pos, v, mask, mask ? row_open : nullptr,
+                                                              lse, grad_out, batch, heads, num_query, num_key, scale, splits,
+                                                              workspace, workspace_bytes, grad_q_content, grad_q_pos,
+                                                              grad_k_content, grad_k_pos, grad_v,
+                                                              static_cast<hipStream_t>(stream)));
 }
 
 int pct_self_attention_forward_f32(const float *q_content, const float *q_pos, const float *k_content, const float *k_pos,

@@ -209,6 +209,21 @@ int launch_cross_attention_bwd_f32(const float *q_c, const float *q_s, const flo
                                    const float *grad_out, int N, int heads, int Q, int S, float scale, float *workspace,
                                    float *grad_q_c, float *grad_q_s, float *grad_k_c, float *grad_k_p, float *grad_v,
                                    hipStream_t stream);
+// the same with the keys of every query-side workgroup divided over min(splits, ceil(S / 64)) workgroups and combine launches
+// (cross_attention_train_split.hip; include/pctrans_hip_attn_train_split.h).  After that launcher's PCT_NOT_COVERED:
+// PCT_ERR_BAD_ARG for splits outside 1 .. 16, a null workspace or workspace_bytes below the need; PCT_ERR_ALIGNMENT for a
+// workspace off 16 bytes -- all before any launch.  Forward 2 launches, backward 4
+int launch_cross_attention_split_fwd_f32(const float *q_c, const float *q_s, const float *k_c, const float *k_p, const float *v,
+                                         const unsigned char *mask, const unsigned char *row_open, int N, int heads, int Q, int S,
+                                         float scale, int splits, void *workspace, long long workspace_bytes, float *out,
+                                         float *lse, hipStream_t stream);
+int launch_cross_attention_split_bwd_f32(const float *q_c, const float *q_s, const float *k_c, const float *k_p, const float *v,
+                                         const unsigned char *mask, const unsigned char *row_open, const float *lse,
+                                         const float *grad_out, int N, int heads, int Q, int S, float scale, int splits,
+                                         void *workspace, long long workspace_bytes, float *grad_q_c, float *grad_q_s,
+                                         float *grad_k_c, float *grad_k_p, float *grad_v, hipStream_t stream);
+// bytes of that workspace, enough for either direction: with R = N * heads * Q, 136 * splits * R + 4 * R rounded up to 16
+long long cross_attention_split_train_workspace(int N, int heads, int Q, int splits);
 // differentiable fp32 self-attention (self_attention_train.hip; include/pctrans_hip_self_attn_train.h).  PCT_NOT_COVERED: heads
 // outside {4, 8}, more than 512 queries or an operand of 2^31 elements or more.  workspace: N * heads * Q floats
 int launch_self_attention_fwd_f32(const float *q_c, const float *q_p, const float *k_c, const float *k_p, const float *v, int N,

@@ -37,6 +37,7 @@ from .. import dynamic_mask_head as dmh
 from .. import fused_ops
 from .. import ragged_attention
 from .. import split_key_attention
+from .. import split_key_attention_train
 from .. import reid_dice
 from .. import reid_query
 from .. import self_attention_train
@@ -169,6 +170,10 @@ class CrossAttentionLayer(nn.Module):
         # "hip": when a gradient is required, fp32 operands outside autocast go through the differentiable split-operand kernels
         # (attention_train.py) instead of the torch chain.  A plain attribute; process default from PCT_ATTN_TRAIN
         self.attn_train = attention_train.default()
+        # "hip": such calls at key counts the switch above leaves to the torch chain (split_key_attention_train.plan) go through
+        # the same kernels with the keys of every query-side workgroup divided over several (split_key_attention_train.py).
+        # Independent of `attn_train`.  A plain attribute; process default from PCT_ATTN_TRAIN_SPLIT
+        self.attn_train_split = split_key_attention_train.default()
         # "hip": bf16 eval calls whose key count the split-operand kernel does not take (no multiple of 64) go through its ragged
         # form (ragged_attention.py) instead of the concatenations, V^T and the generic kernel.  A plain attribute; process
         # default from PCT_XATTN_RAGGED
@@ -224,6 +229,17 @@ class CrossAttentionLayer(nn.Module):
                  and C // h == 16 and self.cross_attn.dropout == 0.0
                  and (memory_mask is None or (memory_mask.dtype == torch.bool
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
+        if self.attn_train_split not in ("torch", "hip"):
+            raise ValueError("CrossAttentionLayer.attn_train_split must be 'torch' or 'hip', got %r" % (self.attn_train_split,))
+        # ... and so do the same kernels with their keys divided over several workgroups, behind a switch of their own
+        train_split = (self.attn_train_split == "hip" and not fused and memory_key_padding_mask is None and torch.is_grad_enabled()
+                       and k.is_cuda and k.dtype == torch.float32 and not torch.is_autocast_enabled("cuda")
+                       and (tgt.requires_grad or memory.requires_grad or q.requires_grad or k.requires_grad or k_pos.requires_grad
+                            or self.ca_v_proj.weight.requires_grad or self.ca_qpos_sine_proj.weight.requires_grad
+                            or self.ca_qpos_proj.weight.requires_grad)
+                       and C // h == 16 and self.cross_attn.dropout == 0.0
+                       and (memory_mask is None or (memory_mask.dtype == torch.bool
+                                                    and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
         if self.attn_eval not in ("torch", "hip"):
             raise ValueError("CrossAttentionLayer.attn_eval must be 'torch' or 'hip', got %r" % (self.attn_eval,))
         # ... and so does their forward-only form, where nothing needs a gradient
@@ -237,7 +253,7 @@ class CrossAttentionLayer(nn.Module):
                  and (memory_mask is None or (memory_mask.dtype == torch.bool
                                               and tuple(memory_mask.shape) == (bs, 1, Q, hw))))
         if (memory_row_open is not None and memory_mask is not None and not split and not ragged and not splitk and not train
-                and not evalk):
+                and not train_split and not evalk):
             memory_mask = memory_mask & ~memory_row_open
             memory_row_open = None
         if fused and not split and not ragged and not splitk:
@@ -269,6 +285,9 @@ class CrossAttentionLayer(nn.Module):
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
         if train and attention_train.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
             core = attention_train.cross_attention_train(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
+            return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
+        if train_split and split_key_attention_train.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
+            core = split_key_attention_train.cross_attention_train(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
             return self.norm2(tgt + self.dropout2(self.cross_attn.out_proj(core)))
         if evalk and attention_eval.supported(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open):
             core = attention_eval.cross_attention(q, q_side, k, k_pos, v, h, memory_mask, memory_row_open)
